@@ -7,9 +7,16 @@ resident in HBM when the timed region starts.  One process per GPU; tiles are in
 units sharded over ranks (weak scaling).  See DESIGN.md "Measurement".
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + the last timed step's results as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full               # + every side leg (see below)
     python bench.py --gpus N --steps K --warmup W        # starts the N ranks itself (a torch.distributed.run child)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`, `inputs`).
+Everything else moves behind ``--full``: the `one_lane` and `same_batch_every_step` legs, the upload leg (`h2d`), the
+instrumented passes behind `roofline`, the CPU sample (`cpu_baseline`) with the `parity` check of the timed result against the
+CPU path (a failed check nulls `value` and exits 3), and the drop-in CLI leg (`cli`).
 
 Process roles (decided before anything touches the GPU):
 * launcher   -- ``--gpus N > 1`` without WORLD_SIZE: starts the N ranks as a CHILD ``torch.distributed.run``, passes rank 0's JSON
@@ -173,6 +180,66 @@ def load_or_make_device_tiles(first: int, n: int, size: int, dev, cache_dir):
         np.save(path, t.cpu().numpy())
         return t
     return synth.em_tiles_device(range(first, first + n), size, dev)
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_step_outputs(out_dir: str, res, size: int) -> None:
+    """``--dump-outputs``: what a caller of the tile-batch path receives for one step (``res``: per tile the packed masks, scores,
+    classes and contour records), as .npy files that two builds can be compared by.  Instances are numbered in tile order, in
+    the path's own order within a tile.
+
+    * ``scores`` f32, ``classes`` f32, ``tile`` f32 (the tile of the step's batch), ``mask_area`` f64 (pixels): one per instance
+    * ``measurements`` f64 [rows, 12] (the float columns of the measurement CSV, every contour record), ``measurement_instance``,
+      ``contour_area`` and ``contour_perimeter`` f64: one per record
+    * ``mask_row_pixels`` / ``mask_col_pixels`` f32 [S, size]: set pixels per row / column of the instances in ``mask_sample``
+      (f32 instance numbers): every instance, or a fixed seeded sample of them when that would pass the 64 MB bound"""
+    scores, classes, tile, recs, packed = [], [], [], [], []
+    for t, (p, sc, cl, rc) in enumerate(res):
+        if p is None or int(p.shape[0]) == 0:
+            continue
+        packed.append(p)
+        scores += [float(v) for v in sc]
+        classes += [int(c) for c in cl]
+        tile += [t] * int(p.shape[0])
+        recs += list(rc)
+    n = len(scores)
+    meas = [(i, c) for i, cs in enumerate(recs) for c in cs]
+    out = {"scores": np.asarray(scores, dtype=np.float32), "classes": np.asarray(classes, dtype=np.float32),
+           "tile": np.asarray(tile, dtype=np.float32),
+           "measurements": np.asarray([c["values"] for _, c in meas], dtype=np.float64).reshape(len(meas), 12),
+           "measurement_instance": np.asarray([i for i, _ in meas], dtype=np.float64),
+           "contour_area": np.asarray([c["area"] for _, c in meas], dtype=np.float64),
+           "contour_perimeter": np.asarray([c["perimeter"] for _, c in meas], dtype=np.float64)}
+    # the mask profiles take what the bound leaves (8 bytes per instance for mask_area, 4 per sampled instance for mask_sample)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in out.values()) - 8 * n
+    s = max(0, min(n, room // (8 * size + 4)))
+    sample = np.arange(n) if s == n else np.sort(np.random.default_rng(0).choice(n, s, replace=False))
+    area = np.zeros((n,), dtype=np.float64)
+    rows = np.zeros((s, size), dtype=np.float32)
+    cols = np.zeros((s, size), dtype=np.float32)
+    if n:
+        # bit k of word j of a packed row is pixel 32 j + k; unpacked on the device in chunks of about 2^27 pixels
+        allp = torch.cat(packed)
+        shifts = torch.arange(32, dtype=torch.int32, device=allp.device)
+        pos = {int(g): k for k, g in enumerate(sample)}
+        chunk = max(1, 2 ** 27 // (size * size))
+        for a in range(0, n, chunk):
+            p = allp[a:a + chunk]
+            bits = ((p.unsqueeze(-1) >> shifts) & 1).reshape(p.shape[0], p.shape[1], -1)[:, :size, :size]
+            r_ = bits.sum(2, dtype=torch.int64).cpu().numpy()
+            c_ = bits.sum(1, dtype=torch.int64).cpu().numpy()
+            area[a:a + p.shape[0]] = r_.sum(1)
+            for k in range(p.shape[0]):
+                if a + k in pos:
+                    rows[pos[a + k]], cols[pos[a + k]] = r_[k], c_[k]
+    out.update(mask_area=area, mask_row_pixels=rows, mask_col_pixels=cols, mask_sample=sample.astype(np.float32))
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in out.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def cli_leg(sd, depth: int, dev, n_images: int, value: float, tmp_root=None) -> dict:
@@ -467,6 +534,11 @@ def main() -> None:
     ap.add_argument("--eager", action="store_true", help="launch the forward kernel by kernel instead of replaying one hipGraph per batch "
                     "(the default replays: +20 %% tiles/s; per-kernel HIP events cannot be taken inside a replayed graph, so the roofline "
                     "numbers of the default mode come from two instrumented eager steps of the same path, run right after the timed region)")
+    ap.add_argument("--full", action="store_true", help="run every side leg after the timed region as well: one_lane, the instrumented "
+                    "roofline passes, same_batch_every_step, h2d, the CPU sample and its parity check, the CLI leg (the --no-* options "
+                    "above switch single legs off again)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(rank 0's tiles) as DIR/<name>.npy in float32 / float64, at most 64 MB in all (see dump_step_outputs)")
     args = ap.parse_args()
 
     # ---- role (before anything touches the GPU) ----
@@ -679,7 +751,10 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
             time.sleep(0.02)
             return 0, 0
         res = ln.pipe.process_tile_batch(f"step{i}", cur["xs"][i % len(cur["xs"])] if i >= 0 else x, SMALL_CLASSES, CLASS_THRESHOLDS, dets=dets)
-        if not my_lane and (i == parity_step or ln.last.get("keep_every")):
+        if i >= 0 and i == cur.get("dump_step"):
+            # --dump-outputs: the last step of the run is the last one of its lane, nothing overwrites these views before the dump
+            ln.last["dump"] = res
+        if not my_lane and ((args.full and i == parity_step) or ln.last.get("keep_every")):
             # the step whose first tiles are synthetic tiles 0, 1, 2 (the parity check's references); with plane pools the masks
             # are views that the lane's next step overwrites, and later steps follow: keep the checked tiles' own copies
             ln.last["res"] = [((r[0].clone() if r[0] is not None else None),) + tuple(r[1:]) for r in res[:n_par_tiles]]
@@ -782,10 +857,11 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
                 "post_s": sum(ln.last.get("post_s", 0.0) for ln in lanes),
                 "post_after_fwd_s": sum(ln.last.get("post_after_fwd_s", 0.0) for ln in lanes)}
 
-    def run_steps(n_steps, leg="main", n_lanes=None):
+    def run_steps(n_steps, leg="main", n_lanes=None, dump=False):
         """n_steps passes dealt out to the lanes round robin (step i -> lane i % L).  Processes mode: this process runs its own
         lane's share, the rank tells its lane children to run theirs (RUN ... / DONE ...) and adds up their counters; threads
-        mode: one host thread per lane in this process.  ``n_lanes=1``: lane 0 alone (the `one_lane` side leg).
+        mode: one host thread per lane in this process.  ``n_lanes=1``: lane 0 alone (the `one_lane` side leg).  ``dump``: the
+        lane that runs the last step keeps its result as ``last["dump"]`` (a lane child writes it after DONE, then says DUMPED).
         Returns ((instances, rows) of the last step, counters over all lanes)."""
         L = args.lanes if n_lanes is None else n_lanes
         launcher = launcher_of(leg)
@@ -793,8 +869,9 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
         reset_stats()
         outs = [[(0, 0), None] for _ in lanes]
         kids = children is not None and L > 1
+        cur["dump_step"] = n_steps - 1 if dump else None
         if kids:
-            children.send(f"RUN {leg} {n_steps} {stagger_s:.6f}")
+            children.send(f"RUN {leg} {n_steps} {stagger_s:.6f}" + (" 1" if dump else ""))
         if len(lanes) == 1 or L == 1:
             run_lane(lanes[0], list(range(lanes[0].lid if L > 1 else 0, n_steps, L)), outs[0], launcher, stagger_s)
         else:
@@ -812,6 +889,7 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
         for o in outs:
             if o[1] is not None:
                 raise o[1]
+        cur.pop("dump_step", None)
         stats = local_stats()
         last_out = outs[(n_steps - 1) % len(lanes)][0] if (len(lanes) > 1 and L > 1) else outs[0][0]
         if kids:
@@ -842,14 +920,24 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
                 if cmd[0] != "RUN":
                     continue
                 leg, n_steps, xchg["stagger_s"] = cmd[1], int(cmd[2]), float(cmd[3])
+                dump = cmd[4:] == ["1"]
                 try:
-                    out_, st_ = run_steps(n_steps, leg)
+                    out_, st_ = run_steps(n_steps, leg, dump=dump)
                     torch.cuda.synchronize()
                     st_["last"] = list(out_)
                 except BaseException as e:      # the rank raises it
                     st_ = {"error": f"{type(e).__name__}: {e}"}
                 reply.write("DONE " + json.dumps(st_) + "\n")
                 reply.flush()
+                if dump:                        # (after DONE: outside the rank's timed region)
+                    try:
+                        if "dump" in lanes[0].last:
+                            dump_step_outputs(args.dump_outputs, lanes[0].last.pop("dump"), args.size)
+                        st_ = {}
+                    except BaseException as e:
+                        st_ = {"error": f"{type(e).__name__}: {e}"}
+                    reply.write("DUMPED " + json.dumps(st_) + "\n")
+                    reply.flush()
         finally:
             if dist is not None:
                 dist.destroy_process_group()
@@ -882,11 +970,20 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
     # the start offset between lanes: with L forwards in flight a lane's forward takes about L single forwards, so the lanes sit
     # one single forward apart (a pass alone is the forward + ~1/4 of it for the post-processing)
     xchg["stagger_s"] = float(os.environ.get("DEEPEMIA_BENCH_STAGGER", "0.8")) * t_warm if (t_warm and args.lanes > 1) else 0.0      # (the factor: an A/B switch)
-    eng.conv_events = None if (args.no_conv_events or args.graph) else []
+    eng.conv_events = None if (args.no_conv_events or args.graph or not args.full) else []
+    want_dump = bool(args.dump_outputs) and rank == 0
     t0 = time.perf_counter()
-    (det_total, rows_total), st_main = run_steps(args.steps)      # K complete passes
+    (det_total, rows_total), st_main = run_steps(args.steps, dump=want_dump)      # K complete passes
     sync_all()
     dt = time.perf_counter() - t0
+    if want_dump:
+        held = [ln.last.pop("dump") for ln in lanes if "dump" in ln.last]
+        if held:
+            dump_step_outputs(args.dump_outputs, held[0], args.size)
+        if children is not None:
+            for k, rep in enumerate(children.recv("DUMPED")):
+                if rep.get("error"):
+                    raise RuntimeError(f"lane child {k + 1}: {rep['error']}")
     if TRACE is not None:
         for li_, i_, what, t_ in TRACE:
             if i_ >= 0:
@@ -905,12 +1002,12 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
 
     # what the parity leg checks is the TIMED path's own result (graph replay in the default mode): taken here, before
     # anything else runs through the pipeline (total-tiles mode: step 0, the step whose tile 0 is synthetic tile 0)
-    want_parity = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.forward_only
+    want_parity = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.forward_only
     timed_snaps = [snapshot(last["res"], t) for t in range(len(last["res"]))] if (want_parity and "res" in last) else None
     # side leg: the same K passes with lane 0 ALONE (this process, the lane children idle): every line carries its own A/B of
     # the second pipeline, and the conv share below is taken against a one-lane step
     one_lane = None
-    if args.lanes > 1 and not args.no_one_lane_leg:
+    if args.full and args.lanes > 1 and not args.no_one_lane_leg:
         sync_all()
         to = time.perf_counter()
         run_steps(args.steps, "main", n_lanes=1)
@@ -925,7 +1022,7 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
     one_lane_step_ms = one_lane["ms_per_step"] if one_lane else (dt / args.steps * 1e3 if args.lanes == 1 else None)
     instrumented_s, eager_snap = None, None
     n_instr = 2
-    if args.graph and not args.no_conv_events:
+    if args.full and args.graph and not args.no_conv_events:
         # per-kernel HIP events cannot be taken inside a replayed graph: two eager, instrumented passes of the same path
         cur["xs"] = xs
         pipe.use_graphs = False
@@ -945,7 +1042,7 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
         events, eng.conv_events = eng.conv_events, None
         pipe.use_graphs = True
     same_batch = None
-    if len(xs) > 1 and not args.total_tiles and world == 1 and not args.no_h2d_leg:
+    if args.full and len(xs) > 1 and not args.total_tiles and world == 1 and not args.no_h2d_leg:
         # side figure: the loop of rounds 1-3, the SAME resident batch every step (paste and pools see identical boxes)
         sync_all()
         ts = time.perf_counter()
@@ -955,7 +1052,7 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
         same_batch = {"value": args.batch * args.steps / dts, "ms_per_step": dts / args.steps * 1e3,
                       "note": "the same K passes over ONE resident batch repeated every step (the headline loop of rounds 1-3)"}
     h2d = None
-    if world == 1 and not args.no_h2d_leg and not args.forward_only and not args.no_overlap:
+    if args.full and world == 1 and not args.no_h2d_leg and not args.forward_only and not args.no_overlap:
         # second leg: the same K passes with every step's tiles UPLOADED from pinned host memory on a copy stream (two device
         # slots per lane; the forward waits for its upload, the upload of step i+1 runs under the forward of step i)
         launcher_of("h2d")           # (set-up outside the timed region; the lane children do theirs on their first h2d step)
@@ -1013,7 +1110,7 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
         native = (args.min_size_test, args.max_size_test) != (800, 1333)
         if native:
             args.no_cpu_baseline = True        # the oracle sample below is the 800-pixel workload
-        if tf.exists() and args.depth == 101 and args.size == 2048 and not native:
+        if args.full and tf.exists() and args.depth == 101 and args.size == 2048 and not native:
             rec = json.loads(tf.read_text())
             if rec.get("kernel") == kernel_name:
                 traffic = rec.get("hbm_bytes_per_launch")
@@ -1098,7 +1195,9 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
                           "distinct_resident_batches": len(xs),
                           "note": "tile 0 = synth.em_tile(0) (numpy PCG64, seed 1234); weights = synth.random_d2_state_dict(depth, 2, seed=0); "
                                   f"batch 0 = {n_np} numpy tiles + device-generated tiles, the other batches device-generated (seeded per tile)"}
-        if sq.exists():
+        if not args.full:
+            del line["roofline"]          # (no conv launch was timed: the roofline figures come from the --full legs)
+        elif sq.exists():
             rec = json.loads(sq.read_text())
             if rec.get("kernel") == kernel_name:
                 line["roofline"]["mfma_busy_frac"] = rec.get("mfma_busy_frac")
@@ -1151,9 +1250,9 @@ def run_rank(args, world, rank, local_rank, my_lane, proc_lanes, children, reply
             if not ok:
                 line["value_rejected"] = line["value"]
                 line["value"] = None          # a fast path whose results differ from the reference's is not measured
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], _ = cpu_baseline(args.depth, args.size, args.threshold, sd, args.cpu_tiles)
-        if world == 1 and not args.no_cli_leg and not args.forward_only and not native and args.precision == "f16x2" and not args.single_stages \
+        if args.full and world == 1 and not args.no_cli_leg and not args.forward_only and not native and args.precision == "f16x2" and not args.single_stages \
                 and (args.depth, args.size) == (101, 2048):
             # the drop-in CLI on its own workloads, as a subprocess -- with the GPU to itself: the lane children end and this process
             # hands its arenas, graphs and resident batches back first (the CLI's worker processes bring ~45 GiB each)

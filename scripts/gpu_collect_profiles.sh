@@ -15,11 +15,11 @@ timeout -k 10 300 python3 $R/bench.py --forward-only --eager --steps 1 --warmup 
 if [ -z "$PMC_ONLY" ]; then
 echo "[collect] kernel trace of the default bench command (tiles from the cache: every kernel in the trace belongs to the path)"
 # (two lanes = the rank and its lane child, two processes: no -o, rocprofv3 then writes <hostname>/<pid>_kernel_stats.csv per process)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_under_rocprofv3.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_under_rocprofv3.json 2> $O/stats.err || { tail -5 $O/stats.err; exit 1; }
 tail -c 600 $O/bench_under_rocprofv3.json; echo
 # ... and with ONE lane: the conv launches of one pipeline alone, the figure roofline.avg_launch_us (HIP events around every launch of
 # two single-lane eager steps) has to agree with; with two lanes in flight every launch shares the CUs with another grid and lasts longer
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_l1 -o bench -- python3 $R/bench.py --lanes 1 --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_l1_under_rocprofv3.json 2> $O/stats_l1.err || { tail -5 $O/stats_l1.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_l1 -o bench -- python3 $R/bench.py --full --lanes 1 --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_l1_under_rocprofv3.json 2> $O/stats_l1.err || { tail -5 $O/stats_l1.err; exit 1; }
 fi
 # The counter passes run the bench's REAL batches (numpy tiles + device-generated ones, two distinct batches): the generated
 # tiles are made once by an UNPROFILED process and cached as .npy under /tmp, so the profiled processes start from an H2D

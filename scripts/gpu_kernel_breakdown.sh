@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/kb
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -o t -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-h2d-leg "$@" > $O/$tag.json 2> $O/$tag.err || { tail -5 $O/$tag.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -o t -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-h2d-leg "$@" > $O/$tag.json 2> $O/$tag.err || { tail -5 $O/$tag.err; exit 1; }
 f=$(find $O/$tag -name "*kernel_stats.csv" | head -1)
 cp $f $O/${tag}_kernel_stats.csv
 find $O/$tag -type f -delete

@@ -11,7 +11,7 @@ timeout -k 10 300 python3 $R/bench.py --forward-only --eager --steps 1 --warmup 
 for ord in 0 1; do
     export DEEPEMIA_ROI_ORDER=$ord
     echo "[roi A/B] order=$ord kernel trace"
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$ord -o bench -- python3 $R/bench.py --lanes 1 --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_$ord.json 2> $O/stats_$ord.err || { tail -5 $O/stats_$ord.err; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$ord -o bench -- python3 $R/bench.py --full --lanes 1 --steps 6 --warmup 2 --no-cpu-baseline --no-h2d-leg --no-cli-leg --tiles-cache $CACHE > $O/bench_$ord.json 2> $O/stats_$ord.err || { tail -5 $O/stats_$ord.err; exit 1; }
     echo "[roi A/B] order=$ord TCC pass"
     timeout -k 10 240 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/tcc_$ord -o p -- python3 $R/bench.py --forward-only --eager --steps 2 --warmup 1 --no-cpu-baseline --no-h2d-leg --no-cli-leg --lanes 1 --tiles-cache $CACHE > $O/tcc_$ord.json 2> $O/tcc_$ord.err || { tail -20 $O/tcc_$ord.err; exit 1; }
 done

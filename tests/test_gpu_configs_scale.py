@@ -98,7 +98,7 @@ def test_bench_two_ranks_on_one_device_and_total_tiles_mode(gpu_device, tmp_path
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     # no torch.distributed.run here: `--gpus 2` makes bench.py start its ranks itself (default --lanes 2: two ranks x two lanes)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--batch", "4",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--batch", "4", "--full",
            "--no-cpu-baseline", "--lane-mode", lane_mode]
     r = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -117,10 +117,10 @@ def test_bench_two_ranks_on_one_device_and_total_tiles_mode(gpu_device, tmp_path
 
 
 def test_bench_default_line_carries_its_contract(gpu_device):
-    """The default bench command at a small batch: one JSON line with the driver's fields, two lanes, two distinct resident batches,
+    """The full bench command (--full) at a small batch: one JSON line with the driver's fields, two lanes, two distinct resident batches,
     the input hashes (tile 0 is byte-reproducible: numpy PCG64), the side figure of the repeated batch, the upload leg, and the
     parity leg on tile 0 of the last timed step over batch 0."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "6", "--warmup", "1", "--batch", "8", "--parity-only", "--cli-images", "8"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "6", "--warmup", "1", "--batch", "8", "--full", "--parity-only", "--cli-images", "8"],
                        cwd=str(ROOT), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:] + r.stdout[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -150,10 +150,45 @@ def test_bench_default_line_carries_its_contract(gpu_device):
     assert 0.3 < rf["conv_share_of_one_lane_step"] < 1.0 and rf["conv_alone_over_step_period"] > 0
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(gpu_device, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without any side leg; --dump-outputs
+    writes the last timed step's results (float32 / float64, at most 64 MB).  Step 3 of four is lane 1's: a lane child writes it
+    in the default processes mode, the rank process itself in the threads mode -- same inputs, so the same arrays."""
+    dumps = {}
+    for mode in ("processes", "threads"):
+        d = tmp_path / mode
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "4", "--lane-mode", mode,
+                            "--dump-outputs", str(d)], cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 4 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        assert line["unit"] == "tiles/s" and line["higher_is_better"] is True and line["dtype"] == "f16x2"
+        assert line["config"]["lanes"] == 2 and line["config"]["lane_mode"] == mode
+        for key in ("roofline", "parity", "cpu_baseline", "cli", "one_lane", "h2d", "same_batch_every_step"):
+            assert key not in line, key
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 * 2 ** 20
+        dumps[mode] = {f.stem: np.load(f) for f in files}
+        for a in dumps[mode].values():
+            assert a.dtype in (np.float32, np.float64)
+        got = dumps[mode]
+        n = got["scores"].shape[0]
+        assert n > 0 and got["classes"].shape == got["tile"].shape == got["mask_area"].shape == (n,)
+        assert got["measurements"].shape[1] == 12 and got["measurement_instance"].shape[0] == got["measurements"].shape[0] > 0
+        assert np.array_equal(got["mask_row_pixels"].sum(1), got["mask_area"][got["mask_sample"].astype(np.int64)])
+    a, b = dumps["processes"], dumps["threads"]
+    assert sorted(a) == sorted(b)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
 def test_bench_carries_on_with_one_lane_when_the_lane_child_dies(gpu_device):
     """A lane child that cannot start (here: made to exit before its warm-up) must not take the measurement with it: the rank
     continues with lane 0 alone and the line says so."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--no-h2d-leg", "--no-cli-leg"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--no-h2d-leg", "--no-cli-leg"],
                        cwd=str(ROOT), env=dict(os.environ, DEEPEMIA_BENCH_FAIL_LANE_CHILD="1"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -165,7 +200,7 @@ def test_config4_job_of_256_distinct_tiles_at_size(gpu_device):
     """BASELINE configs[4] at its stated size on one GPU: a job of 256 DISTINCT 2048^2 tiles (16 steps of 16; step 0 holds
     the numpy tiles, the rest are generated on the device), the whole per-tile path on every tile, the parity leg on tile 0
     of the timed job (graph replay) against the CPU path, and the eager launch sequence against its replay."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--total-tiles", "256", "--batch", "16", "--warmup", "1", "--parity-only", "--no-cli-leg"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--total-tiles", "256", "--batch", "16", "--warmup", "1", "--full", "--parity-only", "--no-cli-leg"],
                        cwd=str(ROOT), capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:] + r.stdout[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
