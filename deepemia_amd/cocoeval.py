@@ -1,0 +1,384 @@
+"""COCO box / mask AP for the evaluate task: pycocotools' ``COCOeval`` (``useCats=1``) and the mask codecs it relies on,
+with the per-pixel and per-pair work on the MI355X and the greedy matching in native host code.
+
+Device (``csrc/evaluate.hip``): polygon rasterisation with ``rleFrPoly``'s rule (``rasterize_polygons``), the detection x
+ground-truth intersection matrix of one image (``cross_matrix``), column-major run lengths of packed masks
+(``rle_counts``).  Host native (``csrc/hostloops.hip``): ``evaluateImg`` for every (task, category, image, area range, IoU
+threshold) in one call (``match``) and ``rleToString`` (``rle_strings``).  numpy: the IoU tables, ``accumulate`` and
+``summarize``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+MAX_DETS = [1, 10, 100]
+AREA_RNG = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], dtype=np.float64)
+AREA_LBL = ["all", "small", "medium", "large"]
+METRICS = ["AP", "AP50", "AP75", "APs", "APm", "APl"]
+
+
+def _ptr(a: np.ndarray) -> int:
+    return 0 if a is None or a.size == 0 else a.ctypes.data
+
+
+# ---- device ----------------------------------------------------------------------------------------------------------------
+def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, W: int
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``masks[m]`` = the polygons of mask m, each a flat ``[x0, y0, x1, y1, ...]`` list -> packed ``[M, H, ceil(W/32)]`` int32
+    on the device, pixel count ``[M]`` and tight box ``[M, 4]`` (``demia_poly_rasterize``)."""
+    M = len(masks)
+    wpr = (W + 31) // 32
+    out = torch.empty((M, H, wpr), dtype=torch.int32, device=ops.device)
+    area = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    bbox = torch.empty((M, 4), dtype=torch.int32, device=ops.device)
+    if M == 0:
+        return out, area, bbox
+    verts, vert_off, mask_poly = [], [0], [0]
+    for polys in masks:
+        for p in polys:
+            a = np.asarray(p, dtype=np.float64).reshape(-1, 2)
+            verts.append(a)
+            vert_off.append(vert_off[-1] + len(a))
+        mask_poly.append(len(vert_off) - 1)
+    xy = np.ascontiguousarray(np.concatenate(verts) if verts else np.zeros((0, 2)), dtype=np.float64)
+    vo = np.asarray(vert_off, dtype=np.int64)
+    k = np.diff(vo)
+    P, E = len(k), int(vo[-1])
+    edge_poly = np.repeat(np.arange(P), k)
+    edge_idx = np.arange(E) - np.repeat(vo[:-1], k)
+    nxt = np.where(edge_idx + 1 == np.repeat(k, k), np.repeat(vo[:-1], k), np.arange(E) + 1)
+    # room for the kept boundary points: at most one per walk point, max(|dx|, |dy|) + 1 of the x5 lattice per edge
+    span = np.abs(xy[nxt] - xy[np.arange(E)]).max(axis=1) if E else np.zeros((0,))
+    room = np.floor(5.0 * span).astype(np.int64) + 3
+    bnd_off = np.zeros(P + 1, dtype=np.int64)
+    np.cumsum(np.bincount(edge_poly, weights=room, minlength=P).astype(np.int64), out=bnd_off[1:])
+    tab = np.concatenate([vo.astype(np.int32), edge_poly.astype(np.int32), edge_idx.astype(np.int32),
+                          np.asarray(mask_poly, dtype=np.int32)])
+    t_tab = torch.from_numpy(tab).to(ops.device)
+    t_xy = torch.from_numpy(xy if len(xy) else np.zeros((1, 2))).to(ops.device)
+    t_off = torch.from_numpy(bnd_off).to(ops.device)
+    bnd = torch.empty((max(1, int(bnd_off[-1])), 2), dtype=torch.int32, device=ops.device)
+    cnt = torch.zeros((P + 1,), dtype=torch.int32, device=ops.device)           # [P] counters + the error word
+    o_e, o_i, o_m = P + 1, P + 1 + E, P + 1 + 2 * E
+    _lib.check(ops.lib.demia_poly_rasterize(_lib.ptr(t_xy), _lib.ptr(t_tab), _lib.ptr(t_tab[o_e:]) if E else _lib.ptr(t_tab),
+                                            _lib.ptr(t_tab[o_i:]) if E else _lib.ptr(t_tab), _lib.ptr(t_off), _lib.ptr(bnd),
+                                            _lib.ptr(cnt), _lib.ptr(cnt[P:]), E, _lib.ptr(t_tab[o_m:]), M, H, W, _lib.ptr(out),
+                                            _lib.ptr(area), _lib.ptr(bbox), ops._stream()), "demia_poly_rasterize")
+    if int(cnt[P].item()):
+        raise _lib.HipKernelError("demia_poly_rasterize: a boundary list overflowed its room")
+    return out, area, bbox
+
+
+def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Optional[np.ndarray], gt: torch.Tensor,
+                 gt_bbox: torch.Tensor, gt_label: Optional[np.ndarray], W: int) -> torch.Tensor:
+    """``[D, G]`` int32 on the device: ``|det_i & gt_j|``, 0 where the labels differ (``demia_mask_cross_matrix``)."""
+    D, H, _ = det.shape
+    G = int(gt.shape[0])
+    out = torch.zeros((D, max(G, 1)), dtype=torch.int32, device=ops.device)
+    if D == 0 or G == 0:
+        return out[:, :G]
+    tab = np.concatenate([np.zeros(D, np.int32), np.full(D, G, np.int32),
+                          np.asarray(det_label if det_label is not None else np.zeros(D), dtype=np.int32),
+                          np.asarray(gt_label if gt_label is not None else np.zeros(G), dtype=np.int32)])
+    tt = torch.from_numpy(tab).to(ops.device)
+    lab = det_label is not None
+    _lib.check(ops.lib.demia_mask_cross_matrix(_lib.ptr(det), _lib.ptr(det_bbox), _lib.ptr(tt[2 * D:]) if lab else 0, _lib.ptr(gt),
+                                               _lib.ptr(gt_bbox), _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]),
+                                               _lib.ptr(out), D, G, H, W, ops._stream()), "demia_mask_cross_matrix")
+    return out
+
+
+def rle_counts(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Column-major run lengths of every mask, the background run first (pycocotools' ``encode``): ``(counts uint32, offsets
+    [M + 1] int64)`` on the host, mask m's runs at ``counts[offsets[m]:offsets[m + 1]]`` (``demia_mask_rle_colmajor``)."""
+    M, H, _ = packed.shape
+    if M == 0:
+        return np.zeros((0,), np.uint32), np.zeros((1,), np.int64)
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(n), 0, 0, M, H, W, ops._stream()),
+               "demia_mask_rle_colmajor")
+    off = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(n.cpu().numpy(), out=off[1:])
+    t_off = torch.from_numpy(off).to(ops.device)
+    counts = torch.empty((int(off[-1]),), dtype=torch.int32, device=ops.device)
+    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(t_off), _lib.ptr(counts), M, H, W,
+                                               ops._stream()), "demia_mask_rle_colmajor")
+    return counts.cpu().numpy().view(np.uint32), off
+
+
+# ---- host codecs -------------------------------------------------------------------------------------------------------------
+def rle_strings(counts: np.ndarray, offsets: np.ndarray) -> List[str]:
+    """pycocotools' ``rleToString`` of each run list (``demia_host_rle_string``)."""
+    lib = _lib.load()
+    M = len(offsets) - 1
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    cap = max(1, 7 * len(counts))
+    buf = C.create_string_buffer(cap)
+    toff = np.zeros(M + 1, dtype=np.int64)
+    got = lib.demia_host_rle_string(_ptr(counts) or 0, offsets.ctypes.data, M, buf, cap, toff.ctypes.data)
+    if got < 0:
+        raise RuntimeError("demia_host_rle_string: buffer too small")
+    raw = buf.raw[:got].decode("ascii")
+    return [raw[toff[m]:toff[m + 1]] for m in range(M)]
+
+
+def rle_from_string(s: str) -> np.ndarray:
+    """pycocotools' ``rleFrString``: the run lengths of a compressed RLE string."""
+    cnts: List[int] = []
+    p = 0
+    while p < len(s):
+        x = k = 0
+        more = True
+        while more:
+            c = ord(s[p]) - 48
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(cnts) > 2:
+            x += cnts[-2]
+        cnts.append(x & 0xffffffff)
+    return np.asarray(cnts, dtype=np.int64)
+
+
+def rle_decode(counts: Sequence[int], h: int, w: int) -> np.ndarray:
+    """Run lengths (background first, column-major) -> (h, w) bool mask."""
+    flat = np.zeros(h * w, dtype=bool)
+    pos = 0
+    for i, c in enumerate(counts):
+        if i % 2:
+            flat[pos:pos + int(c)] = True
+        pos += int(c)
+    return flat.reshape(w, h).T
+
+
+# ---- IoU tables ---------------------------------------------------------------------------------------------------------------
+def mask_iou(inter: np.ndarray, dt_area: np.ndarray, gt_area: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    """``maskUtils.iou`` of RLEs from the intersection counts: ``i / u`` with ``u = |d| + |g| - i`` (``|d|`` for a crowd
+    ground truth), 0 where ``i == 0``."""
+    i = inter.astype(np.float64)
+    u = np.where(crowd[None, :].astype(bool), dt_area[:, None].astype(np.float64),
+                 dt_area[:, None].astype(np.float64) + gt_area[None, :].astype(np.float64) - i)
+    return np.where(inter > 0, i / np.where(inter > 0, u, 1.0), 0.0)
+
+
+def box_iou(dt: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    """``maskUtils.iou``'s box branch (``bbIou``) on XYWH float64 boxes."""
+    dt = np.asarray(dt, dtype=np.float64).reshape(-1, 4)
+    gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4)
+    da = dt[:, 2] * dt[:, 3]
+    ga = gt[:, 2] * gt[:, 3]
+    w = np.fmin(dt[:, None, 2] + dt[:, None, 0], gt[None, :, 2] + gt[None, :, 0]) - np.fmax(dt[:, None, 0], gt[None, :, 0])
+    h = np.fmin(dt[:, None, 3] + dt[:, None, 1], gt[None, :, 3] + gt[None, :, 1]) - np.fmax(dt[:, None, 1], gt[None, :, 1])
+    i = w * h
+    u = np.where(crowd[None, :].astype(bool), da[:, None], da[:, None] + ga[None, :] - i)
+    ok = (w > 0) & (h > 0)
+    return np.where(ok, i / np.where(ok, u, 1.0), 0.0)
+
+
+# ---- COCOeval --------------------------------------------------------------------------------------------------------------
+class EvalTables:
+    """The entries of one task: per detection (image, category, score, area, its row of the task's IoU table) and per ground
+    truth (image, category, area, crowd, its column).  ``add_image`` appends one image in COCOeval's list order."""
+
+    def __init__(self):
+        self.d_img, self.d_cat, self.d_score, self.d_area, self.d_row = [], [], [], [], []
+        self.g_img, self.g_cat, self.g_area, self.g_crowd, self.g_col = [], [], [], [], []
+        self.iou: List[np.ndarray] = []
+        self._base = 0
+
+    def add_image(self, img: int, d_cat, d_score, d_area, g_cat, g_area, g_crowd, iou: np.ndarray) -> None:
+        D, G = len(d_cat), len(g_cat)
+        self.d_img.append(np.full(D, img, np.int64))
+        self.d_cat.append(np.asarray(d_cat, np.int64))
+        self.d_score.append(np.asarray(d_score, np.float64))
+        self.d_area.append(np.asarray(d_area, np.float64))
+        self.d_row.append(self._base + np.arange(D, dtype=np.int64) * G)
+        self.g_img.append(np.full(G, img, np.int64))
+        self.g_cat.append(np.asarray(g_cat, np.int64))
+        self.g_area.append(np.asarray(g_area, np.float64))
+        self.g_crowd.append(np.asarray(g_crowd, np.uint8))
+        self.g_col.append(np.arange(G, dtype=np.int64))
+        flat = np.ascontiguousarray(iou, dtype=np.float64).reshape(-1)
+        assert flat.size == D * G
+        self.iou.append(flat)
+        self._base += D * G
+
+    def cat(self, name):
+        v = getattr(self, name)
+        return np.concatenate(v) if v else np.zeros((0,))
+
+
+def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Sequence[int]) -> Dict[str, dict]:
+    """``COCOeval.evaluate()`` + ``accumulate()`` for every task of ``tables`` with one native matching call:
+    ``{task: {"precision": [T, R, K, A, M], "recall": [T, K, A, M], "stats": [12]}}``; ``img_ids`` / ``cat_ids`` as
+    ``params.imgIds`` / ``params.catIds`` (sorted)."""
+    img_ids = np.asarray(sorted(img_ids), dtype=np.int64)
+    cat_ids = np.asarray(sorted(cat_ids), dtype=np.int64)
+    tasks = list(tables)
+    # one group per (task, category, image) with a detection or a ground truth; groups in (task, category, image) order,
+    # entries inside a group in the image's list order
+    d_parts, g_parts, ious = [], [], []
+    base = 0
+    for ti, task in enumerate(tasks):
+        t = tables[task]
+        dc = t.cat("d_cat").astype(np.int64)
+        gc = t.cat("g_cat").astype(np.int64)
+        d_parts.append(dict(task=np.full(len(dc), ti), cat=dc, img=t.cat("d_img").astype(np.int64), score=t.cat("d_score"),
+                            area=t.cat("d_area"), row=t.cat("d_row").astype(np.int64) + base))
+        g_parts.append(dict(task=np.full(len(gc), ti), cat=gc, img=t.cat("g_img").astype(np.int64), area=t.cat("g_area"),
+                            crowd=t.cat("g_crowd").astype(np.uint8), col=t.cat("g_col").astype(np.int64)))
+        iou = t.cat("iou").astype(np.float64)
+        ious.append(iou)
+        base += len(iou)
+    d = {k: np.concatenate([p[k] for p in d_parts]) for k in d_parts[0]} if d_parts else {}
+    g = {k: np.concatenate([p[k] for p in g_parts]) for k in g_parts[0]} if g_parts else {}
+    iou = np.ascontiguousarray(np.concatenate(ious) if ious else np.zeros((1,)))
+    nI, nK = len(img_ids), len(cat_ids)
+    img_pos = {int(v): i for i, v in enumerate(img_ids)}
+    cat_pos = {int(v): i for i, v in enumerate(cat_ids)}
+    # keep only entries of listed images / categories (COCOeval's _prepare selects by params)
+    def key_of(part):
+        ip = np.array([img_pos.get(int(v), -1) for v in part["img"]], dtype=np.int64)
+        kp = np.array([cat_pos.get(int(v), -1) for v in part["cat"]], dtype=np.int64)
+        ok = (ip >= 0) & (kp >= 0)
+        return (part["task"] * nK + kp) * nI + ip, ok
+    dkey, dok = key_of(d)
+    gkey, gok = key_of(g)
+    dsel = np.nonzero(dok)[0][np.argsort(dkey[dok], kind="mergesort")]
+    gsel = np.nonzero(gok)[0][np.argsort(gkey[gok], kind="mergesort")]
+    dkey, gkey = dkey[dsel], gkey[gsel]
+    groups = np.union1d(dkey, gkey)
+    Gn = len(groups)
+    dt_off = np.searchsorted(dkey, np.append(groups, np.iinfo(np.int64).max), side="left").astype(np.int64)
+    dt_off[-1] = len(dkey)
+    gt_off = np.searchsorted(gkey, np.append(groups, np.iinfo(np.int64).max), side="left").astype(np.int64)
+    gt_off[-1] = len(gkey)
+    ds = {k: np.ascontiguousarray(v[dsel]) for k, v in d.items()}
+    gs = {k: np.ascontiguousarray(v[gsel]) for k, v in g.items()}
+    ndt, ngt = len(dsel), len(gsel)
+    A, T = len(AREA_RNG), len(IOU_THRS)
+    rank = np.full(ndt, -1, dtype=np.int32)
+    matched = np.zeros((A, T, ndt), dtype=np.uint8)
+    dig = np.zeros((A, T, ndt), dtype=np.uint8)
+    gig = np.zeros((A, ngt), dtype=np.uint8)
+    score = ds["score"].astype(np.float64)
+    darea = ds["area"].astype(np.float64)
+    drow = ds["row"].astype(np.int64)
+    garea = gs["area"].astype(np.float64)
+    gcrowd = gs["crowd"].astype(np.uint8)
+    gcol = gs["col"].astype(np.int64)
+    rng = np.ascontiguousarray(AREA_RNG)
+    thr = np.ascontiguousarray(IOU_THRS)
+    _lib.check(_lib.load().demia_host_coco_match(Gn, dt_off.ctypes.data, gt_off.ctypes.data, _ptr(score), _ptr(darea), _ptr(drow),
+                                                 _ptr(garea), _ptr(gcrowd), _ptr(gcol), iou.ctypes.data, rng.ctypes.data, A,
+                                                 thr.ctypes.data, T, MAX_DETS[-1], _ptr(rank), _ptr(matched), _ptr(dig), _ptr(gig)),
+               "demia_host_coco_match")
+    out = {}
+    R, M = len(REC_THRS), len(MAX_DETS)
+    dgrp = np.searchsorted(groups, dkey) if ndt else np.zeros(0, np.int64)
+    ggrp = np.searchsorted(groups, gkey) if ngt else np.zeros(0, np.int64)
+    for ti, task in enumerate(tasks):
+        precision = -np.ones((T, R, nK, A, M))
+        recall = -np.ones((T, nK, A, M))
+        for k in range(nK):
+            lo_key, hi_key = (ti * nK + k) * nI, (ti * nK + k + 1) * nI
+            dsl = slice(np.searchsorted(dkey, lo_key), np.searchsorted(dkey, hi_key))
+            gsl = slice(np.searchsorted(gkey, lo_key), np.searchsorted(gkey, hi_key))
+            if dsl.stop - dsl.start == 0 and gsl.stop - gsl.start == 0:
+                continue
+            # the detections of this category in COCOeval's concatenation order: image by image, by rank
+            dr = rank[dsl]
+            order = np.lexsort((dr, dgrp[dsl]))
+            for a in range(A):
+                npig = int(np.count_nonzero(gig[a, gsl] == 0))
+                if npig == 0:
+                    continue
+                for mi, maxDet in enumerate(MAX_DETS):
+                    keep = order[(dr[order] >= 0) & (dr[order] < maxDet)]
+                    sc = score[dsl][keep]
+                    inds = np.argsort(-sc, kind="mergesort")
+                    dtm = matched[a][:, dsl][:, keep][:, inds].astype(bool)
+                    dti = dig[a][:, dsl][:, keep][:, inds].astype(bool)
+                    tps = np.logical_and(dtm, np.logical_not(dti))
+                    fps = np.logical_and(np.logical_not(dtm), np.logical_not(dti))
+                    tp_sum = np.cumsum(tps, axis=1).astype(dtype=float)
+                    fp_sum = np.cumsum(fps, axis=1).astype(dtype=float)
+                    for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                        nd = len(tp)
+                        rc = tp / npig
+                        pr = tp / (fp + tp + np.spacing(1))
+                        recall[t, k, a, mi] = rc[-1] if nd else 0
+                        pr = np.maximum.accumulate(pr[::-1])[::-1] if nd else pr
+                        q = np.zeros((R,))
+                        idx = np.searchsorted(rc, REC_THRS, side="left")
+                        ok = idx < nd
+                        q[ok] = pr[idx[ok]]            # recall points past the last detection stay 0
+                        precision[t, :, k, a, mi] = q
+        out[task] = {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+    return out
+
+
+def _summ(precision, recall, ap=1, iou_thr=None, area="all", max_dets=100) -> float:
+    aind = [i for i, lbl in enumerate(AREA_LBL) if lbl == area]
+    mind = [i for i, m in enumerate(MAX_DETS) if m == max_dets]
+    if ap == 1:
+        s = precision
+        if iou_thr is not None:
+            s = s[np.where(iou_thr == IOU_THRS)[0]]
+        s = s[:, :, :, aind, mind]
+    else:
+        s = recall
+        if iou_thr is not None:
+            s = s[np.where(iou_thr == IOU_THRS)[0]]
+        s = s[:, :, aind, mind]
+    return -1.0 if len(s[s > -1]) == 0 else float(np.mean(s[s > -1]))
+
+
+def summarize(precision: np.ndarray, recall: np.ndarray) -> np.ndarray:
+    """``COCOeval.summarize()``'s twelve numbers (``_summarizeDets``)."""
+    m = MAX_DETS
+    return np.array([_summ(precision, recall, 1), _summ(precision, recall, 1, .5, max_dets=m[2]),
+                     _summ(precision, recall, 1, .75, max_dets=m[2]), _summ(precision, recall, 1, area="small", max_dets=m[2]),
+                     _summ(precision, recall, 1, area="medium", max_dets=m[2]), _summ(precision, recall, 1, area="large", max_dets=m[2]),
+                     _summ(precision, recall, 0, max_dets=m[0]), _summ(precision, recall, 0, max_dets=m[1]),
+                     _summ(precision, recall, 0, max_dets=m[2]), _summ(precision, recall, 0, area="small", max_dets=m[2]),
+                     _summ(precision, recall, 0, area="medium", max_dets=m[2]), _summ(precision, recall, 0, area="large", max_dets=m[2])])
+
+
+def summary_lines(stats: np.ndarray) -> List[str]:
+    """The twelve lines ``COCOeval.summarize()`` prints."""
+    spec = [(1, None, "all", 100), (1, .5, "all", 100), (1, .75, "all", 100), (1, None, "small", 100), (1, None, "medium", 100),
+            (1, None, "large", 100), (0, None, "all", 1), (0, None, "all", 10), (0, None, "all", 100), (0, None, "small", 100),
+            (0, None, "medium", 100), (0, None, "large", 100)]
+    lines = []
+    for (ap, thr, area, md), v in zip(spec, stats):
+        title = "Average Precision" if ap == 1 else "Average Recall"
+        typ = "(AP)" if ap == 1 else "(AR)"
+        iou = "{:0.2f}:{:0.2f}".format(IOU_THRS[0], IOU_THRS[-1]) if thr is None else "{:0.2f}".format(thr)
+        lines.append(" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(title, typ, iou, area, md, v))
+    return lines
+
+
+def derive_results(stats: np.ndarray, precision: np.ndarray, class_names: Sequence[str]) -> Dict[str, float]:
+    """Detectron2's ``COCOEvaluator._derive_coco_results``: AP, AP50, AP75, APs, APm, APl and ``AP-<class>``, x100, nan where
+    COCO reports -1."""
+    res = {m: float(stats[i] * 100 if stats[i] >= 0 else "nan") for i, m in enumerate(METRICS)}
+    assert len(class_names) == precision.shape[2]
+    for k, name in enumerate(class_names):
+        p = precision[:, :, k, 0, -1]
+        p = p[p > -1]
+        ap = np.mean(p) if p.size else float("nan")
+        res[f"AP-{name}"] = float(ap * 100)
+    return res

@@ -239,3 +239,104 @@ extern "C" int64_t demia_host_rle_text(const uint32_t* payload, const int32_t* b
     text_off[M] = pos;
     return fits ? pos : -pos;
 }
+
+// COCOeval.evaluateImg (pycocotools, useCats = 1) for G groups -- one (task, category, image) each, with at least one
+// detection or ground truth -- under A area ranges and T IoU thresholds in one call, with maxDet = max_det (the largest of
+// maxDets: accumulate slices the smaller ones off this matching).  Group g owns detection entries dt_off[g] .. dt_off[g + 1]
+// and ground-truth entries gt_off[g] .. gt_off[g + 1], both in the order COCOeval lists them; IoU(d, j) = iou[dt_row[d] +
+// gt_col[j]].  Detections are ranked by descending score (stable) and cut to max_det; ground truths are ordered with the
+// non-ignored first (stable); a ground truth is ignored when crowd or when its area is outside [lo, hi].  Outputs by entry:
+// dt_rank [ndt] (-1 past max_det), dt_matched / dt_ignore [A][T][ndt], gt_ignore [A][ngt].
+extern "C" int demia_host_coco_match(int64_t G, const int64_t* dt_off, const int64_t* gt_off, const double* dt_score,
+                                     const double* dt_area, const int64_t* dt_row, const double* gt_area, const uint8_t* gt_crowd,
+                                     const int64_t* gt_col, const double* iou, const double* area_rng, int A, const double* thr,
+                                     int T, int max_det, int32_t* dt_rank, uint8_t* dt_matched, uint8_t* dt_ignore,
+                                     uint8_t* gt_ignore) {
+    DEMIA_REQUIRE(G >= 0 && dt_off && gt_off && area_rng && thr && A > 0 && T > 0 && max_det > 0, "args");
+    const int64_t ndt = dt_off[G], ngt = gt_off[G];
+    DEMIA_REQUIRE(ndt == 0 || (dt_score && dt_area && dt_row && dt_rank && dt_matched && dt_ignore), "detection arrays");
+    DEMIA_REQUIRE(ngt == 0 || (gt_area && gt_crowd && gt_col && gt_ignore), "ground-truth arrays");
+    DEMIA_REQUIRE((ndt == 0 || ngt == 0) || iou, "iou");
+    std::vector<int64_t> dord, gord;
+    std::vector<uint8_t> gtm, gig;
+    for (int64_t g = 0; g < G; ++g) {
+        const int64_t d0 = dt_off[g], nd = dt_off[g + 1] - d0, g0 = gt_off[g], ng = gt_off[g + 1] - g0;
+        dord.resize(nd);
+        std::iota(dord.begin(), dord.end(), d0);
+        std::stable_sort(dord.begin(), dord.end(), [&](int64_t a, int64_t b) { return dt_score[a] > dt_score[b]; });
+        const int64_t D = std::min<int64_t>(nd, max_det);
+        for (int64_t r = 0; r < nd; ++r) dt_rank[dord[r]] = r < D ? (int32_t)r : -1;
+        for (int a = 0; a < A; ++a) {
+            const double lo = area_rng[2 * a], hi = area_rng[2 * a + 1];
+            gig.resize(ng);
+            for (int64_t j = 0; j < ng; ++j) {
+                gig[j] = (gt_crowd[g0 + j] || gt_area[g0 + j] < lo || gt_area[g0 + j] > hi) ? 1 : 0;
+                gt_ignore[(int64_t)a * ngt + g0 + j] = gig[j];
+            }
+            gord.resize(ng);
+            std::iota(gord.begin(), gord.end(), (int64_t)0);
+            std::stable_sort(gord.begin(), gord.end(), [&](int64_t x, int64_t y) { return gig[x] < gig[y]; });
+            for (int t = 0; t < T; ++t) {
+                uint8_t* mt = dt_matched + ((int64_t)a * T + t) * ndt;
+                uint8_t* ig = dt_ignore + ((int64_t)a * T + t) * ndt;
+                gtm.assign(ng, 0);
+                for (int64_t r = 0; r < nd; ++r) {
+                    const int64_t d = dord[r];
+                    mt[d] = 0;
+                    ig[d] = 0;
+                    if (r >= D) continue;
+                    double best = std::min(thr[t], 1 - 1e-10);
+                    int64_t m = -1;
+                    for (int64_t gi = 0; gi < ng; ++gi) {
+                        const int64_t j = gord[gi];
+                        if (gtm[gi] && !gt_crowd[g0 + j]) continue;           // matched already, not a crowd
+                        if (m > -1 && gig[gord[m]] == 0 && gig[j] == 1) break;  // matched a regular gt, now on the ignored ones
+                        const double v = iou[dt_row[d] + gt_col[g0 + j]];
+                        if (v < best) continue;
+                        best = v;
+                        m = gi;
+                    }
+                    if (m > -1) {
+                        mt[d] = 1;
+                        ig[d] = gig[gord[m]];
+                        gtm[m] = 1;
+                    } else {
+                        ig[d] = (dt_area[d] < lo || dt_area[d] > hi) ? 1 : 0;    // unmatched and outside the area range
+                    }
+                }
+            }
+        }
+    }
+    return DEMIA_OK;
+}
+
+// pycocotools' rleToString for M run-length lists: counts of mask m are counts[offsets[m] .. offsets[m + 1]); every count
+// (minus the count two places back, from the fourth on) is written as 5-bit groups, low first, 0x20 = more, + 48.
+// text_off [M + 1]: mask m's string is out[text_off[m] .. text_off[m + 1]).  Returns the bytes written, or -(bytes needed)
+// when cap is too small.
+extern "C" int64_t demia_host_rle_string(const uint32_t* counts, const int64_t* offsets, int64_t M, char* out, int64_t cap,
+                                         int64_t* text_off) {
+    if (!counts || !offsets || !out || !text_off || M < 0) return 0;
+    int64_t pos = 0;
+    for (int64_t m = 0; m < M; ++m) {
+        text_off[m] = pos;
+        const uint32_t* c = counts + offsets[m];
+        const int64_t n = offsets[m + 1] - offsets[m];
+        for (int64_t i = 0; i < n; ++i) {
+            int64_t x = (int64_t)c[i];
+            if (i > 2) x -= (int64_t)c[i - 2];
+            bool more = true;
+            while (more) {
+                char ch = (char)(x & 0x1f);
+                x >>= 5;
+                more = (ch & 0x10) ? x != -1 : x != 0;
+                if (more) ch |= 0x20;
+                ch += 48;
+                if (pos < cap) out[pos] = ch;
+                ++pos;
+            }
+        }
+    }
+    text_off[M] = pos;
+    return pos <= cap ? pos : -pos;
+}

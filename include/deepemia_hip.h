@@ -470,6 +470,36 @@ int demia_contour_measure(const int32_t* select /* [M] or NULL */, const int32_t
                           int C, int max_points, int32_t* work_i, float* work_f, double* work_d, double um_pix,
                           double* out, int out_c, void* stream);
 
+/* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
+ * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
+ *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at
+ *   column-major positions <= x * H + y).  xy [V][2] f64 (x, y); polygon p = vertices vert_off[p] .. vert_off[p + 1] (ring
+ *   closed implicitly); edges: edge_poly [E] / edge_idx [E] = polygon and vertex index of each edge; bnd_off [P + 1] i64:
+ *   room for polygon p's boundary points in bnd ([*, 2] i32, at most one point per walk point of its edges); bnd_cnt [P] and
+ *   err [1] zeroed by the caller (err bit 1: a list overflowed); mask m = polygons mask_poly[m] .. mask_poly[m + 1].  area /
+ *   bbox (optional, together): demia_mask_area_bbox of the result.
+ * mask_cross_matrix: out [D, ld] i32: row i, column c = |det_i & gt_(gt_first[i] + c)| for c < min(gt_count[i], ld); 0 for
+ *   pairs with disjoint boxes (no mask read) or, with labels, different labels.  det and gt share H and W.
+ * mask_rle_colmajor: column-major run lengths, the background run first (pycocotools' encode).  offsets == NULL: count
+ *   pass, n_counts [M] = number of runs; else write pass into counts[offsets[m] .. offsets[m + 1]) (offsets [M + 1] i64 on
+ *   the device, from the count pass).  H * W < 2^32.
+ * host_coco_match / host_rle_string: host code (nothing touches the GPU), see hostloops.hip. */
+int demia_poly_rasterize(const double* xy, const int32_t* vert_off, const int32_t* edge_poly, const int32_t* edge_idx,
+                         const int64_t* bnd_off, int32_t* bnd, int32_t* bnd_cnt, int32_t* err, int64_t E,
+                         const int32_t* mask_poly, int64_t M, int H, int W, uint32_t* out, int32_t* area, int32_t* bbox,
+                         void* stream);
+int demia_mask_cross_matrix(const uint32_t* det, const int32_t* det_bbox, const int32_t* det_label, const uint32_t* gt,
+                            const int32_t* gt_bbox, const int32_t* gt_label, const int32_t* gt_first, const int32_t* gt_count,
+                            int32_t* out, int64_t D, int ld, int H, int W, void* stream);
+int demia_mask_rle_colmajor(const uint32_t* masks, const int32_t* bbox, int32_t* n_counts, const int64_t* offsets,
+                            uint32_t* counts, int64_t M, int H, int W, void* stream);
+int demia_host_coco_match(int64_t G, const int64_t* dt_off, const int64_t* gt_off, const double* dt_score,
+                          const double* dt_area, const int64_t* dt_row, const double* gt_area, const uint8_t* gt_crowd,
+                          const int64_t* gt_col, const double* iou, const double* area_rng, int A, const double* thr, int T,
+                          int max_det, int32_t* dt_rank, uint8_t* dt_matched, uint8_t* dt_ignore, uint8_t* gt_ignore);
+int64_t demia_host_rle_string(const uint32_t* counts, const int64_t* offsets, int64_t M, char* out, int64_t cap,
+                              int64_t* text_off);
+
 #ifdef __cplusplus
 }
 #endif

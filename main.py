@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""``main.py --task inference`` drop-in for deepEMIA (reference ``main.py:241-342,456-528``).
+"""``main.py --task inference`` / ``--task evaluate`` drop-in for deepEMIA (reference ``main.py:241-342,442-528``).
 
-Same flags and defaults as the reference CLI.  Only the ``inference`` task is implemented (the hot
-path this build accelerates); ``prepare`` / ``train`` / ``evaluate`` / ``setup`` are reported as out
-of scope.  Google Cloud Storage is optional: the reference shells out to ``gsutil`` unconditionally
+Same flags and defaults as the reference CLI.  The ``inference`` task (the hot path this build accelerates) and the
+``evaluate`` task (COCO box / mask AP on the test split, ``deepemia_amd/functions/evaluate_model.py``) are implemented;
+``prepare`` / ``train`` / ``setup`` are reported as out of scope.  Google Cloud Storage is optional: the reference shells out to ``gsutil`` unconditionally
 (``main.py:383-398,473``) and ``--download`` / ``--upload`` cannot be switched off there; here the
 GCS steps run only when ``gsutil`` exists and ``DEEPEMIA_OFFLINE`` is not set, so the CLI also runs
 on a box without network.  Inference inputs are deleted after the run only if they were downloaded.
@@ -117,6 +117,50 @@ def launch_workers(workers: int, argv) -> int:
         raise
 
 
+def run_evaluate(args) -> int:
+    """``--task evaluate`` (reference ``main.py:442-454``): one process on one GPU; the results go to ``split_dir``.  Only
+    ``dataset_info.json`` is fetched from GCS (same gate as inference), nothing is uploaded."""
+    from deepemia_amd.utils.config import get_config
+    from deepemia_amd.utils.gpu_check import check_gpu_availability, log_device_info
+    from deepemia_amd.utils.logger_utils import system_logger
+
+    if not args.dataset_name:
+        system_logger.error("--dataset_name is required for --task evaluate")
+        return 2
+    if args.rcnn == "combo":
+        system_logger.error("--rcnn combo is not supported by --task evaluate: evaluate one model at a time (--rcnn 50 or 101)")
+        return 2
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        system_logger.error("--task evaluate runs in ONE process; start it without torchrun (WORLD_SIZE > 1)")
+        return 2
+    config = get_config()
+    if not args.no_gpu_check:
+        log_device_info()
+    check_gpu_availability(require_gpu=True, interactive=False)
+    split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
+    category_json = Path(config["paths"]["category_json"]).expanduser().resolve()
+    bucket = config.get("bucket")
+    if gcs_available() and bool(bucket) and args.download:
+        try:
+            subprocess.run(["gsutil", "cp", f"gs://{bucket}/dataset_info.json", str(category_json)], check=True)
+        except (subprocess.CalledProcessError, OSError) as e:
+            system_logger.error(f"GCS download failed: {e}")
+            return 1
+    else:
+        system_logger.info("GCS disabled (no gsutil / DEEPEMIA_OFFLINE): using the local dataset_info.json")
+    from deepemia_amd.functions.evaluate_model import evaluate_model
+
+    t0 = time.perf_counter()
+    system_logger.info(f"Evaluating model on dataset {args.dataset_name} using '{args.dataset_format}' format...")
+    try:
+        evaluate_model(args.dataset_name, str(split_dir), args.visualize, dataset_format=args.dataset_format, rcnn=int(args.rcnn))
+    except Exception:
+        system_logger.error("evaluation failed", exc_info=True)
+        return 1
+    system_logger.info(f"Evaluate task finished in {time.perf_counter() - t0:.2f}s; results in {split_dir}")
+    return 0
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     from deepemia_amd.utils.config import get_config
@@ -125,8 +169,10 @@ def main(argv=None) -> int:
 
     set_console_log_level({"debug": logging.DEBUG, "info": logging.INFO, "warning": logging.WARNING,
                            "error": logging.ERROR}[args.verbosity])
+    if args.task == "evaluate":
+        return run_evaluate(args)
     if args.task != "inference":
-        system_logger.error(f"task '{args.task}' is outside the scope of this build (inference hot path only)")
+        system_logger.error(f"task '{args.task}' is outside the scope of this build (inference and evaluate only)")
         return 2
     if not args.dataset_name:
         system_logger.error("--dataset_name is required for --task inference")
