@@ -30,10 +30,12 @@ def _ptr(a: np.ndarray) -> int:
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------------
-def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, W: int
+def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, W: int, err_out: Optional[list] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``masks[m]`` = the polygons of mask m, each a flat ``[x0, y0, x1, y1, ...]`` list -> packed ``[M, H, ceil(W/32)]`` int32
-    on the device, pixel count ``[M]`` and tight box ``[M, 4]`` (``demia_poly_rasterize``)."""
+    on the device, pixel count ``[M]`` and tight box ``[M, 4]`` (``demia_poly_rasterize``).  The kernel's error word is waited
+    for and checked here, unless ``err_out`` is a list: the word (a 1-element device tensor) is then appended to it for the
+    caller to fetch with its own tables and hand to :func:`check_rasterize_error`."""
     M = len(masks)
     wpr = (W + 31) // 32
     out = torch.empty((M, H, wpr), dtype=torch.int32, device=ops.device)
@@ -72,9 +74,16 @@ def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, 
                                             _lib.ptr(t_tab[o_i:]) if E else _lib.ptr(t_tab), _lib.ptr(t_off), _lib.ptr(bnd),
                                             _lib.ptr(cnt), _lib.ptr(cnt[P:]), E, _lib.ptr(t_tab[o_m:]), M, H, W, _lib.ptr(out),
                                             _lib.ptr(area), _lib.ptr(bbox), ops._stream()), "demia_poly_rasterize")
-    if int(cnt[P].item()):
-        raise _lib.HipKernelError("demia_poly_rasterize: a boundary list overflowed its room")
+    if err_out is not None:
+        err_out.append(cnt[P:])
+    else:
+        check_rasterize_error(int(cnt[P].item()))
     return out, area, bbox
+
+
+def check_rasterize_error(word: int) -> None:
+    if word:
+        raise _lib.HipKernelError("demia_poly_rasterize: a boundary list overflowed its room")
 
 
 def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Optional[np.ndarray], gt: torch.Tensor,
@@ -112,6 +121,45 @@ def rle_counts(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int) -> Tuple[n
     _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(t_off), _lib.ptr(counts), M, H, W,
                                                ops._stream()), "demia_mask_rle_colmajor")
     return counts.cpu().numpy().view(np.uint32), off
+
+
+def rle_room(bbox: np.ndarray) -> int:
+    """Room (in counts) that :func:`rle_counts_launch` reserves for masks with the HOST boxes ``bbox`` [M, 4] (y0, x0, y1, x1,
+    y0 = -1 when empty): four transitions per box column and a few more per mask -- twice what a mask whose columns are single
+    runs needs.  A set of masks that needs more is encoded again by :func:`rle_counts` (one more wait)."""
+    bbox = np.asarray(bbox, dtype=np.int64).reshape(-1, 4)
+    cols = np.where(bbox[:, 0] >= 0, bbox[:, 3] - bbox[:, 1] + 1, 0)
+    return int((4 * cols + 16).sum())
+
+
+def rle_counts_launch(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int, room: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Both passes of ``demia_mask_rle_colmajor`` enqueued WITHOUT a wait in between: the offsets are summed on the device and
+    cut at ``room``, so a mask whose runs do not fit leaves its slot alone (the write pass checks every slot's size).  Returns
+    the device tensors ``(n_counts [M] int32, counts [room] int32)`` for the caller to fetch together with its other tables;
+    :func:`rle_counts_finish` turns the host copies into ``(counts, offsets)`` or reports that the room was too small."""
+    M, H, _ = packed.shape
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    counts = torch.zeros((max(1, int(room)),), dtype=torch.int32, device=ops.device)
+    if M == 0:
+        return n, counts
+    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(n), 0, 0, M, H, W, ops._stream()),
+               "demia_mask_rle_colmajor")
+    off = torch.zeros((M + 1,), dtype=torch.int64, device=ops.device)
+    off[1:] = torch.cumsum(n, 0, dtype=torch.int64)
+    off.clamp_(max=int(counts.shape[0]))
+    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(off), _lib.ptr(counts), M, H, W,
+                                               ops._stream()), "demia_mask_rle_colmajor")
+    return n, counts
+
+
+def rle_counts_finish(n_host: np.ndarray, counts_host: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+    """Host side of :func:`rle_counts_launch`: ``(counts uint32, offsets [M + 1] int64)`` as :func:`rle_counts` returns them,
+    or None when the runs did not fit the room."""
+    off = np.zeros(len(n_host) + 1, dtype=np.int64)
+    np.cumsum(n_host, dtype=np.int64, out=off[1:])
+    if off[-1] > len(counts_host):
+        return None
+    return np.ascontiguousarray(counts_host[:off[-1]]).view(np.uint32), off
 
 
 # ---- host codecs -------------------------------------------------------------------------------------------------------------
@@ -161,6 +209,37 @@ def rle_decode(counts: Sequence[int], h: int, w: int) -> np.ndarray:
             flat[pos:pos + int(c)] = True
         pos += int(c)
     return flat.reshape(w, h).T
+
+
+def rle_to_bbox(counts: np.ndarray, offsets: np.ndarray, h: int) -> np.ndarray:
+    """pycocotools' ``toBbox`` (``rleToBbox``, 2.0.7 on) of every run list: float64 ``[M, 4]`` XYWH.  The box is the tight box
+    of the mask's pixels, EXCEPT that a foreground run that goes on into the next column (the last row of one column and the
+    first row of the next are both set) makes it span all rows: y = 0, height = h.  An empty mask gives four zeros."""
+    M = len(offsets) - 1
+    out = np.zeros((M, 4), dtype=np.float64)
+    c = np.asarray(counts, dtype=np.int64)
+    if M == 0 or len(c) == 0:
+        return out
+    offsets = np.asarray(offsets, dtype=np.int64)
+    mid = np.repeat(np.arange(M), np.diff(offsets))
+    end = np.cumsum(c)
+    end -= np.concatenate([[0], end])[offsets[:-1]][mid]            # the run's end within its own mask
+    start = end - c
+    fg = (((np.arange(len(c)) - offsets[:-1][mid]) & 1) == 1) & (c > 0)
+    mid, start, last = mid[fg], start[fg], end[fg] - 1
+    ys_, xs_, ye_, xe_ = start % h, start // h, last % h, last // h
+    cross = xs_ < xe_
+    ys_, ye_ = np.where(cross, 0, ys_), np.where(cross, h - 1, ye_)
+    big = np.iinfo(np.int64).max
+    xs, ys = np.full(M, big), np.full(M, big)
+    xe, ye = np.full(M, -1), np.full(M, -1)
+    np.minimum.at(xs, mid, xs_)
+    np.minimum.at(ys, mid, ys_)
+    np.maximum.at(xe, mid, xe_)
+    np.maximum.at(ye, mid, ye_)
+    ok = xe >= 0
+    out[ok] = np.stack([xs[ok], ys[ok], xe[ok] - xs[ok] + 1, ye[ok] - ys[ok] + 1], 1)
+    return out
 
 
 # ---- IoU tables ---------------------------------------------------------------------------------------------------------------
@@ -220,10 +299,20 @@ class EvalTables:
         return np.concatenate(v) if v else np.zeros((0,))
 
 
-def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Sequence[int]) -> Dict[str, dict]:
+def check_max_dets(max_dets: Optional[Sequence[int]]) -> List[int]:
+    """``params.maxDets``: three ascending positive counts (default ``MAX_DETS``); the last is the one AP / AR use."""
+    md = list(MAX_DETS) if max_dets is None else [int(v) for v in max_dets]
+    if len(md) != 3 or md[0] < 1 or any(b <= a for a, b in zip(md, md[1:])):
+        raise ValueError(f"max_dets must be three ascending positive counts, got {max_dets!r}")
+    return md
+
+
+def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Sequence[int],
+             max_dets: Optional[Sequence[int]] = None) -> Dict[str, dict]:
     """``COCOeval.evaluate()`` + ``accumulate()`` for every task of ``tables`` with one native matching call:
     ``{task: {"precision": [T, R, K, A, M], "recall": [T, K, A, M], "stats": [12]}}``; ``img_ids`` / ``cat_ids`` as
-    ``params.imgIds`` / ``params.catIds`` (sorted)."""
+    ``params.imgIds`` / ``params.catIds`` (sorted), ``max_dets`` as ``params.maxDets`` (default ``[1, 10, 100]``)."""
+    max_dets = check_max_dets(max_dets)
     img_ids = np.asarray(sorted(img_ids), dtype=np.int64)
     cat_ids = np.asarray(sorted(cat_ids), dtype=np.int64)
     tasks = list(tables)
@@ -283,10 +372,10 @@ def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Seq
     thr = np.ascontiguousarray(IOU_THRS)
     _lib.check(_lib.load().demia_host_coco_match(Gn, dt_off.ctypes.data, gt_off.ctypes.data, _ptr(score), _ptr(darea), _ptr(drow),
                                                  _ptr(garea), _ptr(gcrowd), _ptr(gcol), iou.ctypes.data, rng.ctypes.data, A,
-                                                 thr.ctypes.data, T, MAX_DETS[-1], _ptr(rank), _ptr(matched), _ptr(dig), _ptr(gig)),
+                                                 thr.ctypes.data, T, max_dets[-1], _ptr(rank), _ptr(matched), _ptr(dig), _ptr(gig)),
                "demia_host_coco_match")
     out = {}
-    R, M = len(REC_THRS), len(MAX_DETS)
+    R, M = len(REC_THRS), len(max_dets)
     dgrp = np.searchsorted(groups, dkey) if ndt else np.zeros(0, np.int64)
     ggrp = np.searchsorted(groups, gkey) if ngt else np.zeros(0, np.int64)
     for ti, task in enumerate(tasks):
@@ -305,7 +394,7 @@ def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Seq
                 npig = int(np.count_nonzero(gig[a, gsl] == 0))
                 if npig == 0:
                     continue
-                for mi, maxDet in enumerate(MAX_DETS):
+                for mi, maxDet in enumerate(max_dets):
                     keep = order[(dr[order] >= 0) & (dr[order] < maxDet)]
                     sc = score[dsl][keep]
                     inds = np.argsort(-sc, kind="mergesort")
@@ -326,13 +415,13 @@ def evaluate(tables: Dict[str, EvalTables], img_ids: Sequence[int], cat_ids: Seq
                         ok = idx < nd
                         q[ok] = pr[idx[ok]]            # recall points past the last detection stay 0
                         precision[t, :, k, a, mi] = q
-        out[task] = {"precision": precision, "recall": recall, "stats": summarize(precision, recall)}
+        out[task] = {"precision": precision, "recall": recall, "stats": summarize(precision, recall, max_dets)}
     return out
 
 
-def _summ(precision, recall, ap=1, iou_thr=None, area="all", max_dets=100) -> float:
+def _summ(precision, recall, ap=1, iou_thr=None, area="all", mind=2) -> float:
     aind = [i for i, lbl in enumerate(AREA_LBL) if lbl == area]
-    mind = [i for i, m in enumerate(MAX_DETS) if m == max_dets]
+    mind = [mind]
     if ap == 1:
         s = precision
         if iou_thr is not None:
@@ -346,28 +435,28 @@ def _summ(precision, recall, ap=1, iou_thr=None, area="all", max_dets=100) -> fl
     return -1.0 if len(s[s > -1]) == 0 else float(np.mean(s[s > -1]))
 
 
-def summarize(precision: np.ndarray, recall: np.ndarray) -> np.ndarray:
-    """``COCOeval.summarize()``'s twelve numbers (``_summarizeDets``)."""
-    m = MAX_DETS
-    return np.array([_summ(precision, recall, 1), _summ(precision, recall, 1, .5, max_dets=m[2]),
-                     _summ(precision, recall, 1, .75, max_dets=m[2]), _summ(precision, recall, 1, area="small", max_dets=m[2]),
-                     _summ(precision, recall, 1, area="medium", max_dets=m[2]), _summ(precision, recall, 1, area="large", max_dets=m[2]),
-                     _summ(precision, recall, 0, max_dets=m[0]), _summ(precision, recall, 0, max_dets=m[1]),
-                     _summ(precision, recall, 0, max_dets=m[2]), _summ(precision, recall, 0, area="small", max_dets=m[2]),
-                     _summ(precision, recall, 0, area="medium", max_dets=m[2]), _summ(precision, recall, 0, area="large", max_dets=m[2])])
+# (AP / AR, IoU threshold, area label, index into max_dets) of COCOeval.summarize()'s twelve numbers (``_summarizeDets``)
+_SPEC = [(1, None, "all", 2), (1, .5, "all", 2), (1, .75, "all", 2), (1, None, "small", 2), (1, None, "medium", 2),
+         (1, None, "large", 2), (0, None, "all", 0), (0, None, "all", 1), (0, None, "all", 2), (0, None, "small", 2),
+         (0, None, "medium", 2), (0, None, "large", 2)]
 
 
-def summary_lines(stats: np.ndarray) -> List[str]:
+def summarize(precision: np.ndarray, recall: np.ndarray, max_dets: Optional[Sequence[int]] = None) -> np.ndarray:
+    """``COCOeval.summarize()``'s twelve numbers (``_summarizeDets``); every AP and the area ARs at the last of ``max_dets``
+    (pycocotools reads its first AP at a literal 100, which is the last entry of its default)."""
+    check_max_dets(max_dets)
+    return np.array([_summ(precision, recall, ap, thr, area, mi) for ap, thr, area, mi in _SPEC])
+
+
+def summary_lines(stats: np.ndarray, max_dets: Optional[Sequence[int]] = None) -> List[str]:
     """The twelve lines ``COCOeval.summarize()`` prints."""
-    spec = [(1, None, "all", 100), (1, .5, "all", 100), (1, .75, "all", 100), (1, None, "small", 100), (1, None, "medium", 100),
-            (1, None, "large", 100), (0, None, "all", 1), (0, None, "all", 10), (0, None, "all", 100), (0, None, "small", 100),
-            (0, None, "medium", 100), (0, None, "large", 100)]
+    md = check_max_dets(max_dets)
     lines = []
-    for (ap, thr, area, md), v in zip(spec, stats):
+    for (ap, thr, area, mi), v in zip(_SPEC, stats):
         title = "Average Precision" if ap == 1 else "Average Recall"
         typ = "(AP)" if ap == 1 else "(AR)"
         iou = "{:0.2f}:{:0.2f}".format(IOU_THRS[0], IOU_THRS[-1]) if thr is None else "{:0.2f}".format(thr)
-        lines.append(" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(title, typ, iou, area, md, v))
+        lines.append(" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(title, typ, iou, area, md[mi], v))
     return lines
 
 

@@ -2,7 +2,7 @@
 //
 //   poly_rasterize   ground-truth polygons -> packed masks with pycocotools' rleFrPoly rule (frPyObjects + merge for a mask
 //                    made of several polygons), built in two kernels: the boundary points of every edge, then the packed
-//                    words, each written by exactly one thread
+//                    words, each written by exactly one thread; only the words of a polygon's columns walk its points
 //   cross_matrix     |det_i & gt_j| for every detection x ground-truth pair of one image segment with equal labels
 //   rle_colmajor     column-major run lengths of each mask (pycocotools' encode order: the background run first)
 //
@@ -99,34 +99,76 @@ __global__ __launch_bounds__(256) void poly_boundary_kernel(const double* __rest
     }
 }
 
-// One thread per output word (mask m, row y, word wx): pixel (x, y) of a polygon is set iff an odd number of its boundary
-// points lie at column-major positions <= x * h + y -- the toggles of rleFrPoly's run list, counted over ALL columns, so a
-// point clamped to y = h toggles row 0 of the next column.  A point (px, py) covers the pixels of row y from column
-// px + (y < py) on.  The mask is the OR of its polygons (merge); bits at x >= W stay zero.
+// Output word (mask m, row y, word wx): pixel (x, y) of a polygon is set iff an odd number of its boundary points lie at
+// column-major positions <= x * h + y -- the toggles of rleFrPoly's run list, counted over ALL columns, so a point clamped
+// to y = h toggles row 0 of the next column.  A point (px, py) covers the pixels of row y from column px + (y < py) on.  The
+// mask is the OR of its polygons (merge); bits at x >= W stay zero.
+// Work is restricted to the polygon's columns: left of its first point's column no point covers a pixel (0), from the column
+// after its last point's on every point does (all ones when the count is odd, as rleFrPoly's closing run) -- only the words
+// of the columns lo .. hi walk the point list, so a frame of thousands of small polygons costs their boxes, not M planes.
+// A block of 256 threads writes FILL_WORDS consecutive words of one mask, each by exactly one thread.
+constexpr int FILL_PER_THREAD = 8;
+constexpr int FILL_WORDS = 256 * FILL_PER_THREAD;
+
 __global__ __launch_bounds__(256) void poly_fill_kernel(const int2* __restrict__ bnd, const long* __restrict__ bnd_off,
                                                         const int* __restrict__ bnd_cnt, const int* __restrict__ mask_poly,
                                                         uint32_t* __restrict__ out, int H, int W) {
+    __shared__ int red_lo[4], red_hi[4];
     const int wpr = (W + 31) >> 5;
     const int m = blockIdx.y;
-    const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (t >= (long)H * wpr) return;
-    const int y = (int)(t / wpr), wx = (int)(t % wpr), x0 = wx << 5;
-    uint32_t word = 0u;
-    for (int p = mask_poly[m]; p < mask_poly[m + 1]; ++p) {
+    const long total = (long)H * wpr;
+    const long base = blockIdx.x * (long)FILL_WORDS + threadIdx.x;
+    uint32_t word[FILL_PER_THREAD];
+#pragma unroll
+    for (int k = 0; k < FILL_PER_THREAD; ++k) word[k] = 0u;
+    for (int p = mask_poly[m]; p < mask_poly[m + 1]; ++p) {          // (block-uniform)
         const long b0 = bnd_off[p];
-        const int n = min((long)bnd_cnt[p], bnd_off[p + 1] - b0);
-        uint32_t par = 0u;
-        for (int i = 0; i < n; ++i) {
-            const int2 q = bnd[b0 + i];
-            const int first = q.x + (y < q.y ? 1 : 0) - x0;
-            if (first <= 0) par = ~par;
-            else if (first < 32) par ^= ~0u << first;
+        const int n = (int)min((long)bnd_cnt[p], bnd_off[p + 1] - b0);
+        int lo = INT_MAX, hi = -1;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int px = bnd[b0 + i].x;
+            lo = min(lo, px);
+            hi = max(hi, px);
         }
-        word |= par;
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = min(lo, __shfl_down(lo, o, 64));
+            hi = max(hi, __shfl_down(hi, o, 64));
+        }
+        __syncthreads();                                             // (the previous polygon's reads of red_* are done)
+        if ((threadIdx.x & 63) == 0) {
+            red_lo[threadIdx.x >> 6] = lo;
+            red_hi[threadIdx.x >> 6] = hi;
+        }
+        __syncthreads();
+        lo = min(min(red_lo[0], red_lo[1]), min(red_lo[2], red_lo[3]));
+        hi = max(max(red_hi[0], red_hi[1]), max(red_hi[2], red_hi[3]));
+        const uint32_t tail = (n & 1) ? ~0u : 0u;
+#pragma unroll
+        for (int k = 0; k < FILL_PER_THREAD; ++k) {
+            const long t = base + (long)k * 256;
+            if (t >= total) continue;
+            const int y = (int)(t / wpr), x0 = (int)(t % wpr) << 5;
+            uint32_t par = 0u;
+            if (x0 > hi) {
+                par = tail;                                          // every point's first column is <= hi + 1 <= x0
+            } else if (x0 + 31 >= lo) {
+                for (int i = 0; i < n; ++i) {
+                    const int2 q = bnd[b0 + i];
+                    const int first = q.x + (y < q.y ? 1 : 0) - x0;
+                    if (first <= 0) par = ~par;
+                    else if (first < 32) par ^= ~0u << first;
+                }
+            }
+            word[k] |= par;
+        }
     }
-    const int valid = W - x0;
-    if (valid < 32) word &= (1u << valid) - 1u;
-    out[((long)m * H + y) * wpr + wx] = word;
+#pragma unroll
+    for (int k = 0; k < FILL_PER_THREAD; ++k) {
+        const long t = base + (long)k * 256;
+        if (t >= total) continue;
+        const int valid = W - ((int)(t % wpr) << 5);
+        out[(long)m * total + t] = valid < 32 ? (word[k] & ((1u << valid) - 1u)) : word[k];
+    }
 }
 
 // ---- |det_i & gt_j| for the pairs of one image segment: block per detection, one wave per candidate gt in turn ----------
@@ -281,7 +323,7 @@ extern "C" int demia_poly_rasterize(const double* xy, const int32_t* vert_off, c
         DEMIA_CHECK_LAUNCH("poly_boundary_kernel");
     }
     const long words = (long)H * ((W + 31) / 32);
-    hipLaunchKernelGGL(poly_fill_kernel, dim3(cdiv(words, 256), (unsigned)M), dim3(256), 0, s, (const int2*)bnd,
+    hipLaunchKernelGGL(poly_fill_kernel, dim3(cdiv(words, FILL_WORDS), (unsigned)M), dim3(256), 0, s, (const int2*)bnd,
                        (const long*)bnd_off, bnd_cnt, mask_poly, out, H, W);
     DEMIA_CHECK_LAUNCH("poly_fill_kernel");
     if (area || bbox) {

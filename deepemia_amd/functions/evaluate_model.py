@@ -6,9 +6,18 @@ the ``metadata`` slot of ``choose_and_use_model``).  Every test image goes throu
 resize, score threshold 0.45, at most 100 detections); the ground truth is rasterised, intersected with the detections and
 run-length encoded on the GPU (``deepemia_amd.cocoeval``), and COCOeval's matching runs as one native host call.
 
+That is the **predictor** mode (the default).  The **pipeline** mode (``evaluation: {mode: pipeline}`` in the configuration,
+global or per dataset, or ``DEEPEMIA_EVAL_MODE=pipeline``) scores what ``--task inference`` ships instead: every test image
+goes through ``functions.inference.final_instances`` -- the class loop with its per-class thresholds, the full-image pass
+plus the upscaled tiles, the merges, the 0.7 cross-class pass and the spatial constraints, with the R50 + R101 ensemble
+where ``--rcnn combo`` is given and the dataset's settings enable it -- and the final masks are scored.  The pipeline has
+no regressed box: a detection's box is ``toBbox`` of its mask's run lengths (``cocoeval.rle_to_bbox``).
+``evaluation.max_dets`` (default ``[1, 10, 100]``) is COCOeval's ``maxDets``; micrographs with several hundred particles
+need its last entry raised.
+
 Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task), ``coco_instances_results.json``
 (``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``.  Not provided: prediction
-images (``--visualize`` only logs a warning) and the ``combo`` model pair.
+images (``--visualize`` only logs a warning) and, in predictor mode, the ``combo`` model pair.
 """
 from __future__ import annotations
 
@@ -18,7 +27,7 @@ import os
 import time
 from collections import OrderedDict
 from pathlib import Path
-from typing import Dict, List
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -33,6 +42,20 @@ from ..utils.logger_utils import system_logger
 
 SCORE_THRESH = 0.45          # evaluate_model.py:78 (--threshold does not apply)
 BATCH = 4                    # same-size test images per forward
+MODES = ("predictor", "pipeline")
+
+
+def evaluation_settings(dataset_name: Optional[str] = None) -> Tuple[str, List[int]]:
+    """``(mode, max_dets)`` from the ``evaluation`` key of the configuration (global, or in the dataset's file; neither entry is
+    required); ``DEEPEMIA_EVAL_MODE`` overrides the mode.  ValueError for an unknown mode or a malformed ``max_dets``."""
+    try:
+        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
+    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
+        cfg = {}
+    mode = str(os.environ.get("DEEPEMIA_EVAL_MODE") or cfg.get("mode", "predictor")).strip().lower()
+    if mode not in MODES:
+        raise ValueError(f"evaluation mode must be one of {MODES}, got {mode!r}")
+    return mode, CE.check_max_dets(cfg.get("max_dets"))
 
 
 def read_image_bgr(path: str) -> np.ndarray:
@@ -83,11 +106,18 @@ def _gt_box_xywh(a: dict) -> List[float]:
 
 
 def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, dataset_format: str = "json",
-                   rcnn: int = 101) -> "OrderedDict[str, Dict[str, float]]":
+                   rcnn: Union[int, str] = 101, mode: str = "predictor", threshold: float = 0.65) -> "OrderedDict[str, Dict[str, float]]":
     """Score the trained ``rcnn_r<rcnn>`` model of ``dataset_name`` on its test split; returns Detectron2's
-    ``OrderedDict(bbox={...}, segm={...})`` and writes the three result files to ``output_dir``."""
+    ``OrderedDict(bbox={...}, segm={...})`` and writes the three result files to ``output_dir``.  ``mode="pipeline"`` scores
+    the final instances of the tiled inference pipeline instead of the bare predictor's: ``rcnn`` may then be ``"combo"``
+    (both models, as ``--task inference`` loads them) and ``threshold`` is the predictors' score threshold (``--threshold``)."""
     t_start = time.perf_counter()
+    if mode not in MODES:
+        raise ValueError(f"evaluation mode must be one of {MODES}, got {mode!r}")
+    if mode == "predictor" and str(rcnn) == "combo":
+        raise ValueError("the predictor mode scores one model: rcnn must be 50 or 101")
     config = get_config()
+    max_dets = CE.check_max_dets((get_config(dataset_name=dataset_name).get("evaluation", {}) or {}).get("max_dets"))
     split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
     category_json = Path(config["paths"]["category_json"]).expanduser().resolve()
     if visualize:
@@ -97,6 +127,10 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     register_datasets(dataset_info, dataset_name, dataset_format=dataset_format)
     recs, class_names, to_dataset_id = _test_records(dataset_name, dataset_format, dataset_info, split_dir)
     metadata = MetadataCatalog.get(f"{dataset_name}_train")
+    if mode == "pipeline":
+        tables = {"bbox": CE.EvalTables(), "segm": CE.EvalTables()}
+        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id)
+        return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline")
     predictor, _ = choose_and_use_model(get_trained_model_paths(str(split_dir), rcnn), dataset_name, SCORE_THRESH, metadata, rcnn)
     if predictor is None:
         raise FileNotFoundError(f"no trained rcnn_r{rcnn} model for dataset {dataset_name} under {split_dir}")
@@ -134,6 +168,14 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         t_fwd += t2 - t1
         t_score += t3 - t2
 
+    return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, (t_read, t_fwd, t_score),
+                          "forwards")
+
+
+def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, work: str):
+    """COCOeval over the tables of all images, the three result files and the timing line (``work`` names what ``times[1]``
+    measured: the predictor's forwards, or the whole inference pipeline of an image)."""
+    t_read, t_fwd, t_score = times
     t0 = time.perf_counter()
     predictions = [{"image_id": recs[i]["image_id"], "instances": per_image[i]["instances"]} for i in range(len(recs))]
     coco_results = [dict(r, category_id=to_dataset_id[r["category_id"]]) for p in predictions for r in p["instances"]]
@@ -149,9 +191,9 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         for task in ("bbox", "segm"):
             results[task] = {m: float("nan") for m in CE.METRICS}
     else:
-        ev = CE.evaluate(tables, [r["image_id"] for r in recs], cat_ids)
+        ev = CE.evaluate(tables, [r["image_id"] for r in recs], cat_ids, max_dets)
         for task in ("bbox", "segm"):
-            system_logger.info(f"Evaluation results for {task}:\n" + "\n".join(CE.summary_lines(ev[task]["stats"])))
+            system_logger.info(f"Evaluation results for {task}:\n" + "\n".join(CE.summary_lines(ev[task]["stats"], max_dets)))
             results[task] = CE.derive_results(ev[task]["stats"], ev[task]["precision"], class_names)
     t_score += time.perf_counter() - t0
     system_logger.info(f"Evaluation metrics: {results}")
@@ -162,7 +204,7 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         for key, value in results.items():
             w.writerow({"metric": key, "value": value})
     n = max(1, len(recs))
-    system_logger.info(f"Evaluation wall time {time.perf_counter() - t_start:.2f}s: forwards {t_fwd:.3f}s ({1e3 * t_fwd / n:.1f} ms/image), "
+    system_logger.info(f"Evaluation wall time {time.perf_counter() - t_start:.2f}s: {work} {t_fwd:.3f}s ({1e3 * t_fwd / n:.1f} ms/image), "
                        f"scoring {t_score:.3f}s ({1e3 * t_score / n:.1f} ms/image), image reads {t_read:.3f}s; "
                        f"metrics saved to {csv_path}")
     return results
@@ -195,15 +237,164 @@ def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables]
     xywh_l, scores_l, classes_l = xywh.tolist(), scores.tolist(), classes.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter)
+    return {"instances": instances}
+
+
+def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter) -> None:
+    """One image's rows of both tasks' tables: detections (contiguous classes, float64 scores and XYWH boxes, mask pixel
+    counts) against the record's annotations (``g_px`` their rasterised pixel counts, ``inter`` the intersection counts)."""
+    anns = rec["annotations"]
     crowd = np.asarray([int(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8)
     g_area = np.asarray([float(a["area"]) for a in anns], dtype=np.float64)
     g_box = np.asarray([_gt_box_xywh(a) for a in anns], dtype=np.float64).reshape(-1, 4)
     d_cat = np.asarray([to_dataset_id[c] for c in classes_l], dtype=np.int64)
     g_cat_ds = np.asarray([to_dataset_id[int(c)] for c in g_cat], dtype=np.int64)
-    d_box64 = xywh.astype(np.float64)
     img = rec["image_id"]
-    tables["segm"].add_image(img, d_cat, scores.astype(np.float64), d_area.astype(np.float64), g_cat_ds, g_area, crowd,
+    tables["segm"].add_image(img, d_cat, scores64, d_area.astype(np.float64), g_cat_ds, g_area, crowd,
                              CE.mask_iou(inter, d_area, g_px, crowd))
-    tables["bbox"].add_image(img, d_cat, scores.astype(np.float64), d_box64[:, 2] * d_box64[:, 3], g_cat_ds, g_area, crowd,
+    tables["bbox"].add_image(img, d_cat, scores64, d_box64[:, 2] * d_box64[:, 3], g_cat_ds, g_area, crowd,
                              CE.box_iou(d_box64, g_box, crowd))
+
+
+# ---- pipeline mode -----------------------------------------------------------------------------------------------------------
+class PipelineRunner:
+    """The per-image work of ``--task inference`` for the evaluate task: the models (``rcnn`` 50 / 101 = that one alone,
+    ``"combo"`` = every trained one, R50 first), the settings, the small classes (``calculate_average_mask_sizes`` over the
+    first <= 5 images) and the image's final instances (``final_instances``) are ``run_inference``'s own; the images of a group
+    share their forwards as they do there.  ``t_read`` / ``t_pipe``: seconds spent decoding images / in the pipeline."""
+
+    def __init__(self, dataset_name: str, metadata, split_dir: str, rcnn: Union[int, str], threshold: float):
+        from ..utils.spatial_constraints import load_spatial_constraints
+        from . import inference as INF
+
+        self.INF = INF
+        predictors, models = [], []
+        for r in ((50, 101) if str(rcnn) == "combo" else (int(rcnn),)):
+            paths = get_trained_model_paths(split_dir, r)
+            if dataset_name in paths:
+                p, _ = choose_and_use_model(paths, dataset_name, threshold, metadata, r)
+                if p is not None:
+                    p.model.eval()
+                    predictors.append(p)
+                    models.append(r)
+        if not predictors:
+            raise FileNotFoundError(f"No trained models found for dataset '{dataset_name}' (rcnn {rcnn}) under {split_dir}")
+        system_logger.info(f"Loaded models: {', '.join(f'R{r}' for r in models)}")
+        self.st = INF.PipelineSettings(dataset_name)
+        self.pipe = INF.InferencePipeline(predictors, dataset_name, self.st.inf, self.st.global_config)
+        if self.pipe.world != 1:
+            raise RuntimeError("the evaluate task runs in one process")
+        self.spatial_cfg = load_spatial_constraints(dataset_name)
+        self.num_classes = len(metadata.thing_classes)
+        self.dev = self.pipe.dev
+        self.t_read = self.t_pipe = 0.0
+
+    def _load(self, path: str) -> torch.Tensor:
+        t0 = time.perf_counter()
+        img = self.INF.imread_bgr(path)            # the inference task's reader (its 16-bit rule included)
+        self.t_read += time.perf_counter() - t0
+        if img is None:
+            raise ValueError(f"Could not load image: {path}")
+        return torch.from_numpy(img).to(self.dev)
+
+    def instances(self, paths: Sequence[str]):
+        """Generator over ``paths`` in order: ``(path, (H, W), packed, scores, classes, tabs)`` -- the image's final packed masks on
+        the device (None or empty when nothing is left), its scores and classes, ``tabs = (pixel counts, boxes)`` on the host."""
+        INF, st, pipe = self.INF, self.st, self.pipe
+        t0, r0 = time.perf_counter(), self.t_read
+        on_dev = {p: self._load(p) for p in paths[:5]}
+        sample = list(on_dev.items())
+        if sample:
+            pipe.finish_prefetch(pipe.prefetch_images(sample, [0], st.tile_size, st.overlap_ratio, st.upscale_factor))
+        small_classes = INF.determine_small_classes(pipe.calculate_average_mask_sizes(sample), 50)
+        system_logger.info(f"Small classes: {sorted(small_classes)}")
+        models_needed = st.models_needed(len(pipe.predictors), small_classes, self.num_classes)
+        tiles = len(pipe._tile_offsets(int(sample[0][1].shape[0]), int(sample[0][1].shape[1]), st.tile_size, st.overlap_ratio)) if sample else 1
+        group = max(1, min(pipe.forward_batch // max(1, tiles), 16))
+        phases_ok = INF.image_phases_enabled(pipe)
+        del sample
+        self.t_pipe += time.perf_counter() - t0 - (self.t_read - r0)
+        for g0 in range(0, len(paths), group):
+            t0, r0 = time.perf_counter(), self.t_read
+            items = [(p, on_dev.pop(p) if p in on_dev else self._load(p)) for p in paths[g0:g0 + group]]
+            pipe.finish_prefetch(pipe.prefetch_images(items, models_needed, st.tile_size, st.overlap_ratio, st.upscale_factor))
+            self.t_pipe += time.perf_counter() - t0 - (self.t_read - r0)
+            for path, image_dev in items:
+                t0 = time.perf_counter()
+                try:
+                    packed, scores, classes, tabs = INF.final_instances(pipe, st, path, image_dev, small_classes, self.num_classes,
+                                                                        self.spatial_cfg, phases_ok)
+                finally:
+                    pipe.drop_cached(path)
+                self.t_pipe += time.perf_counter() - t0
+                yield path, (int(image_dev.shape[0]), int(image_dev.shape[1])), packed, scores, classes, tabs
+        pipe.clear_cache()
+
+
+def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id):
+    """Every test image through the inference pipeline and the scorer; ``(per_image, (reads, pipeline, scoring) seconds)``."""
+    system_logger.info(f"Evaluating the inference pipeline on {len(recs)} test images of {dataset_name} (rcnn {rcnn}, threshold {threshold})")
+    runner = PipelineRunner(dataset_name, metadata, split_dir, rcnn, threshold)
+    ops = MaskOps(str(runner.dev))
+    per_image: Dict[int, dict] = {}
+    t_score = 0.0
+    for ri, (_, hw, packed, scores, classes, tabs) in enumerate(runner.instances([rec["file_name"] for rec in recs])):
+        t0 = time.perf_counter()
+        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id)
+        t_score += time.perf_counter() - t0
+    return per_image, (runner.t_read, runner.t_pipe, t_score)
+
+
+def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id) -> dict:
+    """Device work of one image's final instances (ground-truth masks, intersections, run lengths) and its rows of the IoU
+    tables.  Everything the host needs comes over in ONE device-to-host copy; the detections' pixel counts and boxes are
+    already on the host (``tabs``)."""
+    H, W = int(rec["height"]), int(rec["width"])
+    if tuple(int(v) for v in hw) != (H, W):
+        raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
+    anns = rec["annotations"]
+    n = 0 if packed is None else int(packed.shape[0])
+    G = len(anns)
+    if n == 0:
+        packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
+        d_area, d_bbox = np.zeros((0,), np.int64), np.zeros((0, 4), np.int32)
+    else:
+        d_area, d_bbox = np.asarray(tabs[0]).astype(np.int64), np.ascontiguousarray(np.asarray(tabs[1]).reshape(-1, 4), dtype=np.int32)
+    packed = packed.contiguous()
+    ops.set_frame_width(W)
+    classes_l = [int(c) for c in classes][:n]
+    scores64 = np.asarray([float(v) for v in scores][:n], dtype=np.float64)
+    d_bbox_t = torch.from_numpy(d_bbox).to(ops.device)
+    if any(isinstance(a.get("segmentation"), dict) for a in anns):
+        g_packed, g_area_t, g_bbox_t = _gt_masks(ops, anns, H, W)          # (RLE ground truth: its own waits)
+        err = []
+    else:
+        if any(a.get("segmentation") is None for a in anns):
+            raise ValueError("ground truth without a segmentation cannot be scored for masks")
+        err = []
+        g_packed, g_area_t, g_bbox_t = CE.rasterize_polygons(ops, [a["segmentation"] for a in anns], H, W, err_out=err)
+    g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
+    inter_t = CE.cross_matrix(ops, packed, d_bbox_t, np.asarray(classes_l, dtype=np.int64), g_packed, g_bbox_t, g_cat, W)
+    n_t, counts_t = CE.rle_counts_launch(ops, packed, d_bbox_t, W, CE.rle_room(d_bbox))
+    room = int(counts_t.shape[0])
+    host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [counts_t]).cpu().numpy()   # the ONE wait
+    n_host, pos = host[:n], n
+    inter = host[pos:pos + n * G].reshape(n, G).astype(np.int64)
+    pos += n * G
+    g_px = host[pos:pos + G].astype(np.int64)
+    pos += G
+    if err:
+        CE.check_rasterize_error(int(host[pos]))
+        pos += 1
+    runs = CE.rle_counts_finish(n_host, host[pos:pos + room]) if n else (np.zeros((0,), np.uint32), np.zeros((1,), np.int64))
+    if runs is None:
+        system_logger.debug(f"{rec['file_name']}: run lengths need more than {room} counts; encoding again")
+        runs = CE.rle_counts(ops, packed, d_bbox_t, W)
+    strings = CE.rle_strings(*runs)
+    xywh = CE.rle_to_bbox(runs[0], runs[1], H)
+    xywh_l, scores_l = xywh.tolist(), scores64.tolist()
+    instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
+                  "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter)
     return {"instances": instances}

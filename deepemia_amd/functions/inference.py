@@ -1889,24 +1889,151 @@ class InferencePipeline:
         return {c: float(np.mean(v)) for c, v in sizes.items() if v}
 
 
+class PipelineSettings:
+    """What the per-image pipeline reads from the configuration (``inference_overrides`` or ``inference_settings`` of the
+    dataset, the global ensemble defaults): shared by ``run_inference`` and the pipeline mode of the evaluate task."""
+
+    def __init__(self, dataset_name: str):
+        self.global_config = get_config()
+        dataset_config = get_config(dataset_name=dataset_name)
+        inf = dataset_config.get("inference_overrides", {}) or dataset_config.get("inference_settings", {})
+        self.inf = inf
+        self.confidence_mode = inf.get("confidence_mode", "auto")
+        self.class_specific_settings = inf.get("class_specific_settings", {})
+        tile_cfg = inf.get("tile_settings", {})
+        self.tile_size = tile_cfg.get("tile_size", 512)
+        self.overlap_ratio = tile_cfg.get("overlap_ratio", 0.1)
+        self.upscale_factor = tile_cfg.get("upscale_factor", 2.0)
+        self.edge_filter_enabled = tile_cfg.get("edge_filter_enabled", True)
+        ens = inf.get("ensemble_settings", {})
+        gens = self.global_config.get("inference_settings", {}).get("ensemble_settings", {})
+        self.ensemble_enabled = ens.get("enabled", gens.get("enabled", True))
+        self.ensemble_small_only = ens.get("small_classes_only", gens.get("small_classes_only", True))
+        self.classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
+
+    def target_classes(self, num_classes: int) -> List[int]:
+        return list(range(num_classes) if self.classes_to_infer is None else [c for c in self.classes_to_infer if c < num_classes])
+
+    def models_needed(self, n_predictors: int, small_classes, num_classes: int) -> List[int]:
+        """The models whose standard forwards an image needs: all of them when some class is ensembled, else the first."""
+        any_ens = n_predictors > 1 and any(self.ensemble_enabled and (not self.ensemble_small_only or c in small_classes)
+                                           for c in self.target_classes(num_classes))
+        return list(range(n_predictors)) if any_ens else [0]
+
+
+def image_phases_enabled(pipe: "InferencePipeline") -> bool:
+    """Whether every class of an image may go through the one model's passes in phases (``tile_pipeline_all_classes``)."""
+    return pipe.world == 1 and pipe.merge_mode == "smart" and os.environ.get("DEEPEMIA_IMAGE_PHASES", "1") == "1"     # (A/B switch)
+
+
+def final_instances(pipe: "InferencePipeline", st: PipelineSettings, name: str, image_dev: torch.Tensor, small_classes, num_classes: int,
+                    spatial_cfg, phases_ok: bool):
+    """One image through the class loop, the merges, the 0.7 cross-class pass and the spatial constraints (reference
+    inference.py:735-931): the image's final ``(packed, scores, classes, tabs)`` with ``tabs = (area, bbox[, ...])`` on the host,
+    ``tabs`` None and ``packed`` None or empty when nothing is left.  ``run_inference`` and the evaluate task's pipeline mode
+    both call this; the forwards come from the pipeline's cache where a prefetch filed them."""
+    predictors = pipe.predictors
+    global_config, confidence_mode, class_specific_settings = st.global_config, st.confidence_mode, st.class_specific_settings
+    tile_size, overlap_ratio, upscale_factor, edge_filter_enabled = st.tile_size, st.overlap_ratio, st.upscale_factor, st.edge_filter_enabled
+    ensemble_enabled, ensemble_small_only, classes_to_infer = st.ensemble_enabled, st.ensemble_small_only, st.classes_to_infer
+    image_host = None
+    parts, all_scores, all_classes = [], [], []
+    locals_by_class, ens_by_class, local_err = {}, {}, None
+    targets = range(num_classes) if classes_to_infer is None else [c for c in classes_to_infer if c < num_classes]
+    fast = {}
+    if phases_ok:
+        for target_class in targets:
+            is_small = target_class in small_classes
+            ccfg = class_specific_settings.get(f"class_{target_class}", {})
+            use_ens = ensemble_enabled and (not ensemble_small_only or is_small)
+            if (use_ens and len(predictors) > 1) or pipe.uses_multiscale(target_class):
+                fast = None
+                break
+            if confidence_mode == "manual":
+                conf = ccfg.get("confidence_threshold", 0.3 if is_small else 0.5)
+            else:
+                if image_host is None:
+                    image_host = image_dev.cpu().numpy()
+                conf = get_confidence_threshold(image_host, target_class, small_classes, global_config)
+            fast[target_class] = (conf, ccfg.get("iou_threshold", 0.5 if is_small else 0.7))
+    if fast:
+        # every class goes through the one model's standard passes: all classes in phases, two waits (tile_pipeline_all_classes)
+        by_class = pipe.tile_pipeline_all_classes(name, image_dev, fast, small_classes, tile_size, overlap_ratio, upscale_factor, edge_filter_enabled)
+        for target_class in targets:
+            m, s, c = by_class[target_class]
+            if m is not None and m.shape[0]:
+                parts.append(m)
+                all_scores.extend(s)
+                all_classes.extend(c)
+        targets = []
+    for target_class in targets:
+        is_small = target_class in small_classes
+        ccfg = class_specific_settings.get(f"class_{target_class}", {})
+        if confidence_mode == "manual":
+            conf = ccfg.get("confidence_threshold", 0.3 if is_small else 0.5)
+        else:
+            if image_host is None:
+                image_host = image_dev.cpu().numpy()
+            conf = get_confidence_threshold(image_host, target_class, small_classes, global_config)
+        iou_thresh = ccfg.get("iou_threshold", 0.5 if is_small else 0.7)
+        use_ens = ensemble_enabled and (not ensemble_small_only or is_small)
+        model_ids = list(range(len(predictors))) if (use_ens and len(predictors) > 1) else [0]
+        if pipe.world > 1:
+            # local passes only; ONE all-gather per image after the class loop.  A failure of THIS rank's passes
+            # (a kernel error, out of memory on its tiles) must not make it skip that all-gather: it takes part with
+            # an empty table and status 1, and every rank skips the image together (PeerImageFailure below)
+            if local_err is None:
+                try:
+                    locals_by_class[target_class] = pipe._tile_pipeline_local(model_ids, name, image_dev, target_class, small_classes, conf,
+                                                                              tile_size, overlap_ratio, upscale_factor, iou_thresh,
+                                                                              edge_filter_enabled)
+                    ens_by_class[target_class] = len(model_ids) > 1
+                except Exception as e:
+                    system_logger.error(f"Rank {pipe.rank}: local passes of image {name} failed: {e}", exc_info=True)
+                    local_err = e
+            continue
+        m, s, c = pipe.tile_based_inference_pipeline(model_ids, name, image_dev, target_class, small_classes, conf,
+                                                     tile_size, overlap_ratio, upscale_factor, iou_thresh,
+                                                     edge_filter_enabled)
+        if m is not None and m.shape[0]:
+            parts.append(m)
+            all_scores.extend(s)
+            all_classes.extend(c)
+    if pipe.world > 1:
+        merged = pipe.gather_and_merge({} if local_err is not None else locals_by_class, (int(image_dev.shape[0]), int(image_dev.shape[1])),
+                                       ens_by_class, status=0 if local_err is None else 1)
+        for target_class in targets:
+            r = merged[target_class]
+            if isinstance(r, Exception):
+                raise r               # the reference raises inside the class loop and skips the image (N4)
+            m, s, c = r
+            if m is not None and m.shape[0]:
+                parts.append(m)
+                all_scores.extend(s)
+                all_classes.extend(c)
+    packed = torch.cat(parts, dim=0) if parts else None
+    pipe.ops.set_frame_width(int(image_dev.shape[1]))
+    constrained = bool(spatial_cfg and spatial_cfg.get("enabled", False)) and os.environ.get("DEEPEMIA_ALL_PAIRS", "1") == "1"   # (A/B switch)
+    packed, scores, classes, tabs = pipe.deduplicate_masks_smart(packed, all_scores, all_classes, iou_threshold=0.7, with_tables=True,
+                                                                all_pairs=constrained)
+    if packed is not None and packed.shape[0]:
+        alg = DeviceMaskAlgebra(pipe.ops, packed, area=tabs[0], bbox=tabs[1])       # (pixel counts / boxes: already on the host)
+        if tabs[2] is not None:
+            alg.preload(tabs[2])        # ... and every pair's intersection: the constraints below launch and wait for nothing
+        keep = apply_spatial_constraints_indices(alg, scores, classes, spatial_cfg)
+        if len(keep) != int(packed.shape[0]):
+            packed = pipe.ops.gather_regions(packed, keep, tabs[1][keep])
+            tabs = (tabs[0][keep], tabs[1][keep])
+        scores, classes = [scores[i] for i in keep], [classes[i] for i in keep]
+    return packed, scores, classes, tabs
+
+
 def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw_id=False, dataset_format="json",
                   draw_scalebar=False):
     """Drop-in for ``src/functions/inference.py:499`` (same signature, outputs and skip-image semantics)."""
-    global_config = get_config()
-    dataset_config = get_config(dataset_name=dataset_name)
-    inf = dataset_config.get("inference_overrides", {}) or dataset_config.get("inference_settings", {})
-    confidence_mode = inf.get("confidence_mode", "auto")
-    class_specific_settings = inf.get("class_specific_settings", {})
-    tile_cfg = inf.get("tile_settings", {})
-    tile_size = tile_cfg.get("tile_size", 512)
-    overlap_ratio = tile_cfg.get("overlap_ratio", 0.1)
-    upscale_factor = tile_cfg.get("upscale_factor", 2.0)
-    edge_filter_enabled = tile_cfg.get("edge_filter_enabled", True)
-    ens = inf.get("ensemble_settings", {})
-    gens = global_config.get("inference_settings", {}).get("ensemble_settings", {})
-    ensemble_enabled = ens.get("enabled", gens.get("enabled", True))
-    ensemble_small_only = ens.get("small_classes_only", gens.get("small_classes_only", True))
-    classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
+    st = PipelineSettings(dataset_name)
+    global_config, inf = st.global_config, st.inf
+    tile_size, overlap_ratio, upscale_factor = st.tile_size, st.overlap_ratio, st.upscale_factor
     split_dir = str(Path(global_config["paths"]["split_dir"]).expanduser().resolve())
     category_json = str(Path(global_config["paths"]["category_json"]).expanduser().resolve())
 
@@ -2081,9 +2208,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
             pipe.drop_cached(nm)
     sample = []
     t_all = time.perf_counter()
-    targets_all = list(range(num_classes) if classes_to_infer is None else [c for c in classes_to_infer if c < num_classes])
-    any_ens = len(predictors) > 1 and any(ensemble_enabled and (not ensemble_small_only or c in small_classes) for c in targets_all)
-    models_needed = list(range(len(predictors))) if any_ens else [0]
+    models_needed = st.models_needed(len(predictors), small_classes, num_classes)
     if ahead is not None:
         ok0 = [(nm, t) for nm, t in ahead[0].items() if t is not None]
         ahead = (ahead[0], enqueue_forwards(ok0, models_needed) if (ok0 and len(models_needed) > 1) else None)
@@ -2106,95 +2231,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     system_logger.error(f"Error processing image {name}: {e}")
             return
         try:
-            image_host = None
-            parts, all_scores, all_classes = [], [], []
-            locals_by_class, ens_by_class, local_err = {}, {}, None
-            targets = range(num_classes) if classes_to_infer is None else [c for c in classes_to_infer if c < num_classes]
-            fast = {}
-            if phases_ok:
-                for target_class in targets:
-                    is_small = target_class in small_classes
-                    ccfg = class_specific_settings.get(f"class_{target_class}", {})
-                    use_ens = ensemble_enabled and (not ensemble_small_only or is_small)
-                    if (use_ens and len(predictors) > 1) or pipe.uses_multiscale(target_class):
-                        fast = None
-                        break
-                    if confidence_mode == "manual":
-                        conf = ccfg.get("confidence_threshold", 0.3 if is_small else 0.5)
-                    else:
-                        if image_host is None:
-                            image_host = image_dev.cpu().numpy()
-                        conf = get_confidence_threshold(image_host, target_class, small_classes, global_config)
-                    fast[target_class] = (conf, ccfg.get("iou_threshold", 0.5 if is_small else 0.7))
-            if fast:
-                # every class goes through the one model's standard passes: all classes in phases, two waits (tile_pipeline_all_classes)
-                by_class = pipe.tile_pipeline_all_classes(name, image_dev, fast, small_classes, tile_size, overlap_ratio, upscale_factor, edge_filter_enabled)
-                for target_class in targets:
-                    m, s, c = by_class[target_class]
-                    if m is not None and m.shape[0]:
-                        parts.append(m)
-                        all_scores.extend(s)
-                        all_classes.extend(c)
-                targets = []
-            for target_class in targets:
-                is_small = target_class in small_classes
-                ccfg = class_specific_settings.get(f"class_{target_class}", {})
-                if confidence_mode == "manual":
-                    conf = ccfg.get("confidence_threshold", 0.3 if is_small else 0.5)
-                else:
-                    if image_host is None:
-                        image_host = image_dev.cpu().numpy()
-                    conf = get_confidence_threshold(image_host, target_class, small_classes, global_config)
-                iou_thresh = ccfg.get("iou_threshold", 0.5 if is_small else 0.7)
-                use_ens = ensemble_enabled and (not ensemble_small_only or is_small)
-                model_ids = list(range(len(predictors))) if (use_ens and len(predictors) > 1) else [0]
-                if pipe.world > 1:
-                    # local passes only; ONE all-gather per image after the class loop.  A failure of THIS rank's passes
-                    # (a kernel error, out of memory on its tiles) must not make it skip that all-gather: it takes part with
-                    # an empty table and status 1, and every rank skips the image together (PeerImageFailure below)
-                    if local_err is None:
-                        try:
-                            locals_by_class[target_class] = pipe._tile_pipeline_local(model_ids, name, image_dev, target_class, small_classes, conf,
-                                                                                      tile_size, overlap_ratio, upscale_factor, iou_thresh,
-                                                                                      edge_filter_enabled)
-                            ens_by_class[target_class] = len(model_ids) > 1
-                        except Exception as e:
-                            system_logger.error(f"Rank {pipe.rank}: local passes of image {name} failed: {e}", exc_info=True)
-                            local_err = e
-                    continue
-                m, s, c = pipe.tile_based_inference_pipeline(model_ids, name, image_dev, target_class, small_classes, conf,
-                                                             tile_size, overlap_ratio, upscale_factor, iou_thresh,
-                                                             edge_filter_enabled)
-                if m is not None and m.shape[0]:
-                    parts.append(m)
-                    all_scores.extend(s)
-                    all_classes.extend(c)
-            if pipe.world > 1:
-                merged = pipe.gather_and_merge({} if local_err is not None else locals_by_class, (int(image_dev.shape[0]), int(image_dev.shape[1])),
-                                               ens_by_class, status=0 if local_err is None else 1)
-                for target_class in targets:
-                    r = merged[target_class]
-                    if isinstance(r, Exception):
-                        raise r               # the reference raises inside the class loop and skips the image (N4)
-                    m, s, c = r
-                    if m is not None and m.shape[0]:
-                        parts.append(m)
-                        all_scores.extend(s)
-                        all_classes.extend(c)
-            packed = torch.cat(parts, dim=0) if parts else None
-            pipe.ops.set_frame_width(int(image_dev.shape[1]))
-            constrained = bool(spatial_cfg and spatial_cfg.get("enabled", False)) and os.environ.get("DEEPEMIA_ALL_PAIRS", "1") == "1"   # (A/B switch)
-            packed, scores, classes, tabs = pipe.deduplicate_masks_smart(packed, all_scores, all_classes, iou_threshold=0.7, with_tables=True,
-                                                                        all_pairs=constrained)
-            if packed is not None and packed.shape[0]:
-                alg = DeviceMaskAlgebra(pipe.ops, packed, area=tabs[0], bbox=tabs[1])       # (pixel counts / boxes: already on the host)
-                if tabs[2] is not None:
-                    alg.preload(tabs[2])        # ... and every pair's intersection: the constraints below launch and wait for nothing
-                keep = apply_spatial_constraints_indices(alg, scores, classes, spatial_cfg)
-                if len(keep) != int(packed.shape[0]):
-                    packed = pipe.ops.gather_regions(packed, keep, tabs[1][keep])
-                    tabs = (tabs[0][keep], tabs[1][keep])
-                scores, classes = [scores[i] for i in keep], [classes[i] for i in keep]
+            packed, scores, classes, tabs = final_instances(pipe, st, name, image_dev, small_classes, num_classes, spatial_cfg, phases_ok)
             n_final = 0 if packed is None else int(packed.shape[0])
             result = {"masks": packed, "scores": scores, "classes": classes, "hw": (int(image_dev.shape[0]), int(image_dev.shape[1])),
                       "area": None if tabs is None else tabs[0], "bbox": None if tabs is None else tabs[1]}
@@ -2227,7 +2264,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
     # DEEPEMIA_IMAGE_THREADS=k (experiment switch, default 1): the images of a group are post-processed by k host threads at once
     # (every thread its own MaskOps; forwards stay on this thread) -- their device-to-host waits then overlap instead of queueing
     # one after the other behind the next group's convolution grids
-    phases_ok = pipe.world == 1 and pipe.merge_mode == "smart" and os.environ.get("DEEPEMIA_IMAGE_PHASES", "1") == "1"     # (A/B switch)
+    phases_ok = image_phases_enabled(pipe)
     image_threads = max(1, int(os.environ.get("DEEPEMIA_IMAGE_THREADS", "1"))) if pipe.world == 1 else 1
     image_pool = ThreadPoolExecutor(max_workers=image_threads) if image_threads > 1 else None
 

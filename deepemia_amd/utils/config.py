@@ -9,6 +9,7 @@ elsewhere.  Dataset blocks are folded into the global dict as the reference does
   ``scale_bar_roi``        -> ``scale_bar_rois[<dataset>]``
   ``scalebar_thresholds``  -> deep-merged
   ``scale_bar``            -> deep-merged (not in the reference: the label / calibration that replaces the OCR)
+  ``evaluation``           -> deep-merged (not in the reference: ``mode`` / ``max_dets`` of the evaluate task)
   ``spatial_constraints``  -> ``inference_settings.spatial_constraints[<dataset>]``
   ``rcnn_hyperparameters.best_R50 / best_R101`` -> ``rcnn_hyperparameters.best.R50 / R101``
 """
@@ -90,6 +91,8 @@ def get_config(dataset_name: str = None) -> Dict[str, Any]:
         merged["scalebar_thresholds"] = deep_merge(merged.get("scalebar_thresholds", {}), ds["scalebar_thresholds"])
     if "scale_bar" in ds:        # this build's extension (no OCR): label / text_center / um_per_pixel per dataset
         merged["scale_bar"] = deep_merge(merged.get("scale_bar", {}) or {}, ds["scale_bar"])
+    if "evaluation" in ds:       # this build's extension: the evaluate task's mode (predictor | pipeline) and maxDets
+        merged["evaluation"] = deep_merge(merged.get("evaluation", {}) or {}, ds["evaluation"] or {})
     if "spatial_constraints" in ds:
         inf = merged.setdefault("inference_settings", {})
         if "spatial_constraints" not in inf:

@@ -119,7 +119,9 @@ def launch_workers(workers: int, argv) -> int:
 
 def run_evaluate(args) -> int:
     """``--task evaluate`` (reference ``main.py:442-454``): one process on one GPU; the results go to ``split_dir``.  Only
-    ``dataset_info.json`` is fetched from GCS (same gate as inference), nothing is uploaded."""
+    ``dataset_info.json`` is fetched from GCS (same gate as inference), nothing is uploaded.  The mode -- the bare predictor
+    (default) or the tiled inference pipeline -- comes from the configuration's ``evaluation.mode`` / ``DEEPEMIA_EVAL_MODE``;
+    the pipeline mode takes ``--threshold`` and ``--rcnn combo`` as ``--task inference`` does."""
     from deepemia_amd.utils.config import get_config
     from deepemia_amd.utils.gpu_check import check_gpu_availability, log_device_info
     from deepemia_amd.utils.logger_utils import system_logger
@@ -127,11 +129,18 @@ def run_evaluate(args) -> int:
     if not args.dataset_name:
         system_logger.error("--dataset_name is required for --task evaluate")
         return 2
-    if args.rcnn == "combo":
-        system_logger.error("--rcnn combo is not supported by --task evaluate: evaluate one model at a time (--rcnn 50 or 101)")
-        return 2
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         system_logger.error("--task evaluate runs in ONE process; start it without torchrun (WORLD_SIZE > 1)")
+        return 2
+    from deepemia_amd.functions.evaluate_model import evaluation_settings
+    try:
+        mode, _ = evaluation_settings(args.dataset_name)
+    except ValueError as e:
+        system_logger.error(f"evaluation settings: {e}")
+        return 2
+    if args.rcnn == "combo" and mode != "pipeline":
+        system_logger.error("--rcnn combo is not supported by --task evaluate in predictor mode: evaluate one model at a time "
+                            "(--rcnn 50 or 101), or the inference pipeline with both (evaluation.mode: pipeline)")
         return 2
     config = get_config()
     if not args.no_gpu_check:
@@ -151,9 +160,10 @@ def run_evaluate(args) -> int:
     from deepemia_amd.functions.evaluate_model import evaluate_model
 
     t0 = time.perf_counter()
-    system_logger.info(f"Evaluating model on dataset {args.dataset_name} using '{args.dataset_format}' format...")
+    system_logger.info(f"Evaluating model on dataset {args.dataset_name} using '{args.dataset_format}' format ({mode} mode)...")
     try:
-        evaluate_model(args.dataset_name, str(split_dir), args.visualize, dataset_format=args.dataset_format, rcnn=int(args.rcnn))
+        evaluate_model(args.dataset_name, str(split_dir), args.visualize, dataset_format=args.dataset_format,
+                       rcnn=args.rcnn if args.rcnn == "combo" else int(args.rcnn), mode=mode, threshold=args.threshold)
     except Exception:
         system_logger.error("evaluation failed", exc_info=True)
         return 1
