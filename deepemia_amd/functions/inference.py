@@ -37,7 +37,7 @@ from ..utils.mask_algebra import DeviceMaskAlgebra
 from ..utils.measurements import contrast_percentiles
 from ..utils.mask_utils import (mask_crops, postprocess_masks_device, postprocess_masks_universal_device,
                                 process_masks_device, rle_crop_launch, rle_encoding_packed, rle_text_from_payload,
-                                rle_text_packed)
+                                rle_text_packed, universal_min_size)
 from ..utils.spatial_constraints import apply_spatial_constraints_indices, load_spatial_constraints
 
 CSV_HEADER = ["Instance_ID", "Class", "Class_Name", "Major axis length", "Minor axis length", "Eccentricity", "C. Length",
@@ -249,6 +249,41 @@ class _PassTables:
 
     def __init__(self, area: np.ndarray, bbox: np.ndarray):
         self.area, self.bbox = area, bbox
+
+
+# ---- the decision rules of the vectorised paths, each stated ONCE.  The scalar
+# ---- loops of the host-loop twins spell the same rules out themselves: they are the checkers of what uses these.
+def _not_artefact(area: np.ndarray, bbox: np.ndarray, per0: np.ndarray) -> np.ndarray:
+    """Step 1 of ``deduplicate_masks_smart`` (``inference.py:2552-2677``, before its greedy loop) over whole tables: a mask stays unless it is empty
+    (``bbox[:, 0] < 0``) or its first contour is ragged, ``4 pi A / P^2 < 0.15`` where the perimeter ``P`` is > 0."""
+    return (bbox[:, 0] >= 0) & ~((per0 > 0) & ((4 * np.pi * area) / np.where(per0 > 0, per0, 1.0) ** 2 < 0.15))
+
+
+def _class_min_size(class_specific_settings: dict, target_class: int, is_small: bool):
+    """The ``min_crys_size`` of the single-model class pass (``inference.py:1434``): ``class_specific_settings.class_<c>.min_size``, else 5 / 25."""
+    return class_specific_settings.get(f"class_{target_class}", {}).get("min_size", 5 if is_small else 25)
+
+
+def _smart_dedup_keep(lib, I: np.ndarray, ld: int, run_first: np.ndarray, area: np.ndarray, bbox: np.ndarray,
+                      groups: Sequence[np.ndarray], scores: np.ndarray, classes: np.ndarray, thr: float) -> List[np.ndarray]:
+    """Step 2 of ``deduplicate_masks_smart`` (N6 literally) for MANY independent groups -- tiles, segments -- as ONE native
+    call (``demia_host_dedup_smart``) over host tables; no device work.  ``groups[g]``: the candidate mask indices of group
+    ``g`` (its survivors of step 1, in the caller's order); ``scores`` f64 / ``classes`` i32 per mask; ``I`` i32 ``[n, ld]``
+    with row i, column j - run_first[i] = |i & j| for j > i of the same run; ``area`` i64 ``[n]``, ``bbox`` i64 ``[n, 4]``.
+    Returns the kept mask indices of every group, in keep order."""
+    items = np.ascontiguousarray(np.concatenate(groups) if len(groups) else np.zeros(0), dtype=np.int32)
+    if len(items) == 0:
+        return [np.zeros(0, dtype=np.int64) for _ in groups]
+    T = len(groups)
+    tile_off = np.concatenate(([0], np.cumsum([len(g) for g in groups]))).astype(np.int32)
+    sc_items = np.ascontiguousarray(scores[items], dtype=np.float64)
+    cl_items = np.ascontiguousarray(classes[items], dtype=np.int32)
+    keep_out = np.zeros(len(items), dtype=np.int32)
+    keep_cnt = np.zeros(T, dtype=np.int32)
+    _L.check(lib.demia_host_dedup_smart(I.ctypes.data, ld, run_first.ctypes.data, area.ctypes.data, bbox.ctypes.data,
+                                        items.ctypes.data, sc_items.ctypes.data, cl_items.ctypes.data, tile_off.ctypes.data, T,
+                                        float(thr), keep_out.ctypes.data, keep_cnt.ctypes.data), "demia_host_dedup_smart")
+    return [np.asarray(groups[t])[keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]]] for t in range(T)]
 
 
 class EmptyEnsembleTypeError(ValueError):
@@ -481,8 +516,7 @@ class InferencePipeline:
         masks = det.packed[si].contiguous()
         hint = None if det.bbox is None else det.bbox[si].contiguous()
         is_small = target_class in small_classes
-        ccfg = self.class_specific_settings.get(f"class_{target_class}", {})
-        min_size = ccfg.get("min_size", 5 if is_small else 25)
+        min_size = _class_min_size(self.class_specific_settings, target_class, is_small)
         processed = postprocess_masks_device(self.ops, masks, scores, min_crys_size=min_size, bbox=hint)
         if processed is None or processed.shape[0] == 0:
             return None, [], []
@@ -586,34 +620,10 @@ class InferencePipeline:
         cset = ops.trace(packed, max_contours=256, bbox=bbox_d, max_points=int(min(4096 * n + (1 << 16), 1 << 26)))
         ld = max(1, int(run_count.max()))
         I = ops.pair_matrix(packed, bbox_d, run_first, np.maximum(run_count, 1), None, ld)
-        extra = [area_d.to(torch.int32), bbox_d, I]
-        try:
-            area_h, bbox_h, I_h = cset.fetch(extra=extra)
-        except _L.HipKernelError as e:
-            if "overflow" not in str(e):
-                raise
-            cset = ops.trace(packed, max_contours=256, bbox=bbox_d, total_area=int(area_d.sum().item()))
-            area_h, bbox_h, I_h = cset.fetch(extra=extra)
-        self.d2h_waits += 1
-        area = np.ascontiguousarray(area_h, dtype=np.int64)
-        bbox = np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64)
-        per0 = cset.first_contour_perimeter()
-        ok = (bbox[:, 0] >= 0) & ~((per0 > 0) & ((4 * np.pi * area) / np.where(per0 > 0, per0, 1.0) ** 2 < 0.15))
-        per_seg = [np.nonzero(ok[s0:s1])[0] + s0 for s0, s1 in segments]
-        items = np.ascontiguousarray(np.concatenate(per_seg) if per_seg else np.zeros(0), dtype=np.int32)
-        if len(items) == 0:
-            return [empty for _ in segments]
-        T = len(segments)
-        tile_off = np.concatenate(([0], np.cumsum([len(k) for k in per_seg]))).astype(np.int32)
-        sc_items = np.ascontiguousarray(np.asarray([scores[i] for i in items], dtype=np.float64))
-        cl_items = np.ascontiguousarray(cl[items])
-        keep_out = np.zeros(len(items), dtype=np.int32)
-        keep_cnt = np.zeros(T, dtype=np.int32)
-        I_c = np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32)
-        _L.check(ops.lib.demia_host_dedup_smart(I_c.ctypes.data, ld, run_first.ctypes.data, area.ctypes.data, bbox.ctypes.data,
-                                                items.ctypes.data, sc_items.ctypes.data, cl_items.ctypes.data, tile_off.ctypes.data, T,
-                                                float(iou_threshold), keep_out.ctypes.data, keep_cnt.ctypes.data), "demia_host_dedup_smart")
-        gls = [per_seg[t][keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]]] for t in range(T)]
+        cset, area, bbox, I_c = self._fetch_traced_tables(cset, packed, area_d, bbox_d, I, ld)
+        ok = _not_artefact(area, bbox, cset.first_contour_perimeter())
+        gls = _smart_dedup_keep(ops.lib, I_c, ld, run_first, area, bbox, [np.nonzero(ok[s0:s1])[0] + s0 for s0, s1 in segments],
+                                np.asarray(scores, dtype=np.float64), cl, iou_threshold)
         flat = np.concatenate(gls) if gls else np.zeros(0, dtype=np.int64)
         if len(flat) == 0:
             return [empty for _ in segments]
@@ -636,6 +646,26 @@ class InferencePipeline:
             pos += k
         return out
 
+    def _fetch_traced_tables(self, cset, packed: torch.Tensor, area_d: torch.Tensor, bbox_d: torch.Tensor, I: torch.Tensor, ld: int):
+        """THE wait of a smart-dedup stage whose trace was enqueued before the masks' areas were on the host (point pool sized
+        from the mask COUNT): the contour set's tables plus pixel counts, tight boxes and the pair matrix in one fetch.  A few
+        large ragged masks (boundaries of thousands of points) can overflow that pool; the areas are on the device by then, so
+        the masks are traced again with the area-sized pool ``MaskOps.trace`` defaults to and fetched again -- one more wait
+        for the areas, counted here.  Returns (contour set, area i64 [n], bbox i64 [n, 4], I i32 [n, ld])."""
+        extra = [area_d.to(torch.int32), bbox_d, I]
+        try:
+            area_h, bbox_h, I_h = cset.fetch(extra=extra)
+        except _L.HipKernelError as e:
+            if "overflow" not in str(e):
+                raise
+            self.d2h_waits += 1
+            cset = self.ops.trace(packed, max_contours=256, bbox=bbox_d, total_area=int(area_d.sum().item()))
+            area_h, bbox_h, I_h = cset.fetch(extra=extra)
+        self.d2h_waits += 1
+        n = int(packed.shape[0])
+        return (cset, np.ascontiguousarray(area_h, dtype=np.int64), np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64),
+                np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
+
     def deduplicate_masks_smart_hostloops(self, packed: Optional[torch.Tensor], scores: Sequence[float], classes: Sequence[int],
                                           iou_threshold: float = 0.4):
         """The host-loop version of :meth:`deduplicate_masks_smart` (general class order; its checker)."""
@@ -656,17 +686,8 @@ class InferencePipeline:
             return None, [], []
         scores = [scores[i] for i in keep0]
         classes = [classes[i] for i in keep0]
-        # stored as (y_min, y_max, x_min, x_max) ... (inference.py:2635)
+        # stored as (y_min, y_max, x_min, x_max) (inference.py:2635), read as (y_min, x_min, y_max, x_max) (:2685): N6
         bb = [(int(alg.bbox[i, 0]), int(alg.bbox[i, 2]), int(alg.bbox[i, 1]), int(alg.bbox[i, 3])) for i in keep0]
-
-        def overlap_literal(b1, b2):  # ... unpacked as (y_min, x_min, y_max, x_max) (inference.py:2685)
-            y1_min, x1_min, y1_max, x1_max = b1
-            y2_min, x2_min, y2_max, x2_max = b2
-            if x1_max < x2_min or x2_max < x1_min:
-                return False
-            if y1_max < y2_min or y2_max < y1_min:
-                return False
-            return True
 
         alg.prefetch_overlapping_pairs([[keep0[i] for i in range(len(keep0)) if classes[i] == c] for c in set(classes)])
         keep = self._dedup_smart_order(alg, keep0, scores, classes, bb, iou_threshold)
@@ -923,8 +944,7 @@ class InferencePipeline:
         model_ids = [int(model_idx)] if isinstance(model_idx, (int, np.integer)) else [int(m) for m in model_idx]
         eng = self.predictors[model_ids[0]].engine
         is_small = target_class in small_classes
-        area0 = h * w
-        base_min = max(3, int(area0 * 0.000005)) if is_small else max(25, int(area0 * 0.0001))
+        base_min = universal_min_size(h * w, is_small)
 
         def single_scale(scale: float):
             sh, sw = (h, w) if scale == 1.0 else (int(h * scale), int(w * scale))
@@ -1091,27 +1111,14 @@ class InferencePipeline:
             self.ops.set_frame_width(uw)           # the tile masks' own frame: its right border is pixel uw - 1
             ht = self._single_class_pass_launch(tile_dets, cls, small_classes, conf)
             handles.append((cls, hf, ht))
-        live = [h_ for _, hf, ht in handles for h_ in (hf, ht) if h_ is not None]
-        host = torch.cat([t_ for h_ in live for t_ in (h_["ncols"], h_["area"], h_["bbox"].reshape(-1), h_["I"].reshape(-1))]).cpu().numpy() if live else None
-        if live:
-            self.d2h_waits += 1
-        pos = 0
-
-        def tables(h_):
-            nonlocal pos
-            T, n, ld = h_["T"], h_["n"], h_["ld"]
-            tabs = dict(ncols=host[pos:pos + T], area=host[pos + T:pos + T + n].astype(np.int64),
-                        bbox=host[pos + T + n:pos + T + 5 * n].reshape(n, 4).astype(np.int64),
-                        I=np.ascontiguousarray(host[pos + T + 5 * n:pos + T + 5 * n + n * ld]).reshape(n, ld))
-            pos += T + 5 * n + n * ld
-            return tabs
+        fetched = iter(self._fetch_class_pass_tables([h_ for _, hf, ht in handles for h_ in (hf, ht) if h_ is not None]))
         parts, scores, classes, segments = [], [], [], []
         for cls, hf, ht in handles:
             iou_thr = class_params[cls][1]
             is_small = cls in small_classes
             s0 = len(scores)
             if hf is not None:
-                big, res, tabs = self._single_class_pass_finish(hf, tables(hf), is_small, iou_thr)
+                big, res, tabs = self._single_class_pass_finish(hf, next(fetched), is_small, iou_thr)
                 kept, sc = res[0]
                 if kept:
                     self.ops.set_frame_width(w)
@@ -1119,7 +1126,7 @@ class InferencePipeline:
                     scores += list(sc)
                     classes += [cls] * len(kept)
             if ht is not None:
-                big, res, tabs = self._single_class_pass_finish(ht, tables(ht), is_small, iou_thr)
+                big, res, tabs = self._single_class_pass_finish(ht, next(fetched), is_small, iou_thr)
                 self.ops.set_frame_width(uw)
                 tm_, ts_, tc_, _ = self._place_tile_results(big, res, tabs, mine, offs, tile_size, uh, uw, h, w, edge, edge_filter_enabled, cls)
                 parts += tm_
@@ -1298,23 +1305,43 @@ class InferencePipeline:
         return packed, out, alg
 
     def _single_class_pass_batched(self, dets: Sequence[_Detections], target_class: int, small_classes, conf, iou_threshold):
-        """a6 + a9 + a11 + a12 for ONE class over MANY tiles: everything enqueued at once (:meth:`_single_class_pass_launch`),
-        ONE device-to-host wait for its tables, the greedy loop as one native call (:meth:`_single_class_pass_finish`).
-        Returns (masks, per tile (indices into them, scores), tables with ``area`` / ``bbox``).  The host-loop version
-        below is its checker."""
-        h = self._single_class_pass_launch(dets, target_class, small_classes, conf)
-        T = len(dets)
-        if h is None:
-            return None, [([], []) for _ in range(T)], None
-        host = torch.cat([h["ncols"], h["area"], h["bbox"].reshape(-1), h["I"].reshape(-1)]).cpu().numpy()
+        """a6 + a9 + a11 + a12 for ONE class over MANY tiles: the one-class call of :meth:`_single_class_passes`.
+        Returns (masks, per tile (indices into them, scores), tables with ``area`` / ``bbox``); (None, ..., None) when nothing
+        is kept.  The host-loop version below is its checker."""
+        done = self._single_class_passes(dets, [(target_class, conf, iou_threshold)], small_classes)[0]
+        if done is None:
+            return None, [([], []) for _ in dets], None
+        return done if any(len(k) for k, _ in done[1]) else (None, done[1], None)
+
+    def _single_class_passes(self, dets: Sequence[_Detections], class_params: Sequence[Tuple[int, float, float]], small_classes,
+                             release: bool = False):
+        """The single-model class passes of SEVERAL classes -- ``class_params``: (class, confidence, IoU threshold) each -- over
+        MANY tiles: everything of every class enqueued back to back (:meth:`_single_class_pass_launch`), ONE device-to-host
+        wait for all their tables, then per class the greedy loop as one native call (:meth:`_single_class_pass_finish`).
+        ``release``: the launches' gathers are the last reads of the forwards' own planes behind ``dets``.  Returns per class
+        (masks, per tile (indices into them, scores), tables) -- None for a class with no candidate in any tile."""
+        handles = [self._single_class_pass_launch(dets, cls, small_classes, conf) for cls, conf, _ in class_params]
+        if release:
+            self._release_forward_outputs(dets)
+        tabs = iter(self._fetch_class_pass_tables([h for h in handles if h is not None]))
+        return [None if h is None else self._single_class_pass_finish(h, next(tabs), cls in small_classes, iou_thr)
+                for (cls, _, iou_thr), h in zip(class_params, handles)]
+
+    def _fetch_class_pass_tables(self, handles: Sequence[dict]) -> List[dict]:
+        """THE wait of the launched class passes ``handles``: their tables in ONE device-to-host copy (per pass
+        ``ncols [T] | area [n] | bbox [n, 4] | I [n, ld]``, int32), unpacked into what :meth:`_single_class_pass_finish` reads."""
+        if not handles:
+            return []
+        host = torch.cat([t_ for h in handles for t_ in (h["ncols"], h["area"], h["bbox"].reshape(-1), h["I"].reshape(-1))]).cpu().numpy()
         self.d2h_waits += 1
-        n, ld = h["n"], h["ld"]
-        tabs = dict(ncols=host[:T], area=host[T:T + n].astype(np.int64), bbox=host[T + n:T + 5 * n].reshape(n, 4).astype(np.int64),
-                    I=np.ascontiguousarray(host[T + 5 * n:T + 5 * n + n * ld]).reshape(n, ld))
-        big, res, tables = self._single_class_pass_finish(h, tabs, target_class in small_classes, iou_threshold)
-        if not any(len(k) for k, _ in res):
-            return None, res, None
-        return big, res, tables
+        out, pos = [], 0
+        for h in handles:
+            T, n, ld = h["T"], h["n"], h["ld"]
+            out.append(dict(ncols=host[pos:pos + T], area=host[pos + T:pos + T + n].astype(np.int64),
+                            bbox=host[pos + T + n:pos + T + 5 * n].reshape(n, 4).astype(np.int64),
+                            I=np.ascontiguousarray(host[pos + T + 5 * n:pos + T + 5 * n + n * ld]).reshape(n, ld)))
+            pos += T + 5 * n + n * ld
+        return out
 
     def _single_class_pass_batched_hostloops(self, dets: Sequence[_Detections], target_class: int, small_classes, conf, iou_threshold):
         """a6 + a9 + a11 + a12 for ONE class over MANY tiles with one launch per kernel: the masks of all tiles are
@@ -1455,7 +1482,11 @@ class InferencePipeline:
     def process_tile_batch(self, key: str, tiles: torch.Tensor, small_classes, class_thresholds: Dict[int, Tuple[float, float]],
                            spatial_cfg: Optional[dict] = None, um_pix: float = 1.0, model_ids: Sequence[int] = (0,),
                            dets: Optional[List[_Detections]] = None):
-        """The per-tile unit of work of the headline metric (see :meth:`process_tile_batch_hostloops` for the stages).
+        """The per-tile unit of work of the headline metric: one batched forward for B independent tiles, then per tile the
+        class loop (a6, a9, a11, a12; ensembles: a10 + a14), the cross-class dedup (a14, 0.7), the spatial constraints (a15) and
+        the contour measurements (a17, a18).  Every kernel is launched ONCE for all tiles (segment-aware where the reference's
+        loop carries state), so 256 CUs see hundreds of masks per launch instead of a few dozen.  Returns per tile
+        ``(packed, scores, classes, records)``.
         Single-model calls take the THREE-WAIT path: the class passes of all classes are enqueued back to back with every
         data-dependent choice (the column-count truncation, the `> 2 masks` gate) made on the device, the pair counts come
         from ``demia_mask_pair_matrix`` (pair list made on the device), and the host waits once for the tables of all class
@@ -1463,7 +1494,8 @@ class InferencePipeline:
         stage (gather, contour trace, measurements of every candidate, pair matrix) and waits once more before the native
         smart dedup (``demia_host_dedup_smart``).  With the forward's own result that is three device-to-host waits per
         batch, whatever its size.  Same keep lists, masks and records as the host-loop version, which stays as its checker
-        (``tests/test_gpu_parity_maskops.py``)."""
+        (``tests/test_gpu_parity_maskops.py``).  The smart-dedup stage itself -- one fetch, :func:`_not_artefact`,
+        :func:`_smart_dedup_keep` -- is the one the ensemble passes and the CLI's merges (:meth:`deduplicate_masks_smart_segments`) run."""
         ensemble = len(model_ids) > 1
         ops, dev, lib = self.ops, self.dev, self.ops.lib
         ops.set_frame_width(int(tiles.shape[2]))
@@ -1488,26 +1520,10 @@ class InferencePipeline:
             T = len(dets)
             out = [(None, [], [], []) for _ in range(T)]
             self.last_batch_stats = [(np.zeros((0,), dtype=np.int64), np.zeros((0, 4), dtype=np.int64)) for _ in range(T)]
-            # ---- class passes: enqueue all, wait once ---------------------------------------------------------------
-            handles = [self._single_class_pass_launch(dets, cls, small_classes, conf) for cls, (conf, _) in class_thresholds.items()]
-            self._release_forward_outputs(dets)       # the gathers of the class passes were the last reads of the forward's planes
-            live = [h for h in handles if h is not None]
-            if not live:
-                return out
-            host = torch.cat([t_ for h in live for t_ in (h["ncols"], h["area"], h["bbox"].reshape(-1), h["I"].reshape(-1))]).cpu().numpy()
-            self.d2h_waits += 1
-            passes, pos = [], 0
-            for (cls, (_, iou_thr)), h in zip(class_thresholds.items(), handles):
-                if h is None:
-                    continue
-                n, ld = h["n"], h["ld"]
-                tabs = dict(ncols=host[pos:pos + T], area=host[pos + T:pos + T + n].astype(np.int64),
-                            bbox=host[pos + T + n:pos + T + 5 * n].reshape(n, 4).astype(np.int64),
-                            I=np.ascontiguousarray(host[pos + T + 5 * n:pos + T + 5 * n + n * ld]).reshape(n, ld))
-                pos += T + 5 * n + n * ld
-                big, res, calg = self._single_class_pass_finish(h, tabs, cls in small_classes, iou_thr)
-                if any(len(k) for k, _ in res):
-                    passes.append((cls, big, res, calg))
+            # ---- class passes: enqueue all (their gathers are the last reads of the forward's planes), wait once ------------
+            done = self._single_class_passes(dets, [(cls, conf, iou_thr) for cls, (conf, iou_thr) in class_thresholds.items()],
+                                             small_classes, release=True)
+            passes = [(cls,) + d for cls, d in zip(class_thresholds, done) if d is not None and any(len(k) for k, _ in d[1])]
         total = sum(len(k) for _, _, res, _ in passes for k, _ in res)
         if total == 0:
             return out
@@ -1550,26 +1566,13 @@ class InferencePipeline:
         I2 = ops.pair_matrix(allp, bbox_dev, run_first, run_count, None, ld2)
         (I2h,) = cset.fetch(extra=[I2], with_points=True)
         self.d2h_waits += 1
-        per0 = cset.first_contour_perimeter()
-        ok = (bbox_all[:, 0] >= 0) & ~((per0 > 0) & ((4 * np.pi * area_all) / np.where(per0 > 0, per0, 1.0) ** 2 < 0.15))
-        keep0_all = [[i for i in tile_items[t] if ok[i]] for t in range(T)]
-        items = np.asarray([i for k0 in keep0_all for i in k0], dtype=np.int32)
-        tile_off = np.concatenate(([0], np.cumsum([len(k0) for k0 in keep0_all]))).astype(np.int32)
-        keep_out = np.zeros(max(len(items), 1), dtype=np.int32)
-        keep_cnt = np.zeros(T, dtype=np.int32)
-        if len(items):
-            sc_items = np.ascontiguousarray(scores_all[items])
-            cl_items = np.ascontiguousarray(classes_all[items])
-            I2c = np.ascontiguousarray(I2h, dtype=np.int32)
-            _L.check(lib.demia_host_dedup_smart(I2c.ctypes.data, ld2, run_first.ctypes.data, area_all.ctypes.data, bbox_all.ctypes.data,
-                                                items.ctypes.data, sc_items.ctypes.data, cl_items.ctypes.data, tile_off.ctypes.data, T, 0.7,
-                                                keep_out.ctypes.data, keep_cnt.ctypes.data), "demia_host_dedup_smart")
+        ok = _not_artefact(area_all, bbox_all, cset.first_contour_perimeter())
+        kept = _smart_dedup_keep(lib, np.ascontiguousarray(I2h, dtype=np.int32), ld2, run_first, area_all, bbox_all,
+                                 [c[ok[c]] for c in (np.asarray(ti, dtype=np.int64) for ti in tile_items)], scores_all, classes_all, 0.7)
         final_idx: List[List[int]] = []
         alg = None
         for t in range(T):
-            k0 = keep0_all[t]
-            keep = keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]].tolist()
-            gl = [k0[i] for i in keep]
+            gl = kept[t].tolist()
             sc, cl = [scores_all[i] for i in gl], [int(classes_all[i]) for i in gl]
             sc = [float(v) for v in sc] if ensemble else [self._score_type(v) for v in sc]     # ensemble scores: f64 products
             if gl and spatial_cfg is not None and spatial_cfg.get("enabled", False):
@@ -1579,22 +1582,30 @@ class InferencePipeline:
                 gl, sc, cl = [gl[i] for i in kk], [sc[i] for i in kk], [cl[i] for i in kk]
             final_idx.append(gl)
             out[t] = (None, sc, cl, [])
+        out = self._tile_batch_results(out, final_idx, allp, area_all, bbox_all, cset, um_pix, self.pooled_planes)
+        self.d2h_waits += cset.blocking_point_copies       # (0 in the steady state: the points came with the fetch above)
+        return out
+
+    def _tile_batch_results(self, out, final_idx: List[List[int]], allp: torch.Tensor, area_all: np.ndarray, bbox_all: np.ndarray, cset,
+                            um_pix: float, pooled: bool):
+        """The tail of a tile batch, three-wait and host-loop version alike: ONE gather of the final masks ``final_idx[t]`` of every
+        tile out of ``allp`` (``pooled``: into the "final" plane pool), their contour records out of the candidates' trace, the
+        per-tile pixel counts / tight boxes in ``last_batch_stats`` (what an instance table needs; already reduced) and the
+        per-tile slices filled into ``out``."""
         flat = [i for gl in final_idx for i in gl]
         if not flat:
             return out
-        if self.pooled_planes:
-            finalp = ops.gather_regions_pooled(allp, flat, bbox_all[flat], ops.pool("final", len(flat), H_, wpr_), grow=0)
+        if pooled:
+            finalp = self.ops.gather_regions_pooled(allp, flat, bbox_all[flat], self.ops.pool("final", len(flat), int(allp.shape[1]), int(allp.shape[2])), grow=0)
         else:
-            finalp = ops.gather_regions(allp, flat, bbox_all[flat])
+            finalp = self.ops.gather_regions(allp, flat, bbox_all[flat])
         recs = cset.records(um_pix=um_pix, measure=True, select=flat)
-        self.d2h_waits += cset.blocking_point_copies       # (0 in the steady state: the points came with the fetch above)
+        self.last_batch_stats = [(area_all[gl], bbox_all[gl]) for gl in final_idx]
         pos = 0
-        self.last_batch_stats = [(area_all[final_idx[t]], bbox_all[final_idx[t]]) for t in range(T)]
-        for t in range(T):
-            n = len(final_idx[t])
-            if n:
-                out[t] = (finalp[pos:pos + n], out[t][1], out[t][2], recs[pos:pos + n])
-            pos += n
+        for t, gl in enumerate(final_idx):
+            if gl:
+                out[t] = (finalp[pos:pos + len(gl)], out[t][1], out[t][2], recs[pos:pos + len(gl)])
+            pos += len(gl)
         return out
 
     # ---- ensemble class passes of ALL classes over many tiles, in two halves like the single-model pass below
@@ -1665,48 +1676,19 @@ class InferencePipeline:
                     runs=runs, hw=dets_per_model[0][0].hw)
 
     def _ensemble_passes_finish(self, h: dict, class_thresholds, small_classes):
-        n, T, ld = h["n"], h["T"], h["ld"]
-        extra = [h["area"].to(torch.int32), h["bbox"], h["I"]]
-        try:
-            area_h, bbox_h, I_h = h["cset"].fetch(extra=extra)      # THE wait of the class passes
-        except _L.HipKernelError as e:
-            if "overflow" not in str(e):
-                raise
-            # a few large ragged masks (boundaries of thousands of points) overflowed the pool sized from the mask COUNT at
-            # launch time: the areas are on the device by now -- trace again with the area-sized pool MaskOps.trace defaults to
-            self.d2h_waits += 1
-            h["cset"] = self.ops.trace(h["packed"], max_contours=256, bbox=h["bbox"], total_area=int(h["area"].sum().item()))
-            area_h, bbox_h, I_h = h["cset"].fetch(extra=extra)
-        self.d2h_waits += 1
-        per0 = h["cset"].first_contour_perimeter()
-        area = np.ascontiguousarray(area_h, dtype=np.int64)
-        bbox = np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64)
-        I = np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32)
+        T, ld = h["T"], h["ld"]
+        # THE wait of the class passes
+        h["cset"], area, bbox, I = self._fetch_traced_tables(h["cset"], h["packed"], h["area"], h["bbox"], h["I"], ld)
+        not_artefact = _not_artefact(area, bbox, h["cset"].first_contour_perimeter())
         area_img = h["hw"][0] * h["hw"][1]
         scores, run_first = h["scores"], h["run_first"]
-        compact_bad = (per0 > 0) & ((4 * np.pi * area) / np.where(per0 > 0, per0, 1.0) ** 2 < 0.15)
         passes = []
         for ci, (cls, (_, iou_thr)) in enumerate(class_thresholds.items()):
-            min_size = max(3, int(area_img * 0.000005)) if cls in small_classes else max(25, int(area_img * 0.0001))
-            ok = (area >= min_size) & (bbox[:, 0] >= 0) & ~compact_bad
+            ok = (area >= universal_min_size(area_img, cls in small_classes)) & not_artefact
             k0_all = [np.nonzero(ok[r0:r1])[0] + r0 for r0, r1 in (h["runs"][(ci, t)] for t in range(T))]
-            items = np.ascontiguousarray(np.concatenate(k0_all), dtype=np.int32) if k0_all else np.zeros((0,), dtype=np.int32)
-            if len(items) == 0:
-                continue
-            tile_off = np.concatenate(([0], np.cumsum([len(k) for k in k0_all]))).astype(np.int32)
-            keep_out = np.zeros(len(items), dtype=np.int32)
-            keep_cnt = np.zeros(T, dtype=np.int32)
-            sc_items = np.ascontiguousarray(scores[items])
-            cl_items = np.full(len(items), cls, dtype=np.int32)
-            _L.check(self.ops.lib.demia_host_dedup_smart(I.ctypes.data, ld, run_first.ctypes.data, area.ctypes.data, bbox.ctypes.data,
-                                                         items.ctypes.data, sc_items.ctypes.data, cl_items.ctypes.data, tile_off.ctypes.data, T,
-                                                         float(iou_thr), keep_out.ctypes.data, keep_cnt.ctypes.data), "demia_host_dedup_smart")
-            res = []
-            for t in range(T):
-                keep = keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]]
-                gl = k0_all[t][keep]
-                res.append((gl.tolist(), scores[gl].tolist()))
-            passes.append((cls, h["packed"], res, _PassTables(area, bbox)))
+            kept = _smart_dedup_keep(self.ops.lib, I, ld, run_first, area, bbox, k0_all, scores, np.full(len(area), cls, dtype=np.int32), iou_thr)
+            if any(len(k0) for k0 in k0_all):
+                passes.append((cls, h["packed"], [(gl.tolist(), scores[gl].tolist()) for gl in kept], _PassTables(area, bbox)))
         return passes
 
     @staticmethod
@@ -1730,7 +1712,7 @@ class InferencePipeline:
             return None
         packed, bbox = self._gather_selected(dets, sels, pool_name=f"class{target_class}")
         is_small = target_class in small_classes
-        min_size = self.class_specific_settings.get(f"class_{target_class}", {}).get("min_size", 5 if is_small else 25)
+        min_size = _class_min_size(self.class_specific_settings, target_class, is_small)
         starts = np.concatenate(([0], np.cumsum(lens))).astype(np.int32)
         seg_np = np.repeat(np.arange(T, dtype=np.int32), lens)
         first_np = starts[seg_np]
@@ -1777,11 +1759,9 @@ class InferencePipeline:
     def process_tile_batch_hostloops(self, key: str, tiles: torch.Tensor, small_classes, class_thresholds: Dict[int, Tuple[float, float]],
                                      spatial_cfg: Optional[dict] = None, um_pix: float = 1.0, model_ids: Sequence[int] = (0,),
                                      dets: Optional[List[_Detections]] = None):
-        """The per-tile unit of work of the headline metric: one batched forward for B independent tiles, then per
-        tile the class loop (a6, a9, a11, a12), the cross-class dedup (a14, 0.7), the spatial constraints (a15) and the
-        contour measurements (a17, a18).  Every kernel is launched ONCE for all tiles (segment-aware where the
-        reference's loop carries state), so 256 CUs see hundreds of masks per launch instead of a few dozen.
-        Same results as :meth:`process_tile_batch_unbatched`.  Returns per tile ``(packed, scores, classes, records)``."""
+        """The host-loop version of :meth:`process_tile_batch` (the same stages, stated there) and its checker: one launch per
+        kernel for all tiles too, but a wait wherever a decision needs a table, the decisions as interpreted loops over a
+        ``DeviceMaskAlgebra``, and every rule spelt out here on its own.  Same results as :meth:`process_tile_batch_unbatched`."""
         ensemble = len(model_ids) > 1
         if ensemble:
             dets_per_model = [self._predict_batch(m, key, tiles) for m in model_ids]
@@ -1858,20 +1838,7 @@ class InferencePipeline:
                 gl, sc, cl = [gl[i] for i in kk], [sc[i] for i in kk], [cl[i] for i in kk]
             final_idx.append(gl)
             out[t] = (None, sc, cl, [])
-        flat = [i for gl in final_idx for i in gl]
-        if not flat:
-            return out
-        finalp = self.ops.gather_regions(allp, flat, alg.bbox[flat])
-        recs = cset.records(um_pix=um_pix, measure=True, select=flat)
-        pos = 0
-        # pixel counts / tight boxes of the final masks, per tile (what an instance table needs; already reduced)
-        self.last_batch_stats = [(alg.area[final_idx[t]], alg.bbox[final_idx[t]]) for t in range(T)]
-        for t in range(T):
-            n = len(final_idx[t])
-            if n:
-                out[t] = (finalp[pos:pos + n], out[t][1], out[t][2], recs[pos:pos + n])
-            pos += n
-        return out
+        return self._tile_batch_results(out, final_idx, allp, alg.area, alg.bbox, cset, um_pix, pooled=False)
 
     # ------------------------------------------------------------------ a8
     def calculate_average_mask_sizes(self, sample_images: Sequence[Tuple[str, torch.Tensor]]) -> Dict[int, float]:

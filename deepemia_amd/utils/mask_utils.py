@@ -170,6 +170,11 @@ def process_masks_device(ops, packed: torch.Tensor) -> torch.Tensor:
     return packed
 
 
+def universal_min_size(area_img: int, is_small_class: bool) -> int:
+    """The minimum mask size of ``postprocess_masks_universal`` (``inference.py:1763-1769``), from the IMAGE's pixel count."""
+    return max(3, int(area_img * 0.000005)) if is_small_class else max(25, int(area_img * 0.0001))
+
+
 def postprocess_masks_universal_device(ops, packed: torch.Tensor, image_hw, is_small_class: bool, min_crys_size=None,
                                        bbox: Optional[torch.Tensor] = None):
     """``postprocess_masks_universal`` (``inference.py:1739-1813``): returns (packed_kept, kept_indices);
@@ -177,9 +182,8 @@ def postprocess_masks_universal_device(ops, packed: torch.Tensor, image_hw, is_s
     n = int(packed.shape[0])
     if n == 0:
         return packed, []
-    area_img = image_hw[0] * image_hw[1]
     if min_crys_size is None:
-        min_crys_size = max(3, int(area_img * 0.000005)) if is_small_class else max(25, int(area_img * 0.0001))
+        min_crys_size = universal_min_size(image_hw[0] * image_hw[1], is_small_class)
     area, _, _ = ops.program_(packed, ["fill", "erode"] if is_small_class else ["fill", "erode", "dilate"], bbox)
     keep = (area >= min_crys_size).nonzero().flatten()
     return packed[keep].contiguous(), keep.cpu().tolist()

@@ -613,6 +613,102 @@ def test_native_greedy_keep_and_smart_dedup_equal_the_python_loops():
                 assert got == want, (trial, t, thr)
 
 
+def test_smart_dedup_keep_equals_the_python_loop_group_by_group():
+    """``_smart_dedup_keep`` -- the one host-side keep function of the smart-dedup stage (tile batches, ensemble passes, the
+    CLI's merges) -- against ``InferencePipeline._dedup_smart_order`` per group at 0.4 / 0.5 / 0.7: random class mixes and a
+    single class, tied scores, some groups empty and all groups empty (then the library is not called at all)."""
+    from deepemia_amd import _lib
+    from deepemia_amd.functions.inference import InferencePipeline as IP, _smart_dedup_keep
+
+    lib = _lib.load()
+    g = np.random.default_rng(23)
+    calls = 0
+    # (segment lengths, share of a segment's masks that are candidates, single class, scores rounded to one decimal: ties)
+    cases = [([12, 0, 30, 7], 0.8, False, False), ([25, 25, 25], 0.7, True, True), ([9, 14], 0.0, False, False),
+             ([0, 0, 0], 0.8, False, False), ([1, 39, 2, 0, 18], 1.0, False, True), ([33], 0.9, True, False),
+             ([20, 16, 0, 11], 0.6, False, True)]
+    for case, (seg_lens, share, one_class, ties) in enumerate(cases):
+        n = sum(seg_lens)
+        area, bbox, inter, first = _random_segments(g, seg_lens, quantised=ties)
+        ld = max(1, max(seg_lens))
+        mat = np.zeros((n, ld), dtype=np.int32)              # the device layout: row i, column j - first[i], j > i
+        for i in range(n):
+            for j in range(i + 1, n):
+                if first[j] == first[i]:
+                    mat[i, j - first[i]] = inter[i, j]
+        alg = _FakeAlgebra(inter, area)
+        starts = np.concatenate(([0], np.cumsum(seg_lens))).astype(np.int64)
+        scores = np.round(g.uniform(0.3, 1.0, n), 1 if ties else 6)
+        classes = np.zeros(n, dtype=np.int32) if one_class else g.integers(0, 3, n).astype(np.int32)
+        groups = [np.asarray([i for i in range(s0, s1) if g.random() < share], dtype=np.int64) for s0, s1 in zip(starts[:-1], starts[1:])]
+        if case == 0:
+            groups[2] = groups[2][:0]                        # an empty group between full ones
+        assert any(len(k0) == 0 for k0 in groups) or case in (1, 5)
+        for thr in (0.4, 0.5, 0.7):
+            got = _smart_dedup_keep(lib, mat, ld, first, area, bbox, groups, scores, classes, thr)
+            assert len(got) == len(groups)
+            for t, k0 in enumerate(groups):
+                bb = [(int(bbox[i, 0]), int(bbox[i, 2]), int(bbox[i, 1]), int(bbox[i, 3])) for i in k0]
+                keep = IP._dedup_smart_order(alg, k0.tolist(), scores[k0].tolist(), classes[k0].tolist(), bb, thr) if len(k0) else []
+                assert got[t].tolist() == [int(k0[i]) for i in keep], (case, t, thr)
+                calls += len(k0) > 0
+    assert calls > 30
+    # nothing to decide: empty arrays, and no library call (a lib that cannot be called proves it)
+    assert [k.tolist() for k in _smart_dedup_keep(None, mat, ld, first, area, bbox, [groups[0][:0]] * 3, scores, classes, 0.7)] == [[], [], []]
+    assert _smart_dedup_keep(None, mat, ld, first, area, bbox, [], scores, classes, 0.7) == []
+
+
+def test_not_artefact_mask_equals_the_scalar_compactness_rule():
+    """``_not_artefact`` (the vectorised emptiness + compactness rule of ``deduplicate_masks_smart``) against the scalar
+    statement of the rule -- ``per > 0 and 4 pi A / per^2 < 0.15`` drops, an empty box drops -- on integer areas with integer
+    perimeters either side of 0.15, perimeters that give EXACTLY 0.15 in float64 (kept: the rule is a strict ``<``), and
+    ``per0 == 0`` / ``-1`` (no perimeter, no contour: never dropped by compactness)."""
+    from deepemia_amd.functions.inference import _not_artefact
+
+    area, per, empty = [], [], []
+    exact = 0
+    for a in (1, 7, 100, 101, 2500, 4096, 99991, 1 << 20):
+        p_eq = float(np.sqrt(4 * np.pi * a / 0.15))
+        pf, pc = float(np.floor(p_eq)), float(np.ceil(p_eq))          # integer perimeters: just above / just below 0.15
+        assert (4 * np.pi * a) / pc ** 2 < 0.15 < (4 * np.pi * a) / pf ** 2
+        cands = [pf, pc, 0.0, -1.0, pf - 1.0, pc + 1.0, 3.0 * pc]
+        q = p_eq
+        for _ in range(8):
+            q = float(np.nextafter(q, 0.0))
+        for _ in range(17):                                           # the floats around the root: those that hit 0.15 exactly
+            if (4 * np.pi * a) / q ** 2 == 0.15:
+                cands.append(q)
+                exact += 1
+            q = float(np.nextafter(q, np.inf))
+        for p in cands:
+            for e in (False, True):
+                area.append(a)
+                per.append(p)
+                empty.append(e)
+    assert exact >= 3
+    area = np.asarray(area, dtype=np.int64)
+    per0 = np.asarray(per, dtype=np.float64)
+    bbox = np.tile(np.asarray([2, 3, 40, 50], dtype=np.int64), (len(area), 1))
+    bbox[np.asarray(empty)] = -1
+    got = _not_artefact(area, bbox, per0)
+    want = []
+    for i in range(len(area)):
+        if bbox[i, 0] < 0:
+            want.append(False)
+            continue
+        p = per0[i]
+        want.append(not (p > 0 and (4 * np.pi * int(area[i])) / (p ** 2) < 0.15))
+    assert got.dtype == bool and got.tolist() == want
+    # the sides themselves, from the definition: floor(P) keeps, ceil(P) drops, exactly 0.15 keeps, P <= 0 keeps
+    for i in range(len(area)):
+        if not empty[i] and per0[i] > 0:
+            v = (4 * np.pi * int(area[i])) / (per0[i] ** 2)
+            assert got[i] == (v >= 0.15), (int(area[i]), float(per0[i]))
+        elif not empty[i]:
+            assert got[i]
+    assert 0 < got.sum() < len(got)
+
+
 def test_native_csv_text_equals_csv_writer_byte_for_byte():
     """``measurement_csv_text`` (float columns through ``demia_host_repr_rows``) against ``csv.writer`` over
     ``measurement_rows`` -- what ``write_measurements`` writes: random measurement values of every magnitude (random bit
