@@ -1,0 +1,384 @@
+"""Crop-framed mask sets: instance masks kept in the GLOBAL frame as (room, cropped packed words) instead of full-frame
+planes ``[M, H, W/32]`` -- the representation of the instance tables (``demia_mask_crop_pack``, ``parallel.py``) with the HIP
+kernels that COMPUTE on it (``csrc/cropops.hip``): tile placement, gather, pair counts, and the chunked way back to planes
+for the kernels that want them (contours, measurements, histograms).
+
+All boxes are ``(y0, x0, y1, x1)``, inclusive, ``-1`` = empty -- the order every box of the C ABI has.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .maskset import MaskOps, PlanePool
+from .utils.mask_algebra import DeviceMaskAlgebra
+
+
+def room_lengths(room: np.ndarray) -> np.ndarray:
+    """Words per mask: room rows x word columns of the global word grid (0 for an empty room)."""
+    room = np.asarray(room).reshape(-1, 4)
+    lens = np.zeros(room.shape[0], dtype=np.int64)
+    ok = room[:, 0] >= 0
+    lens[ok] = (room[ok, 2].astype(np.int64) - room[ok, 0] + 1) * ((room[ok, 3] >> 5) - (room[ok, 1] >> 5) + 1)
+    return lens
+
+
+def room_offsets(room: np.ndarray) -> Tuple[np.ndarray, int]:
+    """(exclusive prefix sums of the rooms' word counts [M] i64, total words)."""
+    lens = room_lengths(room)
+    offs = np.zeros(len(lens), dtype=np.int64)
+    if len(lens):
+        np.cumsum(lens[:-1], out=offs[1:])
+    return offs, int(lens.sum())
+
+
+def nearest_index(n_dst: int, n_src: int) -> np.ndarray:
+    """Source index of every destination index under the placement kernels' nearest rule
+    (``min(floor(t * (1 / (n_dst / n_src))), n_src - 1)`` in float64, cv2's INTER_NEAREST); non-decreasing."""
+    t = np.arange(n_dst, dtype=np.float64)
+    return np.minimum(np.floor(t * (1.0 / (float(n_dst) / float(n_src)))).astype(np.int64), n_src - 1)
+
+
+def rooms_of_placed_tiles(boxes: np.ndarray, src_hw: Tuple[int, int], tile_hw: Tuple[int, int], x_off: Sequence[int], y_off: Sequence[int],
+                          hw: Tuple[int, int]) -> np.ndarray:
+    """Rooms ``[M, 4]`` i32 for ``demia_crop_place_tiles``: the boxes of tile-frame masks (``boxes``, tight or not, in the
+    ``src_hw`` frame) mapped through the placement's own index rule -- every destination row / column whose source index lies
+    in the box -- then pasted at the offsets and clipped to the frame ``hw``.  An upper bound of the placed masks' tight boxes
+    (the tight box itself when the resize is the identity and ``boxes`` are tight), from host tables only."""
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    n = boxes.shape[0]
+    out = np.full((n, 4), -1, dtype=np.int32)
+    if n == 0:
+        return out
+    (sh, sw), (th, tw), (H, W) = src_hw, tile_hw, hw
+    iy, ix = nearest_index(th, sh), nearest_index(tw, sw)
+    xo, yo = np.asarray(x_off, dtype=np.int64), np.asarray(y_off, dtype=np.int64)
+    ty0 = np.searchsorted(iy, boxes[:, 0], side="left") + yo
+    ty1 = np.searchsorted(iy, boxes[:, 2], side="right") - 1 + yo
+    tx0 = np.searchsorted(ix, boxes[:, 1], side="left") + xo
+    tx1 = np.searchsorted(ix, boxes[:, 3], side="right") - 1 + xo
+    gy0, gx0 = np.maximum(ty0, 0), np.maximum(tx0, 0)
+    gy1, gx1 = np.minimum(ty1, H - 1), np.minimum(tx1, W - 1)
+    ok = (boxes[:, 0] >= 0) & (gy0 <= gy1) & (gx0 <= gx1)
+    out[ok] = np.stack([gy0, gx0, gy1, gx1], axis=1)[ok].astype(np.int32)
+    return out
+
+
+class CropMaskSet:
+    """M masks over the frame ``hw = (H, W)``.
+
+    * ``room`` [M, 4] i32: the rectangle each mask's words are stored for, columns on the global 32-bit word grid
+      ``x0 >> 5 .. x1 >> 5`` exactly as ``demia_mask_crop_pack`` lays a box out (device tensor; ``room_h`` its host copy);
+    * ``offsets`` [M] i64: exclusive prefix sums of rows x word columns (``offsets_h`` on the host);
+    * ``payload`` i32 words; ``bbox`` [M, 4] i32 tight boxes and ``area`` [M] i32, on the device.
+
+    Invariant: payload bits outside the tight box, and beyond column ``W - 1``, are zero.  Two sets over one frame share
+    the word alignment: intersections need no bit shifts."""
+
+    def __init__(self, ops: MaskOps, hw: Tuple[int, int], room_h: np.ndarray, payload: torch.Tensor, bbox: torch.Tensor, area: torch.Tensor,
+                 room: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None):
+        self.ops, self.hw = ops, (int(hw[0]), int(hw[1]))
+        self.room_h = np.ascontiguousarray(room_h, dtype=np.int32).reshape(-1, 4)
+        self.offsets_h, self.words = room_offsets(self.room_h)
+        self.payload, self.bbox, self.area = payload, bbox, area
+        if room is None or offsets is None:
+            if len(self):
+                tab = ops.upload(np.concatenate([self.offsets_h.view(np.int32), self.room_h.reshape(-1)]))     # one copy for both
+                offsets, room = tab[:2 * len(self)].view(torch.int64), tab[2 * len(self):].view(-1, 4)
+            else:
+                offsets = torch.zeros((0,), dtype=torch.int64, device=ops.device)
+                room = torch.zeros((0, 4), dtype=torch.int32, device=ops.device)
+        self.room, self.offsets = room, offsets
+
+    def __len__(self) -> int:
+        return int(self.room_h.shape[0])
+
+    # what DeviceMaskAlgebra and the pipeline's size checks read of a plane tensor
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        return (len(self), self.hw[0], (self.hw[1] + 31) // 32)
+
+    @property
+    def device(self):
+        return self.ops.device
+
+    @staticmethod
+    def _payload(ops: MaskOps, words: int) -> torch.Tensor:
+        return torch.empty((max(words, 1),), dtype=torch.int32, device=ops.device)       # (never a null pointer)
+
+    @classmethod
+    def empty(cls, ops: MaskOps, hw) -> "CropMaskSet":
+        return cls(ops, hw, np.zeros((0, 4), dtype=np.int32), cls._payload(ops, 0), torch.zeros((0, 4), dtype=torch.int32, device=ops.device),
+                   torch.zeros((0,), dtype=torch.int32, device=ops.device))
+
+    # -- planes <-> crops -----------------------------------------------------------------------------------------
+    @classmethod
+    def from_planes(cls, ops: MaskOps, planes: torch.Tensor, W: int, bbox: Optional[np.ndarray] = None, area=None,
+                    index: Optional[Sequence[int]] = None) -> "CropMaskSet":
+        """Planes ``[n, H, ceil(W / 32)]`` that are zero outside their tight boxes -> a set whose rooms ARE the tight boxes
+        (``demia_mask_crop_pack``).  ``bbox`` / ``area``: the tight boxes and pixel counts of all n planes when the caller has
+        them on the host (a class pass does) -- else one reduction and one device-to-host wait.  ``index``: only these planes,
+        in this order (no plane is copied: the others are packed as empty and left out by one gather)."""
+        n, H = int(planes.shape[0]), int(planes.shape[1])
+        assert planes.dtype == torch.int32 and planes.is_contiguous() and int(planes.shape[2]) == (W + 31) // 32
+        if n == 0:
+            return cls.empty(ops, (H, W))
+        if bbox is None or area is None:
+            ops.set_frame_width(W)
+            a, b = ops.area_bbox(planes)
+            area, bbox = a.cpu().numpy(), b.cpu().numpy()
+        room_h = np.ascontiguousarray(bbox, dtype=np.int32).reshape(n, 4).copy()
+        area_h = np.ascontiguousarray(area, dtype=np.int32).reshape(n)
+        if index is not None:
+            sel = np.asarray(index, dtype=np.int64)
+            drop = np.ones(n, dtype=bool)
+            drop[sel] = False
+            room_h[drop] = -1
+        tab = ops.upload(np.concatenate([room_h.reshape(-1), area_h]))
+        bbox_d, area_d = tab[:4 * n].view(n, 4), tab[4 * n:]
+        out = cls(ops, (H, W), room_h, None, bbox_d, area_d)
+        out.payload = cls._payload(ops, out.words)
+        if out.words:
+            _lib.check(ops.lib.demia_mask_crop_pack(_lib.ptr(planes), _lib.ptr(out.room), _lib.ptr(out.offsets), n, H, W, _lib.ptr(out.payload),
+                                                    ops._stream()), "demia_mask_crop_pack")
+        return out if index is None else out.select(index)
+
+    def to_planes(self, first: int = 0, n: Optional[int] = None) -> torch.Tensor:
+        """Fresh zeroed planes ``[n, H, W/32]`` of the masks ``[first, first + n)`` (``demia_mask_crop_unpack``)."""
+        n = len(self) - first if n is None else int(n)
+        H, W = self.hw
+        planes = torch.zeros((n, H, (W + 31) // 32), dtype=torch.int32, device=self.ops.device)
+        if n and self.words:
+            _lib.check(self.ops.lib.demia_mask_crop_unpack(_lib.ptr(self.payload), _lib.ptr(self.room[first:first + n]),
+                                                           _lib.ptr(self.offsets[first:first + n]), n, H, W, _lib.ptr(planes),
+                                                           self.ops._stream()), "demia_mask_crop_unpack")
+        return planes
+
+    def unpack_pooled(self, pool: PlanePool, first: int, n: int, grow: int = 0) -> torch.Tensor:
+        """Masks ``[first, first + n)`` into slots ``0 .. n - 1`` of ``pool`` (``demia_crop_unpack_pooled``): the union of each
+        slot's previous box and the new one is written.  Returns the view of those slots, valid until the pool is used again."""
+        H, W = self.hw
+        assert 0 <= first and first + n <= len(self) and pool.fits(n, H, (W + 31) // 32)
+        _lib.check(self.ops.lib.demia_crop_unpack_pooled(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                         int(first), int(n), H, W, _lib.ptr(pool.planes), _lib.ptr(pool.prev), int(grow),
+                                                         self.ops._stream()), "demia_crop_unpack_pooled")
+        return pool.planes[:n]
+
+    # -- placement ------------------------------------------------------------------------------------------------
+    @classmethod
+    def place_tiles(cls, ops: MaskOps, src: torch.Tensor, room_h: np.ndarray, x_off: Sequence[int], y_off: Sequence[int], tile_h: int,
+                    tile_w: int, H: int, W: int, src_w: Optional[int] = None) -> "CropMaskSet":
+        """``MaskOps.place_tiles`` into rooms (``demia_crop_place_tiles``): ``room_h`` from :func:`rooms_of_placed_tiles`."""
+        T, sh, swpr = (int(v) for v in src.shape)
+        assert src.dtype == torch.int32 and src.is_contiguous() and len(x_off) == T and len(y_off) == T
+        bbox = torch.empty((T, 4), dtype=torch.int32, device=ops.device)
+        area = torch.empty((T,), dtype=torch.int32, device=ops.device)
+        out = cls(ops, (H, W), room_h, None, bbox, area)
+        assert len(out) == T
+        out.payload = cls._payload(ops, out.words)
+        if T:
+            off = ops.upload(np.stack([np.asarray(x_off, dtype=np.int32), np.asarray(y_off, dtype=np.int32)]))
+            _lib.check(ops.lib.demia_crop_place_tiles(_lib.ptr(src), _lib.ptr(off[0]), _lib.ptr(off[1]), T, sh, swpr * 32 if src_w is None else int(src_w),
+                                                      int(tile_h), int(tile_w), H, W, _lib.ptr(out.room), _lib.ptr(out.offsets), _lib.ptr(out.payload),
+                                                      _lib.ptr(area), _lib.ptr(bbox), ops._stream()), "demia_crop_place_tiles")
+        return out
+
+    # -- select / cat ---------------------------------------------------------------------------------------------
+    def select(self, index: Sequence[int]) -> "CropMaskSet":
+        """``self[index]`` (any order, repeats allowed) without planes: one ``demia_crop_gather``."""
+        idx = np.ascontiguousarray(np.asarray(index, dtype=np.int64).reshape(-1))
+        if len(idx) == 0:
+            return CropMaskSet.empty(self.ops, self.hw)
+        idx_d = self.ops.upload(idx)
+        out = CropMaskSet(self.ops, self.hw, self.room_h[idx], None, self.bbox.index_select(0, idx_d), self.area.index_select(0, idx_d))
+        out.payload = self._payload(self.ops, out.words)
+        _lib.check(self.ops.lib.demia_crop_gather(_lib.ptr(self.payload), _lib.ptr(self.offsets), _lib.ptr(idx_d), _lib.ptr(out.room),
+                                                  _lib.ptr(out.offsets), len(idx), _lib.ptr(out.payload), self.ops._stream()), "demia_crop_gather")
+        return out
+
+    @staticmethod
+    def cat(sets: Sequence["CropMaskSet"]) -> "CropMaskSet":
+        """The masks of ``sets`` (same frame) back to back: every set's words move with one ``demia_crop_gather`` into the
+        result's payload."""
+        sets = [s for s in sets if len(s)]
+        assert sets and all(s.hw == sets[0].hw for s in sets)
+        if len(sets) == 1:
+            return sets[0]
+        ops = sets[0].ops
+        out = CropMaskSet(ops, sets[0].hw, np.concatenate([s.room_h for s in sets]), None, torch.cat([s.bbox for s in sets]),
+                          torch.cat([s.area for s in sets]))
+        out.payload = CropMaskSet._payload(ops, out.words)
+        pos = 0
+        for s in sets:
+            k = len(s)
+            idx = torch.arange(k, dtype=torch.int64, device=ops.device)
+            _lib.check(ops.lib.demia_crop_gather(_lib.ptr(s.payload), _lib.ptr(s.offsets), _lib.ptr(idx), _lib.ptr(out.room[pos:pos + k]),
+                                                 _lib.ptr(out.offsets[pos:pos + k]), k, _lib.ptr(out.payload), ops._stream()), "demia_crop_gather")
+            pos += k
+        return out
+
+    def host_crops(self):
+        """Per mask its room's crop on the host: ``(y0, x0, bool[h, w])`` or ``None`` for an empty room (what ``mask_crops``
+        returns of planes, with the room in place of the tight box: the same pixels are set)."""
+        pay = self.payload[:self.words].cpu().numpy().view(np.uint32)
+        out = []
+        for (y0, x0, y1, x1), off in zip(self.room_h.tolist(), self.offsets_h.tolist()):
+            if y0 < 0:
+                out.append(None)
+                continue
+            rows, c0, cols = y1 - y0 + 1, x0 >> 5, (x1 >> 5) - (x0 >> 5) + 1
+            words = np.ascontiguousarray(pay[off: off + rows * cols].reshape(rows, cols))
+            bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")
+            out.append((y0, x0, bits[:, x0 - 32 * c0: x1 - 32 * c0 + 1].astype(bool)))
+        return out
+
+    # -- pair counts ----------------------------------------------------------------------------------------------
+    def pair_matrix(self, first: np.ndarray, count: np.ndarray, label: Optional[np.ndarray] = None, ld: Optional[int] = None) -> torch.Tensor:
+        """``MaskOps.pair_matrix`` on the cropped words (``demia_crop_pair_matrix``): same segments, same ``[M, ld]`` layout."""
+        M, ops = len(self), self.ops
+        if ld is None:
+            ld = max(1, int(np.max(count)) if M else 1)
+        out = torch.zeros((M, ld), dtype=torch.int32, device=ops.device)
+        if M == 0:
+            return out
+        tab = np.stack([np.asarray(first, dtype=np.int32), np.asarray(count, dtype=np.int32),
+                        np.asarray(label if label is not None else np.zeros(M), dtype=np.int32)])
+        tt = ops.upload(tab)
+        _lib.check(ops.lib.demia_crop_pair_matrix(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                  _lib.ptr(tt[0]), _lib.ptr(tt[1]), _lib.ptr(tt[2]) if label is not None else 0, _lib.ptr(out), M, ld,
+                                                  ops._stream()), "demia_crop_pair_matrix")
+        return out
+
+    def pair_intersections(self, other: "CropMaskSet", pi: np.ndarray, pj: np.ndarray) -> np.ndarray:
+        """``|self[pi[p]] & other[pj[p]]|`` per listed pair (``demia_crop_pair_intersections``); one device-to-host wait."""
+        P, ops = len(pi), self.ops
+        if P == 0:
+            return np.zeros((0,), dtype=np.int64)
+        assert self.hw == other.hw
+        tp = ops.upload(np.stack([np.asarray(pi, dtype=np.int32), np.asarray(pj, dtype=np.int32)]))
+        out = torch.empty((P,), dtype=torch.int32, device=ops.device)
+        _lib.check(ops.lib.demia_crop_pair_intersections(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                         _lib.ptr(other.payload), _lib.ptr(other.room), _lib.ptr(other.offsets), _lib.ptr(other.bbox),
+                                                         _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(out), P, ops._stream()),
+                   "demia_crop_pair_intersections")
+        return out.cpu().numpy().astype(np.int64)
+
+
+class CropMaskAlgebra(DeviceMaskAlgebra):
+    """:class:`DeviceMaskAlgebra` over a :class:`CropMaskSet`: boxes and pixel counts are the set's own (``area`` / ``bbox``: their
+    host copies when the caller has them -- nothing is uploaded or fetched then), and every count the base class asks of the
+    device goes through :meth:`intersections`, i.e. ``demia_crop_pair_intersections`` -- the one place of the base class that
+    reads ``self.packed`` (``inter_row``, ``prefetch_overlapping_pairs`` and ``inter`` all end there)."""
+
+    def __init__(self, cset: CropMaskSet, area=None, bbox=None, blocks=None):
+        super().__init__(cset.ops, cset, area=cset.area if area is None else area, bbox=cset.bbox if bbox is None else bbox, blocks=blocks,
+                         bbox_dev=cset.bbox)
+
+    def intersections(self, pi, pj) -> np.ndarray:
+        pi = np.asarray(pi, dtype=np.int64)
+        pj = np.asarray(pj, dtype=np.int64)
+        out = self.packed.pair_intersections(self.packed, pi, pj)
+        for a, b, v in zip(pi.tolist(), pj.tolist(), out.tolist()):
+            self._cache[(a, b)] = v
+            self._cache[(b, a)] = v
+        self.I[pi, pj] = out
+        self.I[pj, pi] = out
+        self.known[pi, pj] = True
+        self.known[pj, pi] = True
+        return out
+
+
+class CropPlanes:
+    """The full-frame planes a crop-framed image ever holds: a :class:`PlanePool` of ``chunk`` planes the masks are unpacked
+    into, ``chunk`` masks at a time, plus as many scratch planes for the kernels that want them (the contour trace's regions
+    that do not fit in LDS).  ``cap`` = all of them: 32 planes -- 4 MiB of a 1024^2 frame, 256 MiB of an 8192^2 frame."""
+
+    CHUNK = 16
+
+    def __init__(self, ops: MaskOps, hw: Tuple[int, int], chunk: int = CHUNK):
+        H, W = int(hw[0]), int(hw[1])
+        wpr = (W + 31) // 32
+        self.hw, self.chunk, self.cap = (H, W), int(chunk), 2 * int(chunk)
+        self.pool = PlanePool(ops.device, H, wpr, self.chunk)
+        self.scratch = torch.empty((self.chunk, H, wpr), dtype=torch.int32, device=ops.device)
+
+
+def crop_planes(ops: MaskOps, hw: Tuple[int, int]) -> CropPlanes:
+    """The :class:`CropPlanes` of this ``MaskOps`` (one per host thread) for the frame ``hw``, reallocated when the frame changes."""
+    cp = ops.__dict__.get("_crop_planes")
+    if cp is None or cp.hw != (int(hw[0]), int(hw[1])):
+        ops.__dict__.pop("_crop_planes", None)
+        cp = ops.__dict__["_crop_planes"] = CropPlanes(ops, hw)
+    return cp
+
+
+def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256, um_pix: Optional[float] = None,
+                 total_area: Optional[np.ndarray] = None):
+    """The contour trace of every mask of ``cset`` (``MaskOps.trace``, unchanged), ``planes.chunk`` masks at a time through the
+    pool: yields (first, n, ContourSet) per chunk, each with its unpack + trace (+ the measurements of its first contours when
+    ``um_pix`` is given) enqueued and NOT waited for, and with the NEXT chunk already enqueued behind it -- the pool is reused
+    in stream order, every chunk's contour tables are its own -- so the consumer's fetch of one chunk overlaps the device's
+    work on the next, and the contour tables of two chunks at most are alive.  ``total_area``: the masks' pixel counts when
+    they are on the host -- sizes every chunk's point pool as ``MaskOps.trace`` does (else from the mask count; a caller that
+    meets an overflow traces that chunk again)."""
+    ops = cset.ops
+    ops.set_frame_width(cset.hw[1])
+    pending = None
+    for f in range(0, len(cset), planes.chunk):
+        n = min(planes.chunk, len(cset) - f)
+        pl = cset.unpack_pooled(planes.pool, f, n)
+        if total_area is not None:
+            mp = int(min(max(4 * int(np.sum(total_area[f:f + n])) // 8 + 4096 * n, 1 << 16), 1 << 26))
+        else:
+            mp = int(min(4096 * n + (1 << 16), 1 << 26))
+        cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], max_points=mp, scratch=planes.scratch[:n])
+        if um_pix is not None:
+            cs.launch_measure(um_pix, slots=4)
+        if pending is not None:
+            yield pending
+        pending = (f, n, cs)
+    if pending is not None:
+        yield pending
+
+
+def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, total_area: Optional[np.ndarray] = None,
+                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256):
+    """``MaskOps.contours`` (trace + the 12 measurements, records in OpenCV's order) for a crop-framed set, chunk by chunk
+    through the plane pool.  ``extra``: int32 device tensors that come to the host with the FIRST chunk's tables.
+    ``total_area``: the masks' pixel counts on the host (sizes the point pools); without them the pools are sized from the mask
+    count, and a chunk whose pool overflows is unpacked and traced again with the pool sized from its own (device) areas.
+    Returns (records per mask, host arrays of ``extra`` or None); one device-to-host wait per chunk."""
+    ops = cset.ops
+    area = None if total_area is None else np.asarray(total_area).reshape(-1)
+    recs, got = [], None
+    for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area)):
+        ex = extra if k == 0 else None
+        try:
+            g = cs.fetch(extra=ex, with_points=True)
+        except _lib.HipKernelError as e:
+            if "overflow" not in str(e):
+                raise
+            pl = cset.unpack_pooled(planes.pool, f, n)      # (the chunk behind this one has run: the pool is free again)
+            cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], total_area=int(cset.area[f:f + n].sum().item()),
+                           scratch=planes.scratch[:n])
+            cs.launch_measure(um_pix, slots=4)
+            g = cs.fetch(extra=ex, with_points=True)
+        if k == 0:
+            got = list(g)
+        recs.extend(cs.records(um_pix=um_pix, measure=True))
+    if extra is not None and got is None:
+        got = [e.cpu().numpy() for e in extra]
+    return recs, (got if extra is not None else None)
+
+
+def crop_gray_histogram(cset: CropMaskSet, planes: CropPlanes, image: torch.Tensor) -> np.ndarray:
+    """``MaskOps.gray_histogram`` for a crop-framed set, chunk by chunk through the plane pool: [M, 256] gray-level counts."""
+    out = [np.zeros((0, 256), dtype=np.int64)]
+    cset.ops.set_frame_width(cset.hw[1])
+    for f in range(0, len(cset), planes.chunk):
+        n = min(planes.chunk, len(cset) - f)
+        out.append(cset.ops.gray_histogram(cset.unpack_pooled(planes.pool, f, n), image, bbox=cset.bbox[f:f + n]))
+    return np.concatenate(out)

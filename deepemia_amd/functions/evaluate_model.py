@@ -269,6 +269,11 @@ class PipelineRunner:
         from . import inference as INF
 
         self.INF = INF
+        self.st = INF.PipelineSettings(dataset_name)
+        if self.st.mask_frame != "full":
+            # (the scoring below -- cross matrix, COCO RLE -- reads full-frame planes)
+            raise ValueError(f"inference_settings.mask_frame: {self.st.mask_frame} is not supported by the evaluate task's pipeline mode "
+                             "(its scoring runs on full-frame planes only); use mask_frame: full for this dataset")
         predictors, models = [], []
         for r in ((50, 101) if str(rcnn) == "combo" else (int(rcnn),)):
             paths = get_trained_model_paths(split_dir, r)
@@ -281,7 +286,6 @@ class PipelineRunner:
         if not predictors:
             raise FileNotFoundError(f"No trained models found for dataset '{dataset_name}' (rcnn {rcnn}) under {split_dir}")
         system_logger.info(f"Loaded models: {', '.join(f'R{r}' for r in models)}")
-        self.st = INF.PipelineSettings(dataset_name)
         self.pipe = INF.InferencePipeline(predictors, dataset_name, self.st.inf, self.st.global_config)
         if self.pipe.world != 1:
             raise RuntimeError("the evaluate task runs in one process")

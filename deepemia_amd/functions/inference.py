@@ -19,6 +19,7 @@ from __future__ import annotations
 import csv
 import math
 import os
+import threading
 import time
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -30,6 +31,7 @@ from ..data.datasets import DatasetCatalog, MetadataCatalog, read_dataset_info, 
 from ..data.models import choose_and_use_model, get_trained_model_paths
 from .. import _lib as _L
 from .. import parallel
+from ..cropset import CropMaskAlgebra, CropMaskSet, CropPlanes, crop_contours, crop_gray_histogram, crop_planes, rooms_of_placed_tiles, trace_chunks
 from ..maskset import MaskOps
 from ..utils.config import get_config
 from ..utils.logger_utils import log_memory_usage, system_logger
@@ -286,6 +288,24 @@ def _smart_dedup_keep(lib, I: np.ndarray, ld: int, run_first: np.ndarray, area: 
     return [np.asarray(groups[t])[keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]]] for t in range(T)]
 
 
+MASK_FRAMES = ("full", "crop")
+
+
+def mask_frame_setting(inf_settings: dict) -> str:
+    """``inference_settings.mask_frame`` (per dataset): ``full`` (the default) keeps the masks of the stages after the tile ->
+    global mapping as full-frame planes, ``crop`` as a :class:`CropMaskSet`.  An unknown value is a configuration error, and so
+    is ``crop`` with the modes that stay on ``full``: ``merge_mode: soft_nms`` and ``multiscale_settings.enabled``."""
+    frame = str((inf_settings or {}).get("mask_frame", "full"))
+    if frame not in MASK_FRAMES:
+        raise ValueError(f"inference_settings.mask_frame must be 'full' or 'crop', got {frame!r}")
+    if frame == "crop":
+        if str(inf_settings.get("merge_mode", "smart")) == "soft_nms":
+            raise ValueError("inference_settings.mask_frame: crop cannot be combined with merge_mode: soft_nms (soft-NMS runs on full-frame planes only)")
+        if bool((inf_settings.get("multiscale_settings", {}) or {}).get("enabled", False)):
+            raise ValueError("inference_settings.mask_frame: crop cannot be combined with multiscale_settings.enabled (multi-scale runs on full-frame planes only)")
+    return frame
+
+
 class EmptyEnsembleTypeError(ValueError):
     """Reference behaviour N4: ``np.array([]) + [masks...]`` raises and the image is skipped."""
 
@@ -323,6 +343,10 @@ class InferencePipeline:
         self.soft_nms_score_threshold = float(snm.get("score_threshold", 0.001))
         if self.merge_mode not in ("smart", "soft_nms"):
             raise ValueError(f"inference_settings.merge_mode must be 'smart' or 'soft_nms', got {self.merge_mode!r}")
+        # opt-in: the stages after the tile -> global mapping on crop-framed mask sets instead of full-frame planes (same decisions,
+        # same files)
+        self.mask_frame = mask_frame_setting(inf_settings)
+        self.last_image_stats = None             # {"mask_frame", "full_frame_planes_peak", "plane_pool_capacity"} of the image finished last
         if self.merge_mode == "soft_nms":
             system_logger.warning("merge_mode: soft_nms -- NON-PARITY mode: the reference has no soft-NMS (hard greedy dedup only)")
         # f4, flagged NON-parity: `multiscale_settings.enabled: true` makes the classes whose class_specific_settings carry
@@ -351,6 +375,26 @@ class InferencePipeline:
         self.rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.exchange = parallel.ExchangeState()     # this job's agreed capacities: every rank builds its pipeline at the same point
+        if self.mask_frame == "crop" and self.world > 1:
+            raise ValueError("inference_settings.mask_frame: crop runs in one process only (WORLD_SIZE = "
+                             f"{self.world}): the gathered instance tables are unpacked to full-frame planes; use mask_frame: full")
+
+    @property
+    def crop(self) -> bool:
+        return self.mask_frame == "crop"
+
+    def _note_planes(self, n: int) -> None:
+        """``n`` full-frame planes of the stages after the tile -> global mapping are alive at this point (the class passes' own
+        planes -- the network's output and its in-place copy, the same in both frames -- are not counted)."""
+        self._tls.planes_peak = max(getattr(self._tls, "planes_peak", 0), int(n))      # (per host thread: a thread walks one image at a time)
+
+    def begin_image_stats(self) -> None:
+        self._tls.planes_peak = 0
+
+    def end_image_stats(self, hw) -> dict:
+        cap = 2 * CropPlanes.CHUNK if self.crop else None
+        self.last_image_stats = {"mask_frame": self.mask_frame, "full_frame_planes_peak": int(getattr(self._tls, "planes_peak", 0)), "plane_pool_capacity": cap}
+        return self.last_image_stats
 
     @property
     def ops(self) -> MaskOps:
@@ -601,6 +645,9 @@ class InferencePipeline:
             if all_pairs:
                 run_first[s0:s1] = s0
                 run_count[s0:s1] = s1 - s0
+        crop = isinstance(packed, CropMaskSet)
+        if general and crop:
+            raise ValueError("mask_frame: crop runs the smart dedup over classes in contiguous runs only")
         if general:
             out = []
             for s0, s1 in segments:
@@ -615,20 +662,31 @@ class InferencePipeline:
                     out.append((m, s_, c_, (a_.cpu().numpy().astype(np.int64), b_.cpu().numpy().astype(np.int64), None)))
             return out
         ops = self.ops
-        packed = packed.contiguous()
-        area_d, bbox_d = ops.area_bbox(packed)
-        cset = ops.trace(packed, max_contours=256, bbox=bbox_d, max_points=int(min(4096 * n + (1 << 16), 1 << 26)))
         ld = max(1, int(run_count.max()))
-        I = ops.pair_matrix(packed, bbox_d, run_first, np.maximum(run_count, 1), None, ld)
-        cset, area, bbox, I_c = self._fetch_traced_tables(cset, packed, area_d, bbox_d, I, ld)
-        ok = _not_artefact(area, bbox, cset.first_contour_perimeter())
+        if crop:
+            # the same stage on cropped words: pixel counts and tight boxes are the set's own, the pair matrix comes from
+            # demia_crop_pair_matrix, and the (unchanged) contour trace reaches the masks through the plane pool, a chunk at a time
+            I = packed.pair_matrix(run_first, np.maximum(run_count, 1), None, ld)
+            per0, area, bbox, I_c = self._fetch_traced_tables_crop(packed, I, ld)
+        else:
+            packed = packed.contiguous()
+            area_d, bbox_d = ops.area_bbox(packed)
+            cset = ops.trace(packed, max_contours=256, bbox=bbox_d, max_points=int(min(4096 * n + (1 << 16), 1 << 26)))
+            I = ops.pair_matrix(packed, bbox_d, run_first, np.maximum(run_count, 1), None, ld)
+            cset, area, bbox, I_c = self._fetch_traced_tables(cset, packed, area_d, bbox_d, I, ld)
+            per0 = cset.first_contour_perimeter()
+        ok = _not_artefact(area, bbox, per0)
         gls = _smart_dedup_keep(ops.lib, I_c, ld, run_first, area, bbox, [np.nonzero(ok[s0:s1])[0] + s0 for s0, s1 in segments],
                                 np.asarray(scores, dtype=np.float64), cl, iou_threshold)
         flat = np.concatenate(gls) if gls else np.zeros(0, dtype=np.int64)
         if len(flat) == 0:
             return [empty for _ in segments]
-        sel = ops.upload(flat.astype(np.int64))
-        kept_all = ops.gather_regions(packed, sel, bbox_d.index_select(0, sel))
+        if crop:
+            kept_all = packed.select(flat)
+        else:
+            sel = ops.upload(flat.astype(np.int64))
+            kept_all = ops.gather_regions(packed, sel, bbox_d.index_select(0, sel))
+            self._note_planes(2 * n + len(flat))     # the candidates, the trace's scratch planes, the survivors
         out, pos = [], 0
         for gl in gls:
             k = len(gl)
@@ -642,7 +700,8 @@ class InferencePipeline:
                     inter = I_c[lo, np.minimum(hi - s0, ld - 1)].astype(np.int64)      # row i, column j - first[i] holds |i & j| for j > i
                     d_ = np.arange(k)
                     inter[d_, d_] = area[gl]
-                out.append((kept_all[pos:pos + k], [scores[i] for i in gl], [classes[i] for i in gl], (area[gl], bbox[gl], inter)))
+                kept = kept_all.select(np.arange(pos, pos + k)) if crop else kept_all[pos:pos + k]
+                out.append((kept, [scores[i] for i in gl], [classes[i] for i in gl], (area[gl], bbox[gl], inter)))
             pos += k
         return out
 
@@ -664,6 +723,36 @@ class InferencePipeline:
         self.d2h_waits += 1
         n = int(packed.shape[0])
         return (cset, np.ascontiguousarray(area_h, dtype=np.int64), np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64),
+                np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
+
+    def _fetch_traced_tables_crop(self, cs: CropMaskSet, I: torch.Tensor, ld: int):
+        """:meth:`_fetch_traced_tables` for a crop-framed set: the chunks go through the plane pool one behind the other
+        (``trace_chunks``: a chunk is fetched while the next one runs); the first chunk's fetch brings pixel counts, tight boxes
+        and the pair matrix along, every further chunk costs one more wait.  A chunk whose point pool
+        overflows is unpacked and traced again with the area-sized pool.  Returns (first-contour perimeters f64 [n], area i64
+        [n], bbox i64 [n, 4], I i32 [n, ld])."""
+        n = len(cs)
+        planes = crop_planes(self.ops, cs.hw)
+        self._note_planes(planes.cap)
+        per0, tabs = [], None
+        for k, (f, m, cset) in enumerate(trace_chunks(cs, planes)):
+            extra = [cs.area, cs.bbox, I] if k == 0 else None
+            try:
+                got = cset.fetch(extra=extra)
+            except _L.HipKernelError as e:
+                if "overflow" not in str(e):
+                    raise
+                self.d2h_waits += 1
+                pl = cs.unpack_pooled(planes.pool, f, m)
+                cset = self.ops.trace(pl, max_contours=256, bbox=cs.bbox[f:f + m], total_area=int(cs.area[f:f + m].sum().item()),
+                                      scratch=planes.scratch[:m])
+                got = cset.fetch(extra=extra)
+            self.d2h_waits += 1
+            if k == 0:
+                tabs = got
+            per0.append(cset.first_contour_perimeter())
+        area_h, bbox_h, I_h = tabs
+        return (np.concatenate(per0), np.ascontiguousarray(area_h, dtype=np.int64), np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64),
                 np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
 
     def deduplicate_masks_smart_hostloops(self, packed: Optional[torch.Tensor], scores: Sequence[float], classes: Sequence[int],
@@ -807,6 +896,8 @@ class InferencePipeline:
             kept, sc = res[0]
             if big is None or not kept:
                 return None, [], []
+            if self.crop:
+                return CropMaskSet.from_planes(self.ops, big, w, bbox=tabs.bbox, area=tabs.area, index=kept), list(sc), [target_class] * len(kept)
             return self.ops.gather_regions(big, kept, tabs.bbox[kept]), list(sc), [target_class] * len(kept)
 
         rank, world = self.rank, self.world
@@ -823,6 +914,11 @@ class InferencePipeline:
             else:
                 full = [self._predict_batch(m, image_key + "|full", image_dev[None])[0] for m in model_ids]
                 full_masks, full_scores, full_classes = class_pass(full)
+                if self.crop and torch.is_tensor(full_masks):      # (the ensemble pass hands planes back)
+                    self.ops.set_frame_width(w)
+                    self._note_planes(int(full_masks.shape[0]))
+                    full_masks = CropMaskSet.from_planes(self.ops, full_masks.contiguous(), w)
+                    self.d2h_waits += 1
         tile_masks, tile_scores, tile_classes, tile_units = [], [], [], []
         if mine:
             tkey = self._tiles_key(image_key, tile_size, overlap_ratio, upscale_factor)
@@ -884,8 +980,20 @@ class InferencePipeline:
                                                     or bb[i, 1] < edge or bb[i, 3] > tile_size - edge)]
             if keep:
                 sel = torch.tensor(keep, dtype=torch.long, device=self.dev)
-                glob = self.ops.place_tiles(small[sel].contiguous(), [xo[i] for i in keep], [yo[i] for i in keep],
-                                            tile_size, tile_size, h, w, src_w=tile_size)
+                if self.crop:
+                    # the paste writes each mask's ROOM, not an h x w plane: the room is the mask's tile-scale box moved to
+                    # its tile's offset and clipped to the frame (host tables only)
+                    if bb is None:
+                        _, bb = self.ops.area_bbox(small)
+                        bb = bb.cpu().numpy()
+                        self.d2h_waits += 1
+                    kx, ky = [xo[i] for i in keep], [yo[i] for i in keep]
+                    rooms = rooms_of_placed_tiles(np.asarray(bb)[keep], (tile_size, tile_size), (tile_size, tile_size), kx, ky, (h, w))
+                    glob = CropMaskSet.place_tiles(self.ops, small[sel].contiguous(), rooms, kx, ky, tile_size, tile_size, h, w, src_w=tile_size)
+                else:
+                    glob = self.ops.place_tiles(small[sel].contiguous(), [xo[i] for i in keep], [yo[i] for i in keep],
+                                                tile_size, tile_size, h, w, src_w=tile_size)
+                    self._note_planes(len(keep))
                 tile_masks.append(glob)
                 tile_scores.extend(sc_all[i] for i in keep)
                 tile_classes.extend([target_class] * len(keep))
@@ -1012,7 +1120,7 @@ class InferencePipeline:
         parts = ([full_masks] if full_masks is not None and full_masks.shape[0] else []) + list(tile_masks)
         if not parts:
             return None, [], []
-        packed = torch.cat(parts, dim=0)
+        packed = CropMaskSet.cat(parts) if self.crop else torch.cat(parts, dim=0)
         if self.merge_mode == "soft_nms":        # flagged non-parity mode (f4)
             return self.soft_nms_merge(packed, list(full_scores) + list(tile_scores), list(full_classes) + list(tile_classes),
                                        self.soft_nms_sigma, self.soft_nms_score_threshold)
@@ -1122,7 +1230,10 @@ class InferencePipeline:
                 kept, sc = res[0]
                 if kept:
                     self.ops.set_frame_width(w)
-                    parts.append(self.ops.gather_regions(big, kept, tabs.bbox[kept]))
+                    if self.crop:       # the full-image pass's masks enter through from_planes: no plane is copied
+                        parts.append(CropMaskSet.from_planes(self.ops, big, w, bbox=tabs.bbox, area=tabs.area, index=kept))
+                    else:
+                        parts.append(self.ops.gather_regions(big, kept, tabs.bbox[kept]))
                     scores += list(sc)
                     classes += [cls] * len(kept)
             if ht is not None:
@@ -1138,7 +1249,7 @@ class InferencePipeline:
         if not parts:
             return out
         # ---- phase 2: the per-class 0.4 merges (inference.py:2452-2472) as the segments of one call, one wait --------------------
-        merged = self.deduplicate_masks_smart_segments(torch.cat(parts, dim=0), scores, classes, segments, 0.4)
+        merged = self.deduplicate_masks_smart_segments(CropMaskSet.cat(parts) if self.crop else torch.cat(parts, dim=0), scores, classes, segments, 0.4)
         for (cls, _, _), m in zip(handles, merged):
             out[cls] = m[:3]
         return out
@@ -1877,6 +1988,7 @@ class PipelineSettings:
         self.ensemble_enabled = ens.get("enabled", gens.get("enabled", True))
         self.ensemble_small_only = ens.get("small_classes_only", gens.get("small_classes_only", True))
         self.classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
+        self.mask_frame = mask_frame_setting(inf)
 
     def target_classes(self, num_classes: int) -> List[int]:
         return list(range(num_classes) if self.classes_to_infer is None else [c for c in self.classes_to_infer if c < num_classes])
@@ -1978,21 +2090,26 @@ def final_instances(pipe: "InferencePipeline", st: PipelineSettings, name: str, 
                 parts.append(m)
                 all_scores.extend(s)
                 all_classes.extend(c)
-    packed = torch.cat(parts, dim=0) if parts else None
+    packed = (CropMaskSet.cat(parts) if pipe.crop else torch.cat(parts, dim=0)) if parts else None
     pipe.ops.set_frame_width(int(image_dev.shape[1]))
     constrained = bool(spatial_cfg and spatial_cfg.get("enabled", False)) and os.environ.get("DEEPEMIA_ALL_PAIRS", "1") == "1"   # (A/B switch)
     packed, scores, classes, tabs = pipe.deduplicate_masks_smart(packed, all_scores, all_classes, iou_threshold=0.7, with_tables=True,
                                                                 all_pairs=constrained)
     if packed is not None and packed.shape[0]:
-        alg = DeviceMaskAlgebra(pipe.ops, packed, area=tabs[0], bbox=tabs[1])       # (pixel counts / boxes: already on the host)
+        # (pixel counts / boxes: already on the host)
+        alg = CropMaskAlgebra(packed, area=tabs[0], bbox=tabs[1]) if pipe.crop else DeviceMaskAlgebra(pipe.ops, packed, area=tabs[0], bbox=tabs[1])
         if tabs[2] is not None:
             alg.preload(tabs[2])        # ... and every pair's intersection: the constraints below launch and wait for nothing
         keep = apply_spatial_constraints_indices(alg, scores, classes, spatial_cfg)
         if len(keep) != int(packed.shape[0]):
-            packed = pipe.ops.gather_regions(packed, keep, tabs[1][keep])
+            packed = packed.select(keep) if pipe.crop else pipe.ops.gather_regions(packed, keep, tabs[1][keep])
             tabs = (tabs[0][keep], tabs[1][keep])
         scores, classes = [scores[i] for i in keep], [classes[i] for i in keep]
     return packed, scores, classes, tabs
+
+
+# the mask frame of the last ``run_inference`` call and the most full-frame planes any of its images held after the tile mapping
+LAST_RUN_STATS: Dict[str, object] = {}
 
 
 def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw_id=False, dataset_format="json",
@@ -2032,6 +2149,9 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
     pipe = InferencePipeline(predictors, dataset_name, inf, global_config)
     dev = pipe.dev
     spatial_cfg = load_spatial_constraints(dataset_name)
+    run_stats_lock = threading.Lock()
+    LAST_RUN_STATS.clear()
+    LAST_RUN_STATS.update(mask_frame=pipe.mask_frame, full_frame_planes_peak=0, plane_pool_capacity=None)
     # Multi-GPU (one process per GPU): what is sharded over the ranks.  A FOLDER of images is sharded by image (image j ->
     # rank j % world, SURVEY 8(e) "batch": no cross-rank dependency until rank 0 collects the rows it writes); a single large
     # image -- or fewer images than would keep every rank busy -- by tile, with the per-image all-gather of instance tables
@@ -2198,6 +2318,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     system_logger.error(f"Error processing image {name}: {e}")
             return
         try:
+            pipe.begin_image_stats()
             packed, scores, classes, tabs = final_instances(pipe, st, name, image_dev, small_classes, num_classes, spatial_cfg, phases_ok)
             n_final = 0 if packed is None else int(packed.shape[0])
             result = {"masks": packed, "scores": scores, "classes": classes, "hw": (int(image_dev.shape[0]), int(image_dev.shape[1])),
@@ -2209,10 +2330,13 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                 # the measurement phase of this image (inference.py:1030-1291) while its masks and pixels are still resident: the
                 # reference walks the folder a second time after the image loop, which gives the same rows; done here, a folder
                 # of any length holds the masks of ONE image group at a time, and a rank measures the images it owns
-                crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
+                if n_final and pipe.crop:         # the set's own words are what demia_host_rle_text reads (rooms contain the tight boxes)
+                    crop = (packed.payload[:packed.words], packed.room_h, packed.offsets_h)
+                else:
+                    crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
                 extra = [crop[0]] if crop is not None else None
                 rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
-                                                    visualize, image_dev=image_dev, extra=extra)
+                                                    visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes)
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final:
@@ -2222,7 +2346,14 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
             dedup_results[name] = result
             rle_by_image[name] = texts
             processed.add(name)
+            stats = pipe.end_image_stats(result["hw"])
+            with run_stats_lock:
+                LAST_RUN_STATS["mask_frame"] = stats["mask_frame"]
+                LAST_RUN_STATS["plane_pool_capacity"] = stats["plane_pool_capacity"]
+                LAST_RUN_STATS["full_frame_planes_peak"] = max(LAST_RUN_STATS.get("full_frame_planes_peak", 0), stats["full_frame_planes_peak"])
             system_logger.info(f"Image {name}: {n_final} instances in {time.perf_counter() - t0:.2f}s")
+            if pipe.crop:
+                system_logger.info(f"Image {name}: mask frame crop, at most {stats['full_frame_planes_peak']} full-frame planes after the tile mapping")
         except Exception as e:  # reference semantics: log, skip the image, continue (inference.py:928-931)
             system_logger.error(f"Error processing image {name}: {e}", exc_info=True)
         finally:
@@ -2428,7 +2559,7 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
 
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
-                  extra: Optional[list] = None) -> List[list]:
+                  extra: Optional[list] = None, note_planes=None) -> List[list]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
     mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
@@ -2460,7 +2591,15 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     h, wd = data["hw"]
     ops.set_frame_width(wd)
     min_area = max(5, h * wd * 0.000005 * 0.05)
-    if data.get("bbox") is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
+    crop = isinstance(packed, CropMaskSet)
+    if note_planes is not None:
+        note_planes(crop_planes(ops, (h, wd)).cap if crop else 2 * int(packed.shape[0]))      # (the masks + the trace's scratch planes)
+    if crop:
+        # a crop-framed set: the same trace + measurements, a chunk of the plane pool at a time
+        recs, extra_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=extra)
+        if extra is not None:
+            extra[:] = extra_host
+    elif data.get("bbox") is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
         # (``extra``: a list of int32 device tensors the image loop wants on the host in the same copy -- the cropped words of the RLE
         # texts --; replaced in place by their host arrays)
         recs = ops.contours(packed, max_contours=256, um_pix=um_pix, bbox=ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32)),
@@ -2477,10 +2616,10 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
         # measurements.py:195-215: gray levels under the whole instance mask; the histogram is a device reduction
         dev_im = image_dev if image_dev is not None else (None if im_host() is None else torch.from_numpy(im_host()).to(ops.device))
         if dev_im is not None:
-            hist = ops.gray_histogram(packed, dev_im)
+            hist = crop_gray_histogram(packed, crop_planes(ops, (h, wd)), dev_im) if crop else ops.gray_histogram(packed, dev_im)
             contrast = [contrast_percentiles(hh) for hh in hist]
     if visualize and im_host() is not None:
-        write_predictions_png(os.path.join(output_dir, f"{test_img}_predictions.png"), im_host(), mask_crops(ops, packed),
+        write_predictions_png(os.path.join(output_dir, f"{test_img}_predictions.png"), im_host(), packed.host_crops() if crop else mask_crops(ops, packed),
                               classes, recs, metadata.thing_classes)
     return measurement_rows(test_img, classes, recs, metadata.thing_classes, min_area, contrast, psum)
 

@@ -308,10 +308,11 @@ class MaskOps:
 
     # -- contours + measurements ----------------------------------------------------------------
     def trace(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
-              bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None) -> "ContourSet":
+              bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None, scratch: Optional[torch.Tensor] = None) -> "ContourSet":
         """cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) + contourArea + arcLength for every mask, once;
         the returned set can be measured later for any subset of its masks without tracing again.  ``bbox`` (any
-        superset of the tight boxes) and ``total_area`` (sizes the point pool) save a reduction when known."""
+        superset of the tight boxes) and ``total_area`` (sizes the point pool) save a reduction when known.  ``scratch``:
+        the caller's own planes of ``packed``'s shape for the regions that do not fit in LDS (default: allocated here)."""
         M, H, wpr = packed.shape
         W = self._w(packed)
         if bbox is None or (max_points is None and total_area is None):
@@ -321,7 +322,9 @@ class MaskOps:
             max_points = int(min(max(4 * int(total_area) // 8 + 4096 * M, 1 << 16), 1 << 26))
         C = max_contours
         cs = ContourSet(self, M, C, max_points)
-        scratch = torch.empty_like(packed)       # only touched by regions that do not fit in LDS
+        if scratch is None:
+            scratch = torch.empty_like(packed)   # only touched by regions that do not fit in LDS
+        assert scratch.shape == packed.shape and scratch.is_contiguous()
         worklist = torch.empty((M + 2,), dtype=torch.int32, device=self.device) if _WORKLISTS else None    # masks for the large-region variant
         _lib.check(self.lib.demia_mask_contours_wl(_lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bbox), M, H, W, C, max_points,
                                                    _lib.ptr(cs.count), _lib.ptr(cs.info), _lib.ptr(cs.red), _lib.ptr(cs.points),

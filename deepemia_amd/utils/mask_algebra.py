@@ -19,9 +19,10 @@ def _overlap(b1, b2) -> bool:
 
 
 class DeviceMaskAlgebra:
-    def __init__(self, ops, packed: torch.Tensor, area=None, bbox=None, blocks=None):
+    def __init__(self, ops, packed: torch.Tensor, area=None, bbox=None, blocks=None, bbox_dev=None):
         """``area`` / ``bbox`` (device tensors or host arrays): the exact pixel counts and tight boxes when an earlier
         kernel has already reduced them (``MaskOps.program_`` does) -- otherwise one ``demia_mask_area_bbox`` launch.
+        ``bbox_dev``: the device copy of a host ``bbox`` when the caller holds one (no upload here).
         ``blocks``: index arrays (e.g. the masks of one tile each); pairs are only ever asked for INSIDE a block, so the
         box-disjointness table is built block by block (16 x 100^2 instead of 1600^2 entries for a 16-tile batch)."""
         self.ops = ops
@@ -35,7 +36,7 @@ class DeviceMaskAlgebra:
                 self.bbox = bbox.cpu().numpy().astype(np.int64)
             else:
                 self.bbox = np.asarray(bbox, dtype=np.int64).reshape(-1, 4)
-                self._bbox_dev = torch.from_numpy(self.bbox.astype(np.int32)).to(packed.device)
+                self._bbox_dev = bbox_dev if bbox_dev is not None else torch.from_numpy(self.bbox.astype(np.int32)).to(packed.device)
             self.area = (area.cpu().numpy() if isinstance(area, torch.Tensor) else np.asarray(area)).astype(np.int64)
         else:
             self._bbox_dev = torch.zeros((0, 4), dtype=torch.int32, device=packed.device)

@@ -429,6 +429,32 @@ int demia_mask_gather_regions_pooled(const uint32_t* src, const int64_t* index, 
 int demia_mask_crop_unpack(const uint32_t* payload, const int32_t* bbox, const int64_t* offsets, int64_t M, int H, int W,
                            uint32_t* masks, void* stream);
 
+/* Crop-framed mask sets (csrc/cropops.hip): the stages after the tile -> global mapping on masks kept in the global frame as
+ * (room, cropped words) instead of planes [M, H, W/32].  room [M, 4] i32 = (y0, x0, y1, x1) inclusive, -1 = empty: the rectangle
+ * mask m's words are stored for, laid out exactly as demia_mask_crop_pack lays out a bbox -- rows y0 .. y1 x the word columns
+ * (x0 >> 5) .. (x1 >> 5) of the GLOBAL word grid, row-major at payload[offsets[m]]; bbox [M, 4] the TIGHT boxes (inside the
+ * rooms; bits outside them and beyond column W - 1 are zero).  Nothing allocates; every entry is graph-capturable.
+ * place_tiles: demia_mask_place_tiles (same nearest resize of the src_h x src_w tile-frame masks to tile_h x tile_w, same paste
+ *   at (x_off, y_off), same clip at the frame edge) into each mask's room -- the caller's upper bound of its tight box --
+ *   with area / tight bbox reduced on the way out; one workgroup per mask, which writes its own room only.
+ * gather: dst[i] = src[index[i]] (dst_room[i] is the room of src mask index[i]).
+ * pair_matrix / pair_intersections: contract and output layout of demia_mask_pair_matrix / demia_mask_pair_intersections.
+ * unpack_pooled: masks [first, first + n) into slots 0 .. n - 1 of a plane pool that stays zero outside prev (the rule of
+ *   demia_mask_gather_regions_pooled): how the plane kernels (contours, measurements, histograms, programs) reach a set. */
+int demia_crop_place_tiles(const uint32_t* src, const int32_t* x_off, const int32_t* y_off, int64_t M, int src_h, int src_w,
+                           int tile_h, int tile_w, int H, int W, const int32_t* room, const int64_t* offsets, uint32_t* payload,
+                           int32_t* area, int32_t* bbox, void* stream);
+int demia_crop_gather(const uint32_t* src, const int64_t* src_offsets, const int64_t* index, const int32_t* dst_room,
+                      const int64_t* dst_offsets, int64_t M, uint32_t* dst, void* stream);
+int demia_crop_pair_matrix(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                           const int32_t* first, const int32_t* count, const int32_t* label, int32_t* out, int64_t M, int ld,
+                           void* stream);
+int demia_crop_pair_intersections(const uint32_t* payload_a, const int32_t* room_a, const int64_t* offsets_a, const int32_t* bbox_a,
+                                  const uint32_t* payload_b, const int32_t* room_b, const int64_t* offsets_b, const int32_t* bbox_b,
+                                  const int32_t* pi, const int32_t* pj, int32_t* out, int64_t P, void* stream);
+int demia_crop_unpack_pooled(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                             int64_t first, int64_t n, int H, int W, uint32_t* pool, int32_t* prev, int grow, void* stream);
+
 /* a18: contrast distribution (measurements.py:195-215, switched by `measure_contrast_distribution`, inference.py:58,1198):
  * per mask the 256-bin histogram of gray = cv2.cvtColor(image, COLOR_BGR2GRAY) over the mask's pixels -- what
  * np.histogram(gray[mask > 0], bins=256, range=(0, 255)) counts (integer data: bin i = pixels of value i).  The CDF and the

@@ -1,0 +1,107 @@
+"""A/B of `inference_settings.mask_frame`: ONE synthetic 8192 x 8192 image (16 tiles of 2048, overlap 0, upscale 1, R101 -- the shape of
+scripts/gpu_c3_large_image.py and of bench.py's one_8192_image leg) through the CLI's per-image path -- `final_instances` (class passes,
+tile placement, 0.4 merges, 0.7 cross-class pass, spatial constraints), the RLE texts and `measure_image` -- REPS times per frame in one
+process, the frames alternating (full, crop, full, crop, ...), same models, same image, same box.
+
+Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
+forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
+(`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`), the device-to-host waits of the post-processing, the most
+full-frame planes alive after the tile mapping, and whether both frames wrote the same rows and texts.
+
+    python scripts/gpu_crop_frame_ab.py [size=8192] [reps=4] [out.json]
+"""
+import hashlib, json, os, statistics, sys, tempfile, time, types
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
+import numpy as np, torch
+import test_gpu_pipeline_e2e as T
+from deepemia_amd import synth
+
+size = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+out_path = Path(sys.argv[3]).resolve() if len(sys.argv) > 3 else ROOT / "profiles" / f"crop_frame_ab_{size}.json"
+tile = min(2048, size)
+root = Path(tempfile.mkdtemp())
+spatial = {"enabled": True, "containment_rules": {1: 0}, "containment_threshold": 0.5,
+           "overlap_rules": {0: {"allow_overlap": False, "max_iou_threshold": 0.3}, 1: {"allow_overlap": False, "max_iou_threshold": 0.5}}}
+ds_cfg = {"inference_overrides": {"confidence_mode": "manual",
+                                  "class_specific_settings": {"class_0": {"confidence_threshold": 0.3, "iou_threshold": 0.6, "min_size": 25},
+                                                              "class_1": {"confidence_threshold": 0.35, "iou_threshold": 0.5, "min_size": 5}},
+                                  "tile_settings": {"tile_size": tile, "overlap_ratio": 0.0, "upscale_factor": 1.0, "edge_filter_enabled": True},
+                                  "spatial_constraints": spatial}}
+cfgdir, split, sds, _ = T._write_tree(root, [101], 0.5, 6.0, 0, 512, ds_cfg)
+os.environ["DEEPEMIA_CONFIG_DIR"] = str(cfgdir); os.environ["DEEPEMIA_OFFLINE"] = "1"
+os.chdir(root)
+
+from deepemia_amd.engine import MaskRCNNEngine
+from deepemia_amd.functions import inference as I
+from deepemia_amd.predictor import Predictor
+from deepemia_amd.utils.mask_utils import rle_crop_launch, rle_text_from_payload
+from deepemia_amd.utils.spatial_constraints import load_spatial_constraints
+
+k = size // tile
+img = np.concatenate([np.concatenate([synth.em_tile(100 + 4 * r + c, tile) for c in range(k)], axis=1) for r in range(k)], axis=0)
+dev = "cuda:0"
+image_dev = torch.from_numpy(img).to(dev)
+st = I.PipelineSettings(T.DATASET)
+pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"))
+spatial_cfg = load_spatial_constraints(T.DATASET)
+metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
+pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f), st.global_config) for f in ("full", "crop")}
+small = I.determine_small_classes(pipes["full"].calculate_average_mask_sizes([("big.tif", image_dev)]), 50)
+pipes["full"].drop_cached("big.tif")
+
+
+def one_image(pipe):
+    """process_image of run_inference for this image: instances, RLE texts, measurement rows."""
+    name = "big.tif"
+    pipe.begin_image_stats()
+    packed, scores, classes, tabs = I.final_instances(pipe, st, name, image_dev, small, len(T.CLASSES), spatial_cfg, I.image_phases_enabled(pipe))
+    n = 0 if packed is None else int(packed.shape[0])
+    result = {"masks": packed, "scores": scores, "classes": classes, "hw": (size, size),
+              "area": None if tabs is None else tabs[0], "bbox": None if tabs is None else tabs[1]}
+    if n and pipe.crop:
+        crop = (packed.payload[:packed.words], packed.room_h, packed.offsets_h)
+    else:
+        crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
+    extra = [crop[0]] if crop is not None else None
+    rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
+                           note_planes=pipe._note_planes)
+    texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
+    pipe.drop_cached(name)
+    return n, rows, texts, pipe.end_image_stats((size, size))
+
+
+runs = {f: [] for f in pipes}
+digest = {}
+for rep in range(reps):
+    for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ...
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        w0 = pipe.d2h_waits
+        t0 = time.perf_counter()
+        n, rows, texts, stats = one_image(pipe)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        h = hashlib.sha256(("\n".join(texts) + repr(rows)).encode()).hexdigest()
+        digest.setdefault(frame, h)
+        assert digest[frame] == h, "a repetition wrote other rows"
+        runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0, instances=n,
+                                rows=len(rows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
+        print(f"rep {rep} {frame:4s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
+              f"{pipe.d2h_waits - w0} waits, {stats['full_frame_planes_peak']} planes", flush=True)
+
+res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating full, crop",
+       "same_rows_and_texts": digest["full"] == digest["crop"], "device": torch.cuda.get_device_name(0), "frames": {}}
+for frame, rr in runs.items():
+    steady = [r["seconds"] for r in rr[1:]]
+    res["frames"][frame] = dict(first_image_seconds=rr[0]["seconds"], steady_seconds=steady,
+                                steady_median_seconds=statistics.median(steady) if steady else None,
+                                steady_min_max_seconds=[min(steady), max(steady)] if steady else None,
+                                peak_bytes_first=rr[0]["peak_bytes"], peak_bytes_steady=max(r["peak_bytes"] for r in rr[1:]) if steady else None,
+                                d2h_waits_per_image=rr[-1]["d2h_waits"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
+                                full_frame_planes_peak=max(r["full_frame_planes_peak"] for r in rr))
+out_path.parent.mkdir(parents=True, exist_ok=True)
+out_path.write_text(json.dumps(res, indent=1))
+print(json.dumps(res))
