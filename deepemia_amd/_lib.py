@@ -165,6 +165,8 @@ EXPORTS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "demia_crop_unpack_pooled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "demia_crop_gray_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p]),
     "demia_mask_gray_histogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "demia_contour_work_ints": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "demia_contour_work_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
@@ -173,6 +175,10 @@ EXPORTS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "demia_mask_contours_wl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "demia_crop_contour_scratch": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "demia_crop_contours_wl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "demia_contour_measure": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p]),
     "demia_poly_rasterize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,7 +1,8 @@
 """Crop-framed mask sets: instance masks kept in the GLOBAL frame as (room, cropped packed words) instead of full-frame
 planes ``[M, H, W/32]`` -- the representation of the instance tables (``demia_mask_crop_pack``, ``parallel.py``) with the HIP
-kernels that COMPUTE on it (``csrc/cropops.hip``): tile placement, gather, pair counts, and the chunked way back to planes
-for the kernels that want them (contours, measurements, histograms).
+kernels that COMPUTE on it (``csrc/cropops.hip``): tile placement, gather, pair counts, the contour trace and the gray
+histogram on the words in place (``CropMaskSet.trace`` / ``contours`` / ``gray_histogram``: ``mask_frame: crop_direct``), and the
+chunked way back to planes for the plane kernels (``trace_chunks`` / ``crop_contours`` / ``crop_gray_histogram``: ``mask_frame: crop``).
 
 All boxes are ``(y0, x0, y1, x1)``, inclusive, ``-1`` = empty -- the order every box of the C ABI has.
 """
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import MaskOps, PlanePool
+from .maskset import _WORKLISTS, ContourSet, MaskOps, PlanePool
 from .utils.mask_algebra import DeviceMaskAlgebra
 
 
@@ -265,6 +266,80 @@ class CropMaskSet:
                                                          _lib.ptr(tp[0]), _lib.ptr(tp[1]), _lib.ptr(out), P, ops._stream()),
                    "demia_crop_pair_intersections")
         return out.cpu().numpy().astype(np.int64)
+
+    # -- contours, measurements, histogram on the words in place ----------------------------------------------------------
+    def contour_scratch(self) -> Tuple[np.ndarray, int]:
+        """(``scratch_off`` [M] i64, total u32 words) of the scratch a trace of this set needs (``demia_crop_contour_scratch``): host
+        tables only; non-zero for the masks whose room's region exceeds the trace's large LDS buffer."""
+        M = len(self)
+        off = np.zeros(max(M, 1), dtype=np.int64)
+        total = int(self.ops.lib.demia_crop_contour_scratch(self.room_h.ctypes.data, M, self.hw[0], self.hw[1], off.ctypes.data))
+        return off[:M], total
+
+    def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None) -> ContourSet:
+        """``MaskOps.trace`` over ALL masks of the set, read where they are (``demia_crop_contours_wl``): no plane, no chunk, no
+        wait.  The point pool is sized as ``MaskOps.trace`` sizes it from ``total_area`` (the masks' pixel count, or counts, on the
+        host), else from the mask count as ``trace_chunks`` does -- a caller that meets an overflow traces again with the areas.
+        ``scratch``: the caller's own i32 words, at least :meth:`contour_scratch`'s total (default: allocated here)."""
+        ops, M = self.ops, len(self)
+        H, W = self.hw
+        if max_points is None:
+            if total_area is not None:
+                max_points = int(min(max(4 * int(np.sum(total_area)) // 8 + 4096 * M, 1 << 16), 1 << 26))
+            else:
+                max_points = int(min(4096 * M + (1 << 16), 1 << 26))
+        cs = ContourSet(ops, M, int(max_contours), max_points)
+        if M == 0:
+            return cs
+        off_h, total = self.contour_scratch()
+        if total:
+            off_d = ops.upload(off_h)
+            if scratch is None:
+                scratch = torch.empty((total,), dtype=torch.int32, device=ops.device)
+            assert scratch.dtype == torch.int32 and scratch.is_contiguous() and scratch.numel() >= total
+        else:
+            scratch = off_d = torch.empty((1,), dtype=torch.int32, device=ops.device) if scratch is None else scratch      # (never read)
+        worklist = torch.empty((M + 2,), dtype=torch.int32, device=ops.device) if _WORKLISTS else None
+        _lib.check(ops.lib.demia_crop_contours_wl(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox), M, H, W,
+                                                  cs.C, max_points, _lib.ptr(cs.count), _lib.ptr(cs.info), _lib.ptr(cs.red), _lib.ptr(cs.points),
+                                                  _lib.ptr(cs.counters), _lib.ptr(worklist), _lib.ptr(scratch), _lib.ptr(off_d), ops._stream()),
+                   "demia_crop_contours_wl")
+        return cs
+
+    def contours(self, max_contours: int = 64, max_points: Optional[int] = None, um_pix: float = 1.0, measure: bool = True, total_area=None,
+                 extra: Optional[Sequence[torch.Tensor]] = None):
+        """``MaskOps.contours`` for this set: one trace, the measurements of every mask's first four contours right behind it, ONE
+        fetch (``extra`` rides on it); same records, same return value.  Without ``total_area`` the point pool is sized from the
+        mask count; if it overflows, the set is traced again with the pool sized from its own (device) areas -- one more wait."""
+        if len(self) == 0:
+            return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
+
+        def run(area):
+            cs = self.trace(max_contours, max_points, total_area=area)
+            if measure:
+                cs.launch_measure(um_pix, slots=4)
+            return cs, cs.fetch(extra=extra, with_points=True)
+        try:
+            cs, got = run(total_area)
+        except _lib.HipKernelError as e:
+            if "overflow" not in str(e) or total_area is not None or max_points is not None:
+                raise
+            cs, got = run(int(self.area.sum().item()))
+        recs = cs.records(um_pix=um_pix, measure=measure)
+        return recs if extra is None else (recs, list(got))
+
+    def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
+        """``MaskOps.gray_histogram`` on the words in place (``demia_crop_gray_histogram``): [M, 256] gray-level counts."""
+        M, ops = len(self), self.ops
+        if M == 0:
+            return np.zeros((0, 256), dtype=np.int64)
+        H, W = self.hw
+        assert image.dtype == torch.uint8 and image.is_contiguous() and tuple(image.shape[:2]) == (H, W), (image.shape, H, W)
+        ch = 1 if image.dim() == 2 else int(image.shape[2])
+        hist = torch.empty((M, 256), dtype=torch.int32, device=ops.device)
+        _lib.check(ops.lib.demia_crop_gray_histogram(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                     _lib.ptr(image), ch, M, H, W, _lib.ptr(hist), ops._stream()), "demia_crop_gray_histogram")
+        return hist.cpu().numpy().astype(np.int64)
 
 
 class CropMaskAlgebra(DeviceMaskAlgebra):

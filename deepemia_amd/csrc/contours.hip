@@ -191,6 +191,7 @@ constexpr int TRACE_WORDS_SMALL = 1024, CAND_SMALL = 512;
 constexpr int TRACE_WORDS = 8192, CAND_MAX = 3072;
 
 struct ContourP {
+    static constexpr bool ROOM = false;
     const uint32_t* masks;
     uint32_t* scratch;
     const int* bbox;
@@ -203,15 +204,26 @@ struct ContourP {
     int* counters;           // [0] = points used, [1] = error flags, [2] = masks whose walkers fell back, [3] = masks walked by walkers
 };
 
+// The same trace on a crop-framed set (cropops.hip): `masks` is the set's payload -- mask m's words are the rows of room[m] x
+// the word columns (x0 >> 5) .. (x1 >> 5), row-major with the room's own stride at masks[offsets[m]] -- and `scratch` holds,
+// for every mask whose region does not fit in LDS, two buffers in REGION layout (the region with its zero ring, the flood
+// buffer) at scratch[scratch_off[m]] (demia_crop_contour_scratch).  The source is a TYPE: the walks carry no switch on it.
+struct CropContourP : ContourP {
+    static constexpr bool ROOM = true;
+    const int* room;         // [M, 4]
+    const long* offsets;     // [M]
+    const long* scratch_off; // [M]
+};
+
 // One workgroup per mask.  (1) region (+1 ring) -> LDS, (2) flood the outside background (what RETR_EXTERNAL
 // needs to tell an outer border from a component sitting in a hole), hole test and Euler number, (3a) the usual
 // mask -- one component, no holes -- has one border: up to 64 walkers share it (above); (3b) otherwise every
 // start candidate (W, NW, N, NE background, W pixel outside background) is walked by one lane and kept iff the walk
 // never meets a pixel that precedes its start in raster order, i.e. iff it is where OpenCV's raster scan starts
 // that border; valid ones are walked a second time to emit their points.
-template <int TW, int CM>
-__device__ void contour_trace_one(const ContourP& p, const int m, int* __restrict__ worklist) {
-    constexpr bool SMALL = TW != TRACE_WORDS;
+template <int TW, int CM, class P>
+__device__ void contour_trace_one(const P& p, const int m, int* __restrict__ worklist) {
+    constexpr bool SMALL = TW != TRACE_WORDS, ROOM = P::ROOM;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* regA = smem;                              // TW
     uint32_t* regB = smem + TW;                         // TW
@@ -220,7 +232,18 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
     __shared__ Walkers wk;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int wpr = (p.W + 31) >> 5;
-    const int y0 = p.bbox[m * 4 + 0], x0 = p.bbox[m * 4 + 1], y1 = p.bbox[m * 4 + 2], x1 = p.bbox[m * 4 + 3];
+    int y0 = p.bbox[m * 4 + 0], x0 = p.bbox[m * 4 + 1], y1 = p.bbox[m * 4 + 2], x1 = p.bbox[m * 4 + 3];
+    int room_y0 = 0, room_c0 = 0, room_rows = 0, room_cols = 0;
+    if constexpr (ROOM) {
+        // the box is inside the room by contract; clipping it to the room makes that hold for the addressing below whatever
+        // the tables say: the region is then inside the ROOM's region, which is what the host sized the scratch from
+        const int4 r = reinterpret_cast<const int4*>(p.room)[m];          // y0, x0, y1, x1
+        if (y0 >= 0) {
+            y0 = max(y0, r.x); x0 = max(x0, r.y); y1 = min(y1, r.z); x1 = min(x1, r.w);
+            if (r.x < 0 || y0 > y1 || x0 > x1) y0 = -1;
+        }
+        room_y0 = r.x; room_c0 = r.y >> 5; room_rows = r.z - r.x + 1; room_cols = (r.w >> 5) - room_c0 + 1;
+    }
     if (y0 < 0) { if (tid == 0 && SMALL) p.count[m] = 0; return; }
     mreg::Reg g;
     g.H = p.H; g.W = p.W; g.wpr = wpr;
@@ -233,16 +256,32 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
     if (tid == 0) { ncand = 0; ncont = 0; first_cand = 0x7FFFFFFF; wk.K = 0; wk.fail = 0; }
     const int n = g.rh * g.rw;
     const bool use_lds = pn <= TW;
-    const uint32_t* home = p.masks + (long)m * p.H * wpr + (long)g.ry0 * wpr + g.wx0;
-    if (use_lds) {
-        g.A = regA + ps + 1; g.B = regB + ps + 1; g.stride = ps;
+    if constexpr (ROOM) {
+        // LDS or the caller's scratch, the layout is the same: the region with its ring.  A word of the region outside the
+        // room (the ring of a box on the room's edge) is zero and is NEVER fetched: behind a room lie the next mask's words.
+        uint32_t* bufA = regA;
+        uint32_t* bufB = regB;
+        if (!use_lds) { bufA = p.scratch + p.scratch_off[m]; bufB = bufA + pn; }
+        g.A = bufA + ps + 1; g.B = bufB + ps + 1; g.stride = ps;
+        const uint32_t* words = p.masks + p.offsets[m];
         for (int i = tid; i < pn; i += nt) {
             const int py = i / ps, px = i - py * ps;
-            const bool in = py >= 1 && py <= g.rh && px >= 1 && px <= g.rw;
-            regA[i] = in ? home[(long)(py - 1) * wpr + px - 1] : 0u;
+            const int ly = g.ry0 + py - 1 - room_y0, lx = g.wx0 + px - 1 - room_c0;
+            const bool in = py >= 1 && py <= g.rh && px >= 1 && px <= g.rw && (unsigned)ly < (unsigned)room_rows && (unsigned)lx < (unsigned)room_cols;
+            bufA[i] = in ? words[(long)ly * room_cols + lx] : 0u;
         }
     } else {
-        g.A = const_cast<uint32_t*>(home); g.B = p.scratch + (long)m * p.H * wpr + (long)g.ry0 * wpr + g.wx0; g.stride = wpr;
+        const uint32_t* home = p.masks + (long)m * p.H * wpr + (long)g.ry0 * wpr + g.wx0;
+        if (use_lds) {
+            g.A = regA + ps + 1; g.B = regB + ps + 1; g.stride = ps;
+            for (int i = tid; i < pn; i += nt) {
+                const int py = i / ps, px = i - py * ps;
+                const bool in = py >= 1 && py <= g.rh && px >= 1 && px <= g.rw;
+                regA[i] = in ? home[(long)(py - 1) * wpr + px - 1] : 0u;
+            }
+        } else {
+            g.A = const_cast<uint32_t*>(home); g.B = p.scratch + (long)m * p.H * wpr + (long)g.ry0 * wpr + g.wx0; g.stride = wpr;
+        }
     }
     __syncthreads();
     // ---- outside background R (4-connected from beyond the bbox / the image frame) -> g.B -------------------
@@ -288,6 +327,7 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
         return;
     }
     const BitImg im{g.A, g.stride, g.ry0, g.wx0, g.rh, g.rw};
+    const bool pad = ROOM || use_lds;                         // (a room's region carries its zero ring in the scratch as well)
     bool walkers_done = false;
     if (simple && use_lds) {
         // ---------------- (3a) one border, up to 64 walkers (wave 0; lane k = walker k) --------------------------
@@ -391,7 +431,7 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
         for (int c = tid; c < ncand; c += nt) {
             const int code = cand[c];
             const int sy = code / p.W, sx = code - sy * p.W;
-            const TraceResult r = use_lds ? trace_border<true>(im, sx, sy, nullptr, 0) : trace_border<false>(im, sx, sy, nullptr, 0);
+            const TraceResult r = pad ? trace_border<true>(im, sx, sy, nullptr, 0) : trace_border<false>(im, sx, sy, nullptr, 0);
             if (!r.valid) continue;
             const int slot = atomicAdd(&ncont, 1);
             if (slot >= p.C) { atomicOr(&p.counters[1], 2); continue; }
@@ -404,7 +444,7 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
             rd[0] = (double)(r.area2 < 0 ? -r.area2 : r.area2) * 0.5;
             rd[1] = r.perimeter;
             if (off + r.npts + 4 > p.max_points) { atomicOr(&p.counters[1], 4); inf[2] = 0; continue; }
-            if (use_lds) trace_border<true>(im, sx, sy, p.points + 2L * off, r.npts);
+            if (pad) trace_border<true>(im, sx, sy, p.points + 2L * off, r.npts);
             else trace_border<false>(im, sx, sy, p.points + 2L * off, r.npts);
         }
     }
@@ -414,15 +454,15 @@ __device__ void contour_trace_one(const ContourP& p, const int m, int* __restric
 
 // One workgroup per mask; `worklist` (optional, SMALL variant): the masks it leaves to the large variant are appended to
 // worklist[2 ..] (count in worklist[0]).
-template <int TW, int CM>
-__global__ __launch_bounds__(256) void contour_trace_kernel(const ContourP p, int* __restrict__ worklist) {
+template <int TW, int CM, class P>
+__global__ __launch_bounds__(256) void contour_trace_kernel(const P p, int* __restrict__ worklist) {
     contour_trace_one<TW, CM>(p, blockIdx.x, worklist);
 }
 
 // The large variant over that list: a fixed grid, every workgroup takes the next listed mask until the list is empty
 // (as mask_program_list_kernel in maskops.hip: one 78-KiB workgroup per MASK mostly found out that its mask was small).
-template <int TW, int CM>
-__global__ __launch_bounds__(256) void contour_trace_list_kernel(const ContourP p, int* __restrict__ worklist) {
+template <int TW, int CM, class P>
+__global__ __launch_bounds__(256) void contour_trace_list_kernel(const P p, int* __restrict__ worklist) {
     __shared__ int s_next;
     const int count = worklist[0];
     for (;;) {
@@ -949,6 +989,35 @@ __global__ __launch_bounds__(64) void contour_measure_kernel(const MeasureP p) {
     }
 }
 
+// The small / worklist / large launch structure of a trace, for either source of the words.
+template <class P>
+int launch_contour_trace(const P& p, int32_t* worklist, hipStream_t st) {
+    const int M = p.M;
+    hipError_t e = hipMemsetAsync(p.counters, 0, 4 * sizeof(int32_t), st);
+    if (e == hipSuccess && worklist) e = hipMemsetAsync(worklist, 0, 2 * sizeof(int32_t), st);
+    if (e != hipSuccess) { demia_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return DEMIA_ELAUNCH; }
+    constexpr int smem = (2 * TRACE_WORDS + CAND_MAX) * 4, smem_small = (2 * TRACE_WORDS_SMALL + CAND_SMALL) * 4;
+    auto k_small = contour_trace_kernel<TRACE_WORDS_SMALL, CAND_SMALL, P>;
+    auto k_large = contour_trace_kernel<TRACE_WORDS, CAND_MAX, P>;
+    auto k_list = contour_trace_list_kernel<TRACE_WORDS, CAND_MAX, P>;
+    static bool attr_done = false;
+    if (!attr_done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_large), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_list), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(k_small, dim3(M), dim3(256), smem_small, st, p, worklist);
+    DEMIA_CHECK_LAUNCH("contour_trace_kernel<small>");
+    if (worklist) {
+        hipLaunchKernelGGL(k_list, dim3(M < 512 ? M : 512), dim3(256), smem, st, p, worklist);     // two 78-KiB workgroups per CU
+        DEMIA_CHECK_LAUNCH("contour_trace_list_kernel<large>");
+    } else {
+        hipLaunchKernelGGL(k_large, dim3(M), dim3(256), smem, st, p, (int*)nullptr);
+        DEMIA_CHECK_LAUNCH("contour_trace_kernel<large>");
+    }
+    return DEMIA_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t demia_contour_work_ints(int M, int C, int max_points) { return 4L * max_points + 8L * M * C + 16; }
@@ -961,31 +1030,35 @@ extern "C" int demia_mask_contours_wl(const uint32_t* masks, uint32_t* scratch, 
     DEMIA_REQUIRE(masks && scratch && bbox && count && info && red && points && counters && W > 0, "args");
     DEMIA_REQUIRE((long)H * W < (1L << 31) && C > 0 && max_points > 0, "sizes");
     if (M == 0) return DEMIA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), st);
-    if (e == hipSuccess && worklist) e = hipMemsetAsync(worklist, 0, 2 * sizeof(int32_t), st);
-    if (e != hipSuccess) { demia_set_error("hipMemsetAsync: %s", hipGetErrorString(e)); return DEMIA_ELAUNCH; }
-    constexpr int smem = (2 * TRACE_WORDS + CAND_MAX) * 4, smem_small = (2 * TRACE_WORDS_SMALL + CAND_SMALL) * 4;
-    auto k_small = contour_trace_kernel<TRACE_WORDS_SMALL, CAND_SMALL>;
-    auto k_large = contour_trace_kernel<TRACE_WORDS, CAND_MAX>;
-    auto k_list = contour_trace_list_kernel<TRACE_WORDS, CAND_MAX>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_large), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_list), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        attr_done = true;
-    }
     ContourP p{masks, scratch, bbox, M, H, W, C, max_points, count, info, red, points, counters};
-    hipLaunchKernelGGL(k_small, dim3(M), dim3(256), smem_small, st, p, worklist);
-    DEMIA_CHECK_LAUNCH("contour_trace_kernel<small>");
-    if (worklist) {
-        hipLaunchKernelGGL(k_list, dim3(M < 512 ? M : 512), dim3(256), smem, st, p, worklist);     // two 78-KiB workgroups per CU
-        DEMIA_CHECK_LAUNCH("contour_trace_list_kernel<large>");
-    } else {
-        hipLaunchKernelGGL(k_large, dim3(M), dim3(256), smem, st, p, (int*)nullptr);
-        DEMIA_CHECK_LAUNCH("contour_trace_kernel<large>");
+    return launch_contour_trace(p, worklist, (hipStream_t)stream);
+}
+
+// Words of scratch a crop-framed trace needs, from the host's room table alone: a mask whose ROOM's region (+ 1 ring, clipped
+// to the frame: an upper bound of the region of its tight box) exceeds the large LDS buffer gets two padded region buffers.
+extern "C" int64_t demia_crop_contour_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch_off) {
+    int64_t total = 0;
+    for (int64_t m = 0; m < M; ++m) {
+        const int32_t* r = room_host + 4 * m;
+        scratch_off[m] = total;
+        if (r[0] < 0) continue;
+        int ry0, wx0, rh, rw;
+        mreg::region_of(r[0], r[1], r[2], r[3], 1, H, W, ry0, wx0, rh, rw);
+        const int64_t pn = (int64_t)(rh + 2) * (rw + 2);
+        if (pn > TRACE_WORDS) total += 2 * pn;
     }
-    return DEMIA_OK;
+    return total;
+}
+
+extern "C" int demia_crop_contours_wl(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox, int M, int H,
+                                      int W, int C, int max_points, int32_t* count, int32_t* info, double* red, int32_t* points,
+                                      int32_t* counters, int32_t* worklist, uint32_t* scratch, const int64_t* scratch_off, void* stream) {
+    DEMIA_REQUIRE(payload && room && offsets && bbox && count && info && red && points && counters && scratch && scratch_off && W > 0 && H > 0, "args");
+    DEMIA_REQUIRE((long)H * W < (1L << 31) && C > 0 && max_points > 0, "sizes");
+    if (M == 0) return DEMIA_OK;
+    CropContourP p{{payload, scratch, bbox, M, H, W, C, max_points, count, info, red, points, counters}, room,
+                   reinterpret_cast<const long*>(offsets), reinterpret_cast<const long*>(scratch_off)};
+    return launch_contour_trace(p, worklist, (hipStream_t)stream);
 }
 
 extern "C" int demia_mask_contours(const uint32_t* masks, uint32_t* scratch, const int32_t* bbox, int M, int H, int W, int C,

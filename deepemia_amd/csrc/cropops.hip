@@ -203,6 +203,48 @@ __global__ __launch_bounds__(256) void crop_unpack_pooled_kernel(const uint32_t*
     }
 }
 
+// ---- gray_hist_kernel (maskops.hip) on a room's words: same bins, same BGR -> gray fixed point.  One workgroup per mask over
+// the words of its tight box that lie in its room; bits beyond column W - 1 are masked off before they index the image.
+__global__ __launch_bounds__(256) void crop_gray_hist_kernel(const uint32_t* __restrict__ payload, const int* __restrict__ room,
+                                                             const long* __restrict__ offsets, const int* __restrict__ bbox,
+                                                             const uint8_t* __restrict__ img, int channels, int H, int W,
+                                                             int* __restrict__ hist) {
+    __shared__ int s_h[256];
+    const long m = blockIdx.x;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const int4 b4 = reinterpret_cast<const int4*>(bbox)[m];       // y0, x0, y1, x1
+    const Room g = room_of(room, m);
+    if (b4.x >= 0 && g.rows > 0) {
+        const int ry0 = max(max(b4.x, 0), g.y0), ry1 = min(min(b4.z, H - 1), g.y0 + g.rows - 1);
+        const int wx0 = max(max(b4.y, 0) >> 5, g.c0), wx1 = min(min(b4.w, W - 1) >> 5, g.c0 + g.cols - 1);
+        const int rh = ry1 - ry0 + 1, rw = wx1 - wx0 + 1;
+        const int last = (W - 1) >> 5;
+        const uint32_t* src = payload + offsets[m];
+        for (int i = threadIdx.x; i < rh * rw && rw > 0; i += blockDim.x) {
+            const int ly = i / rw, lx = i - ly * rw;
+            const int y = ry0 + ly, wx = wx0 + lx;
+            uint32_t b = src[(long)(y - g.y0) * g.cols + (wx - g.c0)];
+            if (wx == last && (W & 31)) b &= (1u << (W & 31)) - 1u;
+            while (b) {
+                const int bit = __ffs((int)b) - 1;
+                b &= b - 1;
+                const long px = (long)y * W + (wx << 5) + bit;
+                int gr;
+                if (channels == 3) {
+                    const uint8_t* q = img + px * 3;
+                    gr = (q[0] * 1868 + q[1] * 9617 + q[2] * 4899 + (1 << 13)) >> 14;
+                } else {
+                    gr = img[px];
+                }
+                atomicAdd(&s_h[gr], 1);
+            }
+        }
+    }
+    __syncthreads();
+    hist[m * 256 + threadIdx.x] = s_h[threadIdx.x];
+}
+
 }  // namespace
 
 extern "C" int demia_crop_place_tiles(const uint32_t* src, const int32_t* x_off, const int32_t* y_off, int64_t M, int src_h, int src_w,
@@ -267,5 +309,17 @@ extern "C" int demia_crop_unpack_pooled(const uint32_t* payload, const int32_t* 
     hipLaunchKernelGGL(crop_unpack_pooled_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, payload, room,
                        reinterpret_cast<const long*>(offsets), bbox, (long)first, pool, prev, H, W, grow);
     DEMIA_CHECK_LAUNCH("crop_unpack_pooled_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_gray_histogram(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                                         const uint8_t* image, int channels, int64_t M, int H, int W, int32_t* hist, void* stream) {
+    DEMIA_REQUIRE(M >= 0 && W > 0 && H > 0 && (channels == 1 || channels == 3), "shapes");
+    if (M == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(payload && room && offsets && bbox && image && hist, "args");
+    DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
+    hipLaunchKernelGGL(crop_gray_hist_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, payload, room,
+                       reinterpret_cast<const long*>(offsets), bbox, image, channels, H, W, hist);
+    DEMIA_CHECK_LAUNCH("crop_gray_hist_kernel");
     return DEMIA_OK;
 }

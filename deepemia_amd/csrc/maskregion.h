@@ -47,8 +47,8 @@ struct Reg {
     int H, W, wpr;      // frame
 };
 
-// Region of a (superset) bbox grown by `e` pixels, clipped to the frame.
-__device__ __forceinline__ void region_of(int y0, int x0, int y1, int x1, int e, int H, int W, int& ry0, int& wx0, int& rh, int& rw) {
+// Region of a (superset) bbox grown by `e` pixels, clipped to the frame.  (Host code sizes buffers with the same rule.)
+__host__ __device__ __forceinline__ void region_of(int y0, int x0, int y1, int x1, int e, int H, int W, int& ry0, int& wx0, int& rh, int& rw) {
     ry0 = max(y0 - e, 0);
     const int ry1 = min(y1 + e, H - 1);
     wx0 = max(x0 - e, 0) >> 5;

@@ -288,21 +288,23 @@ def _smart_dedup_keep(lib, I: np.ndarray, ld: int, run_first: np.ndarray, area: 
     return [np.asarray(groups[t])[keep_out[tile_off[t]:tile_off[t] + keep_cnt[t]]] for t in range(T)]
 
 
-MASK_FRAMES = ("full", "crop")
+MASK_FRAMES = ("full", "crop", "crop_direct")
 
 
 def mask_frame_setting(inf_settings: dict) -> str:
     """``inference_settings.mask_frame`` (per dataset): ``full`` (the default) keeps the masks of the stages after the tile ->
-    global mapping as full-frame planes, ``crop`` as a :class:`CropMaskSet`.  An unknown value is a configuration error, and so
-    is ``crop`` with the modes that stay on ``full``: ``merge_mode: soft_nms`` and ``multiscale_settings.enabled``."""
+    global mapping as full-frame planes, ``crop`` and ``crop_direct`` as a :class:`CropMaskSet` -- ``crop`` takes the set through
+    a pool of 32 planes for the contour trace, the measurements and the gray histogram, ``crop_direct`` runs those three on the
+    cropped words in place.  An unknown value is a configuration error, and so is either crop value with the modes that stay on
+    ``full``: ``merge_mode: soft_nms`` and ``multiscale_settings.enabled``."""
     frame = str((inf_settings or {}).get("mask_frame", "full"))
     if frame not in MASK_FRAMES:
-        raise ValueError(f"inference_settings.mask_frame must be 'full' or 'crop', got {frame!r}")
-    if frame == "crop":
+        raise ValueError(f"inference_settings.mask_frame must be 'full' or 'crop' or 'crop_direct', got {frame!r}")
+    if frame != "full":
         if str(inf_settings.get("merge_mode", "smart")) == "soft_nms":
-            raise ValueError("inference_settings.mask_frame: crop cannot be combined with merge_mode: soft_nms (soft-NMS runs on full-frame planes only)")
+            raise ValueError(f"inference_settings.mask_frame: {frame} cannot be combined with merge_mode: soft_nms (soft-NMS runs on full-frame planes only)")
         if bool((inf_settings.get("multiscale_settings", {}) or {}).get("enabled", False)):
-            raise ValueError("inference_settings.mask_frame: crop cannot be combined with multiscale_settings.enabled (multi-scale runs on full-frame planes only)")
+            raise ValueError(f"inference_settings.mask_frame: {frame} cannot be combined with multiscale_settings.enabled (multi-scale runs on full-frame planes only)")
     return frame
 
 
@@ -375,13 +377,19 @@ class InferencePipeline:
         self.rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.exchange = parallel.ExchangeState()     # this job's agreed capacities: every rank builds its pipeline at the same point
-        if self.mask_frame == "crop" and self.world > 1:
-            raise ValueError("inference_settings.mask_frame: crop runs in one process only (WORLD_SIZE = "
+        if self.crop and self.world > 1:
+            raise ValueError(f"inference_settings.mask_frame: {self.mask_frame} runs in one process only (WORLD_SIZE = "
                              f"{self.world}): the gathered instance tables are unpacked to full-frame planes; use mask_frame: full")
 
     @property
     def crop(self) -> bool:
-        return self.mask_frame == "crop"
+        """The stages after the tile -> global mapping hold a :class:`CropMaskSet` (``crop`` and ``crop_direct``)."""
+        return self.mask_frame != "full"
+
+    @property
+    def crop_direct(self) -> bool:
+        """... and trace, measure and histogram it in place instead of through the plane pool."""
+        return self.mask_frame == "crop_direct"
 
     def _note_planes(self, n: int) -> None:
         """``n`` full-frame planes of the stages after the tile -> global mapping are alive at this point (the class passes' own
@@ -392,7 +400,7 @@ class InferencePipeline:
         self._tls.planes_peak = 0
 
     def end_image_stats(self, hw) -> dict:
-        cap = 2 * CropPlanes.CHUNK if self.crop else None
+        cap = None if not self.crop else 0 if self.crop_direct else 2 * CropPlanes.CHUNK
         self.last_image_stats = {"mask_frame": self.mask_frame, "full_frame_planes_peak": int(getattr(self._tls, "planes_peak", 0)), "plane_pool_capacity": cap}
         return self.last_image_stats
 
@@ -665,7 +673,8 @@ class InferencePipeline:
         ld = max(1, int(run_count.max()))
         if crop:
             # the same stage on cropped words: pixel counts and tight boxes are the set's own, the pair matrix comes from
-            # demia_crop_pair_matrix, and the (unchanged) contour trace reaches the masks through the plane pool, a chunk at a time
+            # demia_crop_pair_matrix, and the contour trace reaches the masks through the plane pool, a chunk at a time (crop), or
+            # reads the words in place (crop_direct)
             I = packed.pair_matrix(run_first, np.maximum(run_count, 1), None, ld)
             per0, area, bbox, I_c = self._fetch_traced_tables_crop(packed, I, ld)
         else:
@@ -726,12 +735,29 @@ class InferencePipeline:
                 np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
 
     def _fetch_traced_tables_crop(self, cs: CropMaskSet, I: torch.Tensor, ld: int):
-        """:meth:`_fetch_traced_tables` for a crop-framed set: the chunks go through the plane pool one behind the other
+        """:meth:`_fetch_traced_tables` for a crop-framed set.  ``crop_direct``: one ``CropMaskSet.trace`` and one fetch that carries
+        the contour tables, pixel counts, tight boxes and the pair matrix (one more wait only when the point pool overflows and the
+        set is traced again).  ``crop``: the chunks go through the plane pool one behind the other
         (``trace_chunks``: a chunk is fetched while the next one runs); the first chunk's fetch brings pixel counts, tight boxes
         and the pair matrix along, every further chunk costs one more wait.  A chunk whose point pool
         overflows is unpacked and traced again with the area-sized pool.  Returns (first-contour perimeters f64 [n], area i64
         [n], bbox i64 [n, 4], I i32 [n, ld])."""
         n = len(cs)
+        if self.crop_direct:
+            # one trace over all masks on the words in place, one fetch: the accounting of _fetch_traced_tables
+            extra = [cs.area, cs.bbox, I]
+            cset = cs.trace(max_contours=256)
+            try:
+                area_h, bbox_h, I_h = cset.fetch(extra=extra)
+            except _L.HipKernelError as e:
+                if "overflow" not in str(e):
+                    raise
+                self.d2h_waits += 1
+                cset = cs.trace(max_contours=256, total_area=int(cs.area.sum().item()))
+                area_h, bbox_h, I_h = cset.fetch(extra=extra)
+            self.d2h_waits += 1
+            return (cset.first_contour_perimeter(), np.ascontiguousarray(area_h, dtype=np.int64),
+                    np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64), np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
         planes = crop_planes(self.ops, cs.hw)
         self._note_planes(planes.cap)
         per0, tabs = [], None
@@ -2336,7 +2362,8 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
                 extra = [crop[0]] if crop is not None else None
                 rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
-                                                    visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes)
+                                                    visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes,
+                                                    crop_direct=pipe.crop_direct)
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final:
@@ -2353,7 +2380,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                 LAST_RUN_STATS["full_frame_planes_peak"] = max(LAST_RUN_STATS.get("full_frame_planes_peak", 0), stats["full_frame_planes_peak"])
             system_logger.info(f"Image {name}: {n_final} instances in {time.perf_counter() - t0:.2f}s")
             if pipe.crop:
-                system_logger.info(f"Image {name}: mask frame crop, at most {stats['full_frame_planes_peak']} full-frame planes after the tile mapping")
+                system_logger.info(f"Image {name}: mask frame {pipe.mask_frame}, at most {stats['full_frame_planes_peak']} full-frame planes after the tile mapping")
         except Exception as e:  # reference semantics: log, skip the image, continue (inference.py:928-931)
             system_logger.error(f"Error processing image {name}: {e}", exc_info=True)
         finally:
@@ -2430,7 +2457,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     wri.writerow([name.rsplit(".", 1)[0], text])
 
         write_measurements(pipe.ops, dedup_results, inpath, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                           rows_by_image=rows_by_image)
+                           rows_by_image=rows_by_image, crop_direct=pipe.crop_direct)
         with open(os.path.join(output_dir, "class_color_legend.txt"), "w") as f:
             f.write("Class Color Legend (BGR)\n")
             for i, cname in enumerate(metadata.thing_classes):
@@ -2559,11 +2586,12 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
 
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
-                  extra: Optional[list] = None, note_planes=None) -> List[list]:
+                  extra: Optional[list] = None, note_planes=None, crop_direct: bool = False) -> List[list]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
     mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
-    the file here, which gives the same bytes)."""
+    the file here, which gives the same bytes).  ``crop_direct``: a crop-framed set is traced, measured and histogrammed on its
+    words in place (``mask_frame: crop_direct``) instead of through the plane pool."""
     measure_contrast = bool(get_config().get("measure_contrast_distribution", False))     # inference.py:58: GLOBAL config
     host = {}
 
@@ -2592,9 +2620,17 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     ops.set_frame_width(wd)
     min_area = max(5, h * wd * 0.000005 * 0.05)
     crop = isinstance(packed, CropMaskSet)
-    if note_planes is not None:
+    direct = crop and crop_direct
+    if note_planes is not None and not direct:
         note_planes(crop_planes(ops, (h, wd)).cap if crop else 2 * int(packed.shape[0]))      # (the masks + the trace's scratch planes)
-    if crop:
+    if direct:
+        # a crop-framed set traced and measured on its words in place: one trace, one fetch, no plane
+        area_h = data.get("area")
+        recs = packed.contours(max_contours=256, um_pix=um_pix, total_area=None if area_h is None else int(np.sum(area_h)), extra=extra)
+        if extra is not None:
+            recs, extra_host = recs
+            extra[:] = extra_host
+    elif crop:
         # a crop-framed set: the same trace + measurements, a chunk of the plane pool at a time
         recs, extra_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=extra)
         if extra is not None:
@@ -2616,7 +2652,10 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
         # measurements.py:195-215: gray levels under the whole instance mask; the histogram is a device reduction
         dev_im = image_dev if image_dev is not None else (None if im_host() is None else torch.from_numpy(im_host()).to(ops.device))
         if dev_im is not None:
-            hist = crop_gray_histogram(packed, crop_planes(ops, (h, wd)), dev_im) if crop else ops.gray_histogram(packed, dev_im)
+            if direct:
+                hist = packed.gray_histogram(dev_im)
+            else:
+                hist = crop_gray_histogram(packed, crop_planes(ops, (h, wd)), dev_im) if crop else ops.gray_histogram(packed, dev_im)
             contrast = [contrast_percentiles(hh) for hh in hist]
     if visualize and im_host() is not None:
         write_predictions_png(os.path.join(output_dir, f"{test_img}_predictions.png"), im_host(), packed.host_crops() if crop else mask_crops(ops, packed),
@@ -2626,7 +2665,7 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
 
 def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_path: str, output_dir: str, metadata,
                        dataset_name: str, draw_scalebar: bool = False, visualize: bool = False,
-                       rows_by_image: Optional[Dict[str, List[list]]] = None) -> str:
+                       rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False) -> str:
     """Measurement phase (``inference.py:983-1291``): one CSV row per external contour that passes
     the area gate, 20 columns, ``None`` -> empty field, floats through ``csv.writer``.  ``rows_by_image``: rows the image
     loop (or another rank, when images are sharded over ranks) has already measured; images without an entry are measured here."""
@@ -2641,7 +2680,8 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
             if rows_by_image is not None and test_img in rows_by_image:
                 rows = rows_by_image[test_img]
             else:
-                rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize)
+                rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize,
+                                     crop_direct=crop_direct)
             for r in rows:
                 w.writerow(r)
             csvfile.flush()

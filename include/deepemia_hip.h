@@ -440,7 +440,8 @@ int demia_mask_crop_unpack(const uint32_t* payload, const int32_t* bbox, const i
  * gather: dst[i] = src[index[i]] (dst_room[i] is the room of src mask index[i]).
  * pair_matrix / pair_intersections: contract and output layout of demia_mask_pair_matrix / demia_mask_pair_intersections.
  * unpack_pooled: masks [first, first + n) into slots 0 .. n - 1 of a plane pool that stays zero outside prev (the rule of
- *   demia_mask_gather_regions_pooled): how the plane kernels (contours, measurements, histograms, programs) reach a set. */
+ *   demia_mask_gather_regions_pooled): how the plane kernels (contours, measurements, histograms, programs) reach a set.
+ * gray_histogram: contract, bins and BGR -> gray arithmetic of demia_mask_gray_histogram, read from the rooms' words in place. */
 int demia_crop_place_tiles(const uint32_t* src, const int32_t* x_off, const int32_t* y_off, int64_t M, int src_h, int src_w,
                            int tile_h, int tile_w, int H, int W, const int32_t* room, const int64_t* offsets, uint32_t* payload,
                            int32_t* area, int32_t* bbox, void* stream);
@@ -454,6 +455,8 @@ int demia_crop_pair_intersections(const uint32_t* payload_a, const int32_t* room
                                   const int32_t* pi, const int32_t* pj, int32_t* out, int64_t P, void* stream);
 int demia_crop_unpack_pooled(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
                              int64_t first, int64_t n, int H, int W, uint32_t* pool, int32_t* prev, int grow, void* stream);
+int demia_crop_gray_histogram(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                              const uint8_t* image, int channels, int64_t M, int H, int W, int32_t* hist, void* stream);
 
 /* a18: contrast distribution (measurements.py:195-215, switched by `measure_contrast_distribution`, inference.py:58,1198):
  * per mask the 256-bin histogram of gray = cv2.cvtColor(image, COLOR_BGR2GRAY) over the mask's pixels -- what
@@ -491,6 +494,19 @@ int demia_mask_contours(const uint32_t* masks, uint32_t* scratch, const int32_t*
 int demia_mask_contours_wl(const uint32_t* masks, uint32_t* scratch, const int32_t* bbox, int M, int H, int W, int C,
                            int max_points, int32_t* count, int32_t* info, double* red, int32_t* points,
                            int32_t* counters, int32_t* worklist, void* stream);
+/* demia_mask_contours_wl for a crop-framed set (payload, room, offsets, bbox as the demia_crop_* entries take them): the same
+ * tracer reads each mask's words in place, with the contract and the output layouts above, so its tables feed
+ * demia_contour_measure unchanged.  A word of a traced region (tight box + 1 ring, clipped to the frame) that lies outside the
+ * mask's room is zero and is never fetched.  No full-frame plane exists anywhere: a region larger than the LDS buffers works in
+ * scratch[scratch_off[m] ..) (u32 words: the region with its zero ring, then the flood buffer), which
+ * demia_crop_contour_scratch sizes from the HOST copy of the rooms alone (nothing there touches the GPU): it fills scratch_off
+ * [M] i64 and returns the total words -- 2 x the padded region of the ROOM (an upper bound of the box's) for a mask whose room
+ * region exceeds the large LDS buffer, 0 for every other mask.  With a total of 0, scratch and scratch_off may be any non-NULL
+ * device pointers: they are not read. */
+int64_t demia_crop_contour_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch_off);
+int demia_crop_contours_wl(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox, int M, int H,
+                           int W, int C, int max_points, int32_t* count, int32_t* info, double* red, int32_t* points,
+                           int32_t* counters, int32_t* worklist, uint32_t* scratch, const int64_t* scratch_off, void* stream);
 int demia_contour_measure(const int32_t* select /* [M] or NULL */, const int32_t* count, const int32_t* info,
                           const double* red, const int32_t* points, int M,
                           int C, int max_points, int32_t* work_i, float* work_f, double* work_d, double um_pix,

@@ -1,14 +1,15 @@
 """A/B of `inference_settings.mask_frame`: ONE synthetic 8192 x 8192 image (16 tiles of 2048, overlap 0, upscale 1, R101 -- the shape of
 scripts/gpu_c3_large_image.py and of bench.py's one_8192_image leg) through the CLI's per-image path -- `final_instances` (class passes,
 tile placement, 0.4 merges, 0.7 cross-class pass, spatial constraints), the RLE texts and `measure_image` -- REPS times per frame in one
-process, the frames alternating (full, crop, full, crop, ...), same models, same image, same box.
+process, the frames alternating (full, crop, full, crop, ...; the fourth argument names other frames to alternate, e.g.
+full,crop,crop_direct), same models, same image, same box.
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
 (`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`), the device-to-host waits of the post-processing, the most
-full-frame planes alive after the tile mapping, and whether both frames wrote the same rows and texts.
+full-frame planes alive after the tile mapping, and whether all frames wrote the same rows and texts.
 
-    python scripts/gpu_crop_frame_ab.py [size=8192] [reps=4] [out.json]
+    python scripts/gpu_crop_frame_ab.py [size=8192] [reps=4] [out.json] [frames=full,crop]
 """
 import hashlib, json, os, statistics, sys, tempfile, time, types
 from pathlib import Path
@@ -21,6 +22,7 @@ from deepemia_amd import synth
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 out_path = Path(sys.argv[3]).resolve() if len(sys.argv) > 3 else ROOT / "profiles" / f"crop_frame_ab_{size}.json"
+frames = tuple(sys.argv[4].split(",")) if len(sys.argv) > 4 else ("full", "crop")
 tile = min(2048, size)
 root = Path(tempfile.mkdtemp())
 spatial = {"enabled": True, "containment_rules": {1: 0}, "containment_threshold": 0.5,
@@ -48,9 +50,9 @@ st = I.PipelineSettings(T.DATASET)
 pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"))
 spatial_cfg = load_spatial_constraints(T.DATASET)
 metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
-pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f), st.global_config) for f in ("full", "crop")}
-small = I.determine_small_classes(pipes["full"].calculate_average_mask_sizes([("big.tif", image_dev)]), 50)
-pipes["full"].drop_cached("big.tif")
+pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f), st.global_config) for f in frames}
+small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes([("big.tif", image_dev)]), 50)
+pipes[frames[0]].drop_cached("big.tif")
 
 
 def one_image(pipe):
@@ -67,7 +69,7 @@ def one_image(pipe):
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     pipe.drop_cached(name)
     return n, rows, texts, pipe.end_image_stats((size, size))
@@ -76,7 +78,7 @@ def one_image(pipe):
 runs = {f: [] for f in pipes}
 digest = {}
 for rep in range(reps):
-    for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ...
+    for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ... (the order of `frames`)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         w0 = pipe.d2h_waits
@@ -89,11 +91,11 @@ for rep in range(reps):
         assert digest[frame] == h, "a repetition wrote other rows"
         runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0, instances=n,
                                 rows=len(rows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
-        print(f"rep {rep} {frame:4s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
+        print(f"rep {rep} {frame:11s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
               f"{pipe.d2h_waits - w0} waits, {stats['full_frame_planes_peak']} planes", flush=True)
 
-res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating full, crop",
-       "same_rows_and_texts": digest["full"] == digest["crop"], "device": torch.cuda.get_device_name(0), "frames": {}}
+res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating " + ", ".join(frames),
+       "same_rows_and_texts": len(set(digest.values())) == 1, "device": torch.cuda.get_device_name(0), "frames": {}}
 for frame, rr in runs.items():
     steady = [r["seconds"] for r in rr[1:]]
     res["frames"][frame] = dict(first_image_seconds=rr[0]["seconds"], steady_seconds=steady,
