@@ -10,7 +10,8 @@ scikit-image primitives under a10 / a11.  The OpenCV / imutils geometry (contour
 minAreaRect, boxPoints, order_points, fitEllipse -- rows a14, a17, a18) restates the published
 algorithms of opencv-python-headless 4.11.0.86 / imutils and is **parity unpinned** (no
 OpenCV here, no reference fixtures); it is anchored by closed-form
-known-answer shapes in the tests.
+known-answer shapes in the tests and, for the twelve measurement values, by the independent
+float64 geometry of ``tests/contour_cases.py`` (``tests/test_cpu_contour_geometry.py``).
 """
 from __future__ import annotations
 
