@@ -1,6 +1,7 @@
 """Crop-framed mask sets: instance masks kept in the GLOBAL frame as (room, cropped packed words) instead of full-frame
 planes ``[M, H, W/32]`` -- the representation of the instance tables (``demia_mask_crop_pack``, ``parallel.py``) with the HIP
-kernels that COMPUTE on it (``csrc/cropops.hip``): tile placement, gather, pair counts, the contour trace and the gray
+kernels that COMPUTE on it (``csrc/cropops.hip``; the reading stages are ``csrc/maskops.hip``'s own kernels over
+``mwords::CropWords``): tile placement, gather, pair counts, the contour trace and the gray
 histogram on the words in place (``CropMaskSet.trace`` / ``contours`` / ``gray_histogram``: ``mask_frame: crop_direct``), and the
 chunked way back to planes for the plane kernels (``trace_chunks`` / ``crop_contours`` / ``crop_gray_histogram``: ``mask_frame: crop``).
 

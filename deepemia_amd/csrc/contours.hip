@@ -204,7 +204,7 @@ struct ContourP {
     int* counters;           // [0] = points used, [1] = error flags, [2] = masks whose walkers fell back, [3] = masks walked by walkers
 };
 
-// The same trace on a crop-framed set (cropops.hip): `masks` is the set's payload -- mask m's words are the rows of room[m] x
+// The same trace on a crop-framed set (layout: cropops.hip): `masks` is the set's payload -- mask m's words are the rows of room[m] x
 // the word columns (x0 >> 5) .. (x1 >> 5), row-major with the room's own stride at masks[offsets[m]] -- and `scratch` holds,
 // for every mask whose region does not fit in LDS, two buffers in REGION layout (the region with its zero ring, the flood
 // buffer) at scratch[scratch_off[m]] (demia_crop_contour_scratch).  The source is a TYPE: the walks carry no switch on it.

@@ -13,10 +13,18 @@
 // Layout: [M, H, ceil(W/32)] u32, bit (x & 31) of word (x >> 5).  Fill / erode / dilate / component test run as
 // stage PROGRAMS on the mask's bounding-box region, in place, one workgroup per mask (maskregion.h): the frame
 // outside the box is never touched.  Every kernel that takes a bbox accepts a superset of the tight box.
+//
+// The kernels that only READ masks -- pair counts, gray histogram, pooled gather -- are templates over the SOURCE of the
+// words (maskwords.h): PlaneWords for this layout, CropWords for crop-framed sets (cropops.hip has the layout), whose
+// demia_crop_* entries are therefore here, next to their plane forms.
 #include "common.h"
 #include "maskregion.h"
+#include "maskwords.h"
 
 namespace {
+
+using mwords::CropWords;
+using mwords::PlaneWords;
 
 // LDS words per region buffer.  Two launches per program: most masks are a few hundred words and run in the SMALL
 // variant, whose 8 KiB of LDS fit beside the two resident workgroups of a convolution on the other stream (the next
@@ -253,31 +261,20 @@ __global__ void column_counts_kernel(const uint32_t* __restrict__ masks, const i
     if (c) atomicAdd(&counts[(long)(seg ? seg[m] : 0) * W + x], c);
 }
 
-// ---- |a & b| for a list of pairs: block per pair over the bbox intersection ----------------------
-__global__ __launch_bounds__(256) void pair_intersections_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
-                                                                 const int* __restrict__ pi, const int* __restrict__ pj,
-                                                                 const int* __restrict__ bbox_a, const int* __restrict__ bbox_b,
-                                                                 int* __restrict__ out, int H, int W) {
+// ---- |a_i & b_j| for a list of pairs: block per pair over the intersection of the two tight boxes (mwords::pair_count) ----
+template <class SA, class SB>
+__global__ __launch_bounds__(256) void pair_intersections_kernel(const SA a, const int* __restrict__ bbox_a, const SB b,
+                                                                 const int* __restrict__ bbox_b, const int* __restrict__ pi,
+                                                                 const int* __restrict__ pj, int* __restrict__ out) {
     __shared__ int acc;
     const int p = blockIdx.x;
     const int i = pi[p], j = pj[p];
-    const int wpr = (W + 31) >> 5;
-    const int y0 = max(bbox_a[i * 4 + 0], bbox_b[j * 4 + 0]), y1 = min(bbox_a[i * 4 + 2], bbox_b[j * 4 + 2]);
-    const int x0 = max(bbox_a[i * 4 + 1], bbox_b[j * 4 + 1]), x1 = min(bbox_a[i * 4 + 3], bbox_b[j * 4 + 3]);
     if (threadIdx.x == 0) acc = 0;
     __syncthreads();
-    if (bbox_a[i * 4] >= 0 && bbox_b[j * 4] >= 0 && y0 <= y1 && x0 <= x1) {
-        const int wx0 = x0 >> 5, rw = (x1 >> 5) - wx0 + 1, rh = y1 - y0 + 1;
-        const uint32_t* ma = a + (long)i * H * wpr;
-        const uint32_t* mb = b + (long)j * H * wpr;
-        int c = 0;
-        for (int t = threadIdx.x; t < rh * rw; t += blockDim.x) {
-            const long o = (long)(y0 + t / rw) * wpr + wx0 + t % rw;
-            c += __popc(ma[o] & mb[o]);
-        }
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&acc, c);
-    }
+    int c = mwords::pair_count<1>(a.view(i), reinterpret_cast<const int4*>(bbox_a)[i], b.view(j), reinterpret_cast<const int4*>(bbox_b)[j],
+                                  threadIdx.x, 256);
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&acc, c);
     __syncthreads();
     if (threadIdx.x == 0) out[p] = acc;
 }
@@ -286,30 +283,23 @@ __global__ __launch_bounds__(256) void pair_intersections_kernel(const uint32_t*
 // candidate j > i in turn; pairs whose boxes are disjoint (nearly all) cost four scalar loads.  Row i of `out`
 // ([M, ld], pre-zeroed) receives |a_i & a_j| at column j - first[i] -- the upper triangle; the host mirrors it.
 // `label` (optional): only pairs with equal labels are counted (same-class pairs of a cross-class set).
-__global__ __launch_bounds__(256) void pair_matrix_kernel(const uint32_t* __restrict__ a, const int* __restrict__ bbox,
-                                                          const int* __restrict__ first, const int* __restrict__ count,
-                                                          const int* __restrict__ label, int* __restrict__ out, int ld, int H, int W) {
+template <class S>
+__global__ __launch_bounds__(256) void pair_matrix_kernel(const S src, const int* __restrict__ bbox, const int* __restrict__ first,
+                                                          const int* __restrict__ count, const int* __restrict__ label,
+                                                          int* __restrict__ out, int ld) {
     const int i = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = first[i], end = f + count[i];
     const int4 bi = reinterpret_cast<const int4*>(bbox)[i];          // y0, x0, y1, x1
     if (bi.x < 0) return;
     const int li = label ? label[i] : 0;
-    const int wpr = (W + 31) >> 5;
-    const uint32_t* ma = a + (long)i * H * wpr;
+    const mwords::View vi = src.view(i);
     for (int j = i + 1 + wave; j < end; j += 4) {
         if (j - f >= ld) break;
         if (label && label[j] != li) continue;
         const int4 bj = reinterpret_cast<const int4*>(bbox)[j];
-        const int y0 = max(bi.x, bj.x), y1 = min(bi.z, bj.z), x0 = max(bi.y, bj.y), x1 = min(bi.w, bj.w);
-        if (bj.x < 0 || y0 > y1 || x0 > x1) continue;
-        const int wx0 = x0 >> 5, rw = (x1 >> 5) - wx0 + 1, rh = y1 - y0 + 1;
-        const uint32_t* mb = a + (long)j * H * wpr;
-        int c = 0;
-        for (int t = lane; t < rh * rw; t += 64) {
-            const long o = (long)(y0 + t / rw) * wpr + wx0 + t % rw;
-            c += __popc(ma[o] & mb[o]);
-        }
+        if (bj.x < 0 || max(bi.x, bj.x) > min(bi.z, bj.z) || max(bi.y, bj.y) > min(bi.w, bj.w)) continue;
+        int c = mwords::pair_count<8>(vi, bi, src.view(j), bj, lane, 64);
         for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
         if (lane == 0) out[(long)i * ld + (j - f)] = c;
     }
@@ -326,20 +316,7 @@ __global__ void place_tile_kernel(const uint32_t* __restrict__ src, uint32_t* __
         const int wx = (int)(i % wpr);
         const int y = (int)((i / wpr) % H);
         const int t = (int)(i / ((long)wpr * H));
-        const int ty = y - y_off[t];
-        uint32_t bits = 0u;
-        if (ty >= 0 && ty < tile_h) {
-            const int sy = min((int)floor((double)ty * (1.0 / ((double)tile_h / (double)sh))), sh - 1);
-            const uint32_t* srow = src + ((long)t * sh + sy) * swpr;
-            for (int bb = 0; bb < 32; ++bb) {
-                if (wx * 32 + bb >= W) break;                      // padding bits of the last word stay 0
-                const int tx = wx * 32 + bb - x_off[t];
-                if (tx < 0 || tx >= tile_w) continue;
-                const int sx = min((int)floor((double)tx * (1.0 / ((double)tile_w / (double)sw))), sw - 1);
-                bits |= ((srow[sx >> 5] >> (sx & 31)) & 1u) << bb;
-            }
-        }
-        dst[i] = bits;
+        dst[i] = mwords::placed_word(src + (long)t * sh * swpr, sh, sw, tile_h, tile_w, x_off[t], y_off[t], H, W, y, wx);
     }
 }
 
@@ -397,35 +374,43 @@ __global__ __launch_bounds__(256) void gather_regions_kernel(const uint32_t* __r
     }
 }
 
-// The same gather into a POOL of planes that are known to be zero outside `prev` (the box the previous use of the slot could
+// Masks -> the slots of a POOL of planes that are known to be zero outside `prev` (the box the previous use of the slot could
 // have set): only the union of the slot's old box and the new one is written -- a few hundred words instead of a 512-KiB
 // plane -- and `prev` becomes the new box grown by `grow` pixels (what the in-place stages that follow may still set: a
-// dilation reaches one pixel beyond its input).  One block per slot.
-__global__ __launch_bounds__(256) void gather_regions_pooled_kernel(const uint32_t* __restrict__ src, const long* __restrict__ index,
-                                                                    const int* __restrict__ bbox, uint32_t* __restrict__ dst,
-                                                                    int* __restrict__ prev, int H, int W, int grow) {
-    const int m = blockIdx.x;
+// dilation reaches one pixel beyond its input).  One block per slot; slot s receives mask s of `src` (the index[s]-th plane,
+// or mask first + s of a crop-framed set: the launcher shifts the set's tables).  bbox[s] is the mask's box, tight for a crop
+// (its words are zero outside it); words are read only inside the box AND the mask's view.
+template <class S>
+__global__ __launch_bounds__(256) void gather_pooled_kernel(const S src, const int* __restrict__ bbox, uint32_t* __restrict__ pool,
+                                                            int* __restrict__ prev, int H, int W, int grow) {
+    const int s = blockIdx.x;
     const int wpr = (W + 31) >> 5;
-    const int4 nb = reinterpret_cast<const int4*>(bbox)[m];       // y0, x0, y1, x1 (inclusive), -1: empty
-    const int4 pb = reinterpret_cast<const int4*>(prev)[m];
+    int4 nb = reinterpret_cast<const int4*>(bbox)[s];             // y0, x0, y1, x1 (inclusive), -1: empty
+    const int4 pb = reinterpret_cast<const int4*>(prev)[s];
     __syncthreads();                                              // every thread has read prev before thread 0 rewrites it
-    const bool has_n = nb.x >= 0, has_p = pb.x >= 0;
+    const mwords::View v = src.view(s);
+    bool has_n = nb.x >= 0 && v.rows > 0;
+    if (has_n) {                                                  // a box never leaves the frame (nor a plane its pool)
+        nb = make_int4(max(nb.x, 0), max(nb.y, 0), min(nb.z, H - 1), min(nb.w, W - 1));
+        has_n = nb.x <= nb.z && nb.y <= nb.w;
+    }
+    const bool has_p = pb.x >= 0 && pb.x <= pb.z && pb.z < H && pb.y >= 0 && pb.y <= pb.w && pb.w < W;
     if (threadIdx.x == 0) {
-        int4 g = make_int4(-1, -1, -1, -1);
-        if (has_n) g = make_int4(max(nb.x - grow, 0), max(nb.y - grow, 0), min(nb.z + grow, H - 1), min(nb.w + grow, W - 1));
-        reinterpret_cast<int4*>(prev)[m] = g;
+        int4 q = make_int4(-1, -1, -1, -1);
+        if (has_n) q = make_int4(max(nb.x - grow, 0), max(nb.y - grow, 0), min(nb.z + grow, H - 1), min(nb.w + grow, W - 1));
+        reinterpret_cast<int4*>(prev)[s] = q;
     }
     if (!has_n && !has_p) return;
     const int ry0 = min(has_n ? nb.x : 1 << 30, has_p ? pb.x : 1 << 30), ry1 = max(has_n ? nb.z : -1, has_p ? pb.z : -1);
     const int c0 = min(has_n ? nb.y >> 5 : 1 << 30, has_p ? pb.y >> 5 : 1 << 30), c1 = max(has_n ? nb.w >> 5 : -1, has_p ? pb.w >> 5 : -1);
     const int nc0 = nb.y >> 5, nc1 = nb.w >> 5;
-    const uint32_t* sp = src + index[m] * (long)H * wpr;
-    uint32_t* dp = dst + (long)m * H * wpr;
+    uint32_t* dp = pool + (long)s * H * wpr;
     const int cols = c1 - c0 + 1, rows = ry1 - ry0 + 1;
-    for (int t = threadIdx.x; t < rows * cols; t += blockDim.x) {
+    for (int t = threadIdx.x; t < rows * cols; t += 256) {
         const int ry = ry0 + t / cols, cx = c0 + t % cols;
-        const bool in = has_n && ry >= nb.x && ry <= nb.z && cx >= nc0 && cx <= nc1;
-        dp[(long)ry * wpr + cx] = in ? sp[(long)ry * wpr + cx] : 0u;
+        const int ly = ry - v.y0, lx = cx - v.c0;
+        const bool in = has_n && ry >= nb.x && ry <= nb.z && cx >= nc0 && cx <= nc1 && ly >= 0 && ly < v.rows && lx >= 0 && lx < v.cols;
+        dp[(long)ry * wpr + cx] = in ? v.p[(long)ly * v.cols + lx] : 0u;
     }
 }
 
@@ -436,28 +421,31 @@ inline int grid_for(long total, int block) {
 
 // 256-bin histogram of the gray image under one mask (measurements.py:197-205: cv2.cvtColor(BGR2GRAY) then
 // np.histogram(gray[mask > 0], bins=256, range=(0, 255)): with integer data bin i holds the pixels of value i).
-// One workgroup per mask over its bbox words; BGR -> gray is OpenCV's 8-bit fixed point (B 1868, G 9617, R 4899, >> 14).
-__global__ __launch_bounds__(256) void gray_hist_kernel(const uint32_t* __restrict__ masks, const int* __restrict__ bbox,
-                                                        const uint8_t* __restrict__ img, int channels, int H, int W,
-                                                        int* __restrict__ hist) {
+// One workgroup per mask over the words of its box that lie in its view; bits beyond column W - 1 are masked off before they
+// index the image.  BGR -> gray is OpenCV's 8-bit fixed point (B 1868, G 9617, R 4899, >> 14).
+template <class S>
+__global__ __launch_bounds__(256) void gray_hist_kernel(const S src, const int* __restrict__ bbox, const uint8_t* __restrict__ img,
+                                                        int channels, int H, int W, int* __restrict__ hist) {
     __shared__ int s_h[256];
     const long m = blockIdx.x;
-    const int wpr = (W + 31) >> 5;
     s_h[threadIdx.x] = 0;
     __syncthreads();
-    const int y0 = bbox[m * 4 + 0], x0 = bbox[m * 4 + 1], y1 = bbox[m * 4 + 2], x1 = bbox[m * 4 + 3];
-    if (y0 >= 0) {
-        const int ry0 = max(y0, 0), rh = min(y1, H - 1) - ry0 + 1;
-        const int wx0 = max(x0, 0) >> 5, rw = (min(x1, W - 1) >> 5) - wx0 + 1;
-        const uint32_t* src = masks + m * (long)H * wpr;
-        for (int i = threadIdx.x; i < rh * rw; i += blockDim.x) {
+    const int4 b4 = reinterpret_cast<const int4*>(bbox)[m];       // y0, x0, y1, x1
+    const mwords::View v = src.view(m);
+    if (b4.x >= 0 && v.rows > 0) {
+        const int ry0 = max(max(b4.x, 0), v.y0), ry1 = min(min(b4.z, H - 1), v.y0 + v.rows - 1);
+        const int wx0 = max(max(b4.y, 0) >> 5, v.c0), wx1 = min(min(b4.w, W - 1) >> 5, v.c0 + v.cols - 1);
+        const int rh = ry1 - ry0 + 1, rw = wx1 - wx0 + 1;
+        const int last = (W - 1) >> 5;
+        for (int i = threadIdx.x; i < rh * rw && rw > 0; i += 256) {
             const int ly = i / rw, lx = i - ly * rw;
-            const int y = ry0 + ly;
-            uint32_t b = src[(long)y * wpr + wx0 + lx];
+            const int y = ry0 + ly, wx = wx0 + lx;
+            uint32_t b = v.p[(long)(y - v.y0) * v.cols + (wx - v.c0)];
+            if (wx == last && (W & 31)) b &= (1u << (W & 31)) - 1u;
             while (b) {
                 const int bit = __ffs((int)b) - 1;
                 b &= b - 1;
-                const long px = (long)y * W + ((wx0 + lx) << 5) + bit;
+                const long px = (long)y * W + (wx << 5) + bit;
                 int g;
                 if (channels == 3) {
                     const uint8_t* q = img + px * 3;
@@ -537,9 +525,24 @@ extern "C" int demia_mask_pair_intersections(const uint32_t* a, const uint32_t* 
                                              int H, int W, void* stream) {
     DEMIA_REQUIRE(a && b && pi && pj && bbox_a && bbox_b && out && W > 0, "args");
     if (P == 0) return DEMIA_OK;
-    hipLaunchKernelGGL(pair_intersections_kernel, dim3((int)P), dim3(256), 0, (hipStream_t)stream, a, b, pi, pj, bbox_a, bbox_b,
-                       out, H, W);
+    const int wpr = (W + 31) >> 5;
+    hipLaunchKernelGGL((pair_intersections_kernel<PlaneWords, PlaneWords>), dim3((int)P), dim3(256), 0, (hipStream_t)stream,
+                       PlaneWords{a, H, wpr, nullptr}, bbox_a, PlaneWords{b, H, wpr, nullptr}, bbox_b, pi, pj, out);
     DEMIA_CHECK_LAUNCH("pair_intersections_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_pair_intersections(const uint32_t* payload_a, const int32_t* room_a, const int64_t* offsets_a, const int32_t* bbox_a,
+                                             const uint32_t* payload_b, const int32_t* room_b, const int64_t* offsets_b, const int32_t* bbox_b,
+                                             const int32_t* pi, const int32_t* pj, int32_t* out, int64_t P, void* stream) {
+    DEMIA_REQUIRE(P >= 0, "P");
+    if (P == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(payload_a && room_a && offsets_a && bbox_a && payload_b && room_b && offsets_b && bbox_b && pi && pj && out, "args");
+    DEMIA_REQUIRE(P <= 0x7fffffffL, "P");
+    hipLaunchKernelGGL((pair_intersections_kernel<CropWords, CropWords>), dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream,
+                       CropWords{payload_a, room_a, reinterpret_cast<const long*>(offsets_a)}, bbox_a,
+                       CropWords{payload_b, room_b, reinterpret_cast<const long*>(offsets_b)}, bbox_b, pi, pj, out);
+    DEMIA_CHECK_LAUNCH("pair_intersections_kernel<crop>");
     return DEMIA_OK;
 }
 
@@ -548,9 +551,22 @@ extern "C" int demia_mask_pair_matrix(const uint32_t* masks, const int32_t* bbox
     DEMIA_REQUIRE(masks && bbox && first && count && out && W > 0 && ld > 0, "args");
     if (M == 0) return DEMIA_OK;
     DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
-    hipLaunchKernelGGL(pair_matrix_kernel, dim3((int)M), dim3(256), 0, (hipStream_t)stream, masks, bbox, first, count, label, out, ld,
-                       H, W);
+    hipLaunchKernelGGL(pair_matrix_kernel<PlaneWords>, dim3((int)M), dim3(256), 0, (hipStream_t)stream,
+                       PlaneWords{masks, H, (W + 31) >> 5, nullptr}, bbox, first, count, label, out, ld);
     DEMIA_CHECK_LAUNCH("pair_matrix_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_pair_matrix(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                                      const int32_t* first, const int32_t* count, const int32_t* label, int32_t* out, int64_t M, int ld,
+                                      void* stream) {
+    DEMIA_REQUIRE(M >= 0 && ld > 0, "shapes");
+    if (M == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(payload && room && offsets && bbox && first && count && out, "args");
+    DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
+    hipLaunchKernelGGL(pair_matrix_kernel<CropWords>, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream,
+                       CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, bbox, first, count, label, out, ld);
+    DEMIA_CHECK_LAUNCH("pair_matrix_kernel<crop>");
     return DEMIA_OK;
 }
 
@@ -607,9 +623,23 @@ extern "C" int demia_mask_gather_regions_pooled(const uint32_t* src, const int64
     DEMIA_REQUIRE(src && index && bbox && pool && prev && W > 0 && H > 0 && grow >= 0, "args");
     if (M == 0) return DEMIA_OK;
     DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
-    hipLaunchKernelGGL(gather_regions_pooled_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, src,
-                       reinterpret_cast<const long*>(index), bbox, pool, prev, H, W, grow);
-    DEMIA_CHECK_LAUNCH("gather_regions_pooled_kernel");
+    hipLaunchKernelGGL(gather_pooled_kernel<PlaneWords>, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream,
+                       PlaneWords{src, H, (W + 31) >> 5, reinterpret_cast<const long*>(index)}, bbox, pool, prev, H, W, grow);
+    DEMIA_CHECK_LAUNCH("gather_pooled_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_unpack_pooled(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                                        int64_t first, int64_t n, int H, int W, uint32_t* pool, int32_t* prev, int grow, void* stream) {
+    DEMIA_REQUIRE(first >= 0 && n >= 0 && W > 0 && H > 0 && grow >= 0, "shapes");
+    if (n == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(payload && room && offsets && bbox && pool && prev, "args");
+    DEMIA_REQUIRE(n <= 0x7fffffffL, "n");
+    // slot s takes mask first + s: the set's per-mask tables start at `first`
+    hipLaunchKernelGGL(gather_pooled_kernel<CropWords>, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                       CropWords{payload, room + 4 * first, reinterpret_cast<const long*>(offsets) + first}, bbox + 4 * first, pool, prev, H,
+                       W, grow);
+    DEMIA_CHECK_LAUNCH("gather_pooled_kernel<crop>");
     return DEMIA_OK;
 }
 
@@ -617,7 +647,20 @@ extern "C" int demia_mask_gray_histogram(const uint32_t* masks, const int32_t* b
                                          int64_t M, int H, int W, int32_t* hist, void* stream) {
     DEMIA_REQUIRE(masks && bbox && image && hist && W > 0 && (channels == 1 || channels == 3), "args");
     if (M == 0) return DEMIA_OK;
-    hipLaunchKernelGGL(gray_hist_kernel, dim3((int)M), dim3(256), 0, (hipStream_t)stream, masks, bbox, image, channels, H, W, hist);
+    hipLaunchKernelGGL(gray_hist_kernel<PlaneWords>, dim3((int)M), dim3(256), 0, (hipStream_t)stream,
+                       PlaneWords{masks, H, (W + 31) >> 5, nullptr}, bbox, image, channels, H, W, hist);
     DEMIA_CHECK_LAUNCH("gray_hist_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_gray_histogram(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                                         const uint8_t* image, int channels, int64_t M, int H, int W, int32_t* hist, void* stream) {
+    DEMIA_REQUIRE(M >= 0 && W > 0 && H > 0 && (channels == 1 || channels == 3), "shapes");
+    if (M == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(payload && room && offsets && bbox && image && hist, "args");
+    DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
+    hipLaunchKernelGGL(gray_hist_kernel<CropWords>, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream,
+                       CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, bbox, image, channels, H, W, hist);
+    DEMIA_CHECK_LAUNCH("gray_hist_kernel<crop>");
     return DEMIA_OK;
 }

@@ -682,7 +682,8 @@ class InferencePipeline:
             area_d, bbox_d = ops.area_bbox(packed)
             cset = ops.trace(packed, max_contours=256, bbox=bbox_d, max_points=int(min(4096 * n + (1 << 16), 1 << 26)))
             I = ops.pair_matrix(packed, bbox_d, run_first, np.maximum(run_count, 1), None, ld)
-            cset, area, bbox, I_c = self._fetch_traced_tables(cset, packed, area_d, bbox_d, I, ld)
+            cset, area, bbox, I_c = self._fetch_traced_tables(
+                cset, lambda total: ops.trace(packed, max_contours=256, bbox=bbox_d, total_area=total), [area_d.to(torch.int32), bbox_d, I], n, ld)
             per0 = cset.first_contour_perimeter()
         ok = _not_artefact(area, bbox, per0)
         gls = _smart_dedup_keep(ops.lib, I_c, ld, run_first, area, bbox, [np.nonzero(ok[s0:s1])[0] + s0 for s0, s1 in segments],
@@ -714,23 +715,22 @@ class InferencePipeline:
             pos += k
         return out
 
-    def _fetch_traced_tables(self, cset, packed: torch.Tensor, area_d: torch.Tensor, bbox_d: torch.Tensor, I: torch.Tensor, ld: int):
+    def _fetch_traced_tables(self, cset, retrace, extra, n: int, ld: int):
         """THE wait of a smart-dedup stage whose trace was enqueued before the masks' areas were on the host (point pool sized
-        from the mask COUNT): the contour set's tables plus pixel counts, tight boxes and the pair matrix in one fetch.  A few
-        large ragged masks (boundaries of thousands of points) can overflow that pool; the areas are on the device by then, so
-        the masks are traced again with the area-sized pool ``MaskOps.trace`` defaults to and fetched again -- one more wait
-        for the areas, counted here.  Returns (contour set, area i64 [n], bbox i64 [n, 4], I i32 [n, ld])."""
-        extra = [area_d.to(torch.int32), bbox_d, I]
+        from the mask COUNT): the contour set's tables plus ``extra`` = [pixel counts i32 [n], tight boxes [n, 4], pair matrix
+        [n, ld]] in one fetch.  A few large ragged masks (boundaries of thousands of points) can overflow that pool; the areas
+        are on the device by then, so ``retrace(total_area)`` traces the masks again with the area-sized pool and they are
+        fetched again -- one more wait for the areas, counted here.  Returns (contour set, area i64 [n], bbox i64 [n, 4],
+        I i32 [n, ld])."""
         try:
             area_h, bbox_h, I_h = cset.fetch(extra=extra)
         except _L.HipKernelError as e:
             if "overflow" not in str(e):
                 raise
             self.d2h_waits += 1
-            cset = self.ops.trace(packed, max_contours=256, bbox=bbox_d, total_area=int(area_d.sum().item()))
+            cset = retrace(int(extra[0].sum().item()))
             area_h, bbox_h, I_h = cset.fetch(extra=extra)
         self.d2h_waits += 1
-        n = int(packed.shape[0])
         return (cset, np.ascontiguousarray(area_h, dtype=np.int64), np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64),
                 np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
 
@@ -744,20 +744,10 @@ class InferencePipeline:
         [n], bbox i64 [n, 4], I i32 [n, ld])."""
         n = len(cs)
         if self.crop_direct:
-            # one trace over all masks on the words in place, one fetch: the accounting of _fetch_traced_tables
-            extra = [cs.area, cs.bbox, I]
-            cset = cs.trace(max_contours=256)
-            try:
-                area_h, bbox_h, I_h = cset.fetch(extra=extra)
-            except _L.HipKernelError as e:
-                if "overflow" not in str(e):
-                    raise
-                self.d2h_waits += 1
-                cset = cs.trace(max_contours=256, total_area=int(cs.area.sum().item()))
-                area_h, bbox_h, I_h = cset.fetch(extra=extra)
-            self.d2h_waits += 1
-            return (cset.first_contour_perimeter(), np.ascontiguousarray(area_h, dtype=np.int64),
-                    np.ascontiguousarray(bbox_h.reshape(n, 4), dtype=np.int64), np.ascontiguousarray(I_h.reshape(n, ld), dtype=np.int32))
+            # one trace over all masks on the words in place, one fetch
+            cset, area, bbox, I_c = self._fetch_traced_tables(cs.trace(max_contours=256), lambda total: cs.trace(max_contours=256, total_area=total),
+                                                              [cs.area, cs.bbox, I], n, ld)
+            return cset.first_contour_perimeter(), area, bbox, I_c
         planes = crop_planes(self.ops, cs.hw)
         self._note_planes(planes.cap)
         per0, tabs = [], None
@@ -1815,7 +1805,9 @@ class InferencePipeline:
     def _ensemble_passes_finish(self, h: dict, class_thresholds, small_classes):
         T, ld = h["T"], h["ld"]
         # THE wait of the class passes
-        h["cset"], area, bbox, I = self._fetch_traced_tables(h["cset"], h["packed"], h["area"], h["bbox"], h["I"], ld)
+        h["cset"], area, bbox, I = self._fetch_traced_tables(
+            h["cset"], lambda total: self.ops.trace(h["packed"], max_contours=256, bbox=h["bbox"], total_area=total),
+            [h["area"].to(torch.int32), h["bbox"], h["I"]], h["n"], ld)
         not_artefact = _not_artefact(area, bbox, h["cset"].first_contour_perimeter())
         area_img = h["hw"][0] * h["hw"][1]
         scores, run_first = h["scores"], h["run_first"]

@@ -1,5 +1,6 @@
-"""Crop-framed mask sets (``deepemia_amd/cropset.py``, ``csrc/cropops.hip``) against the full-frame kernels they are the twins of:
-every comparison is ``torch.equal`` / byte equality -- the two frames hold the same bits, so nothing here has a tolerance.
+"""Crop-framed mask sets (``deepemia_amd/cropset.py``, ``csrc/cropops.hip``, ``csrc/maskwords.h``) against their full-frame forms:
+every comparison is ``torch.equal`` / byte equality -- the two frames hold the same bits, so nothing here has a tolerance.  Where
+both frames run ONE kernel over a word source (pair counts, gray histogram, pooled gather) a dense NumPy answer stands beside them.
 
 Boxes are (y0, x0, y1, x1) everywhere, as in the C ABI."""
 import json
@@ -142,7 +143,23 @@ def pair_env(ops):
     cs, area, bbox = _loose_set(ops, planes, W, 12)
     first = np.repeat(np.concatenate(([0], np.cumsum(SEGS)[:-1])), SEGS).astype(np.int32)
     count = np.repeat(SEGS, SEGS).astype(np.int32)
-    return dict(planes=planes, cs=cs, area=area, bbox=bbox, first=first, count=count, n=n)
+    return dict(planes=planes, cs=cs, area=area, bbox=bbox, first=first, count=count, n=n, G=_dense_counts(ops, planes, W))
+
+
+def _dense_counts(ops, planes, w):
+    """G[i, j] = |mask_i & mask_j| from the unpacked masks (every count is below 2^24, so the float32 product is exact)."""
+    D = ops.to_dense(planes, w).reshape(int(planes.shape[0]), -1).astype(np.float32)
+    return (D @ D.T).astype(np.int32)
+
+
+def _dense_pair_matrix(G, first, count, label, ld):
+    """The [n, ld] layout of ``pair_matrix`` from G: |i & j| at [i, j - first[i]] for j > i of i's segment with an equal label."""
+    want = np.zeros((len(first), ld), np.int32)
+    for i in range(len(first)):
+        for j in range(i + 1, int(first[i]) + int(count[i])):
+            if j - first[i] < ld and (label is None or label[i] == label[j]):
+                want[i, j - first[i]] = G[i, j]
+    return want
 
 
 @pytest.mark.parametrize("labels", ["none", "one_per_segment", "mixed"])
@@ -157,6 +174,7 @@ def test_pair_matrix_equals_plane_kernel(ops, pair_env, labels, ld):
     got = e["cs"].pair_matrix(e["first"], e["count"], label, ld)
     assert int((ref > 0).sum()) > 50                                             # the blobs do overlap (mixed labels count a third of the pairs)
     assert torch.equal(got, ref)
+    assert np.array_equal(ref.cpu().numpy(), _dense_pair_matrix(e["G"], e["first"], e["count"], label, ld))
 
 
 def test_pair_intersections_equal_plane_kernel(ops, pair_env):
@@ -170,10 +188,61 @@ def test_pair_intersections_equal_plane_kernel(ops, pair_env):
     ops.set_frame_width(W)
     ref_aa = ops.pair_intersections(e["planes"], e["planes"], e["bbox"], e["bbox"], pi, pj)
     assert np.array_equal(e["cs"].pair_intersections(e["cs"], pi, pj), ref_aa)
+    assert np.array_equal(ref_aa, e["G"][pi, pj])
     assert int(e["area"][2]) == 0 and ref_aa[-3] == 0 and ref_aa[400] == int(e["area"][0]) > 0
     bbox_b = e["bbox"][torch.from_numpy(perm).to(ops.device)].contiguous()
     ref_ab = ops.pair_intersections(e["planes"], planes_b, e["bbox"], bbox_b, pi, pj)
     assert np.array_equal(e["cs"].pair_intersections(other, pi, pj), ref_ab) and int(ref_ab.sum()) > 0
+    assert np.array_equal(ref_ab, e["G"][pi, perm[pj]])
+
+
+def test_long_windows_in_both_frames_against_dense_numpy(ops):
+    """The stages that are ONE kernel over a word source, on windows of every length: two nearly-full-frame masks (a shared window
+    of 96 x 7 words: ten trips per lane of the matrix kernel's wave and a remainder after any unroll factor), a full-width row,
+    a full-height column in the frame's partly used last word, the frame's last pixel and an empty mask -- from planes and
+    from a set with grown rooms, against dense NumPy and against each other."""
+    from deepemia_amd.maskset import PlanePool
+    g = np.random.default_rng(51)
+    dense = np.zeros((6, H, W), bool)
+    dense[0] = g.random((H, W)) < 0.9; dense[0, [0, -1], :] = True; dense[0, :, [0, -1]] = True
+    dense[1] = g.random((H, W)) < 0.8; dense[1, [0, -1], :] = True; dense[1, :, [0, -1]] = True
+    dense[2, 40, :] = True
+    dense[3, :, 197] = True
+    dense[4, H - 1, W - 1] = True
+    n = len(dense)
+    ops.set_frame_width(W)
+    planes = ops.from_dense(dense).contiguous()
+    cs, area, bbox = _loose_set(ops, planes, W, 52)
+    G = (dense.reshape(n, -1).astype(np.int32) @ dense.reshape(n, -1).T.astype(np.int32)).astype(np.int32)
+    assert np.array_equal(bbox.cpu().numpy()[:2], [[0, 0, H - 1, W - 1]] * 2) and G[0, 1] > 10000 and G[2, 3] == 1 and G[1, 4] == 1 and G[5].sum() == 0
+    # every pair of one segment, and every listed pair (i, j) in both orders
+    first, count = np.zeros(n, np.int32), np.full(n, n, np.int32)
+    want = _dense_pair_matrix(G, first, count, None, n)
+    assert np.array_equal(ops.pair_matrix(planes, bbox, first, count, None, n).cpu().numpy(), want)
+    assert np.array_equal(cs.pair_matrix(first, count, None, n).cpu().numpy(), want)
+    pi, pj = [a.ravel().astype(np.int64) for a in np.mgrid[0:n, 0:n]]
+    assert np.array_equal(ops.pair_intersections(planes, planes, bbox, bbox, pi, pj), G[pi, pj])
+    assert np.array_equal(cs.pair_intersections(cs, pi, pj), G[pi, pj])
+    # gray histogram: BGR through OpenCV's fixed point, and a gray image as it is
+    bgr = g.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    gray = ((bgr[..., 0].astype(np.int64) * 1868 + bgr[..., 1].astype(np.int64) * 9617 + bgr[..., 2].astype(np.int64) * 4899 + (1 << 13)) >> 14)
+    for img, lv in ((bgr, gray), (np.ascontiguousarray(bgr[..., 1]), bgr[..., 1])):
+        hist = np.stack([np.bincount(lv[d], minlength=256) for d in dense])
+        dev = torch.from_numpy(img).to(ops.device)
+        assert np.array_equal(ops.gray_histogram(planes, dev, bbox), hist) and np.array_equal(cs.gray_histogram(dev), hist)
+    # pooled gather, twice through the same slots: the second pass puts small boxes where large ones were
+    pool_p, pool_c = PlanePool(ops.device, H, (W + 31) // 32, n), PlanePool(ops.device, H, (W + 31) // 32, n)
+    bb = bbox.cpu().numpy()
+    for order in (np.arange(n), np.array([4, 5, 3, 0, 1, 2])):
+        it = torch.from_numpy(order).to(ops.device)
+        ops.gather_regions_pooled(planes, order, bb[order], pool_p, grow=1)
+        cs.select(order).unpack_pooled(pool_c, 0, n, grow=1)
+        grown = np.stack([np.maximum(bb[order, 0] - 1, 0), np.maximum(bb[order, 1] - 1, 0),
+                          np.minimum(bb[order, 2] + 1, H - 1), np.minimum(bb[order, 3] + 1, W - 1)], axis=1)
+        grown[bb[order, 0] < 0] = -1
+        for pool in (pool_p, pool_c):
+            assert np.array_equal(ops.to_dense(pool.planes, W), dense[order]) and torch.equal(pool.planes, planes[it])
+            assert np.array_equal(pool.prev.cpu().numpy(), grown)
 
 
 # ------------------------------------------------------------------------------------------------ gather / select / cat
