@@ -1,7 +1,8 @@
 """Crop-framed mask sets: instance masks kept in the GLOBAL frame as (room, cropped packed words) instead of full-frame
 planes ``[M, H, W/32]`` -- the representation of the instance tables (``demia_mask_crop_pack``, ``parallel.py``) with the HIP
 kernels that COMPUTE on it (``csrc/cropops.hip``; the reading stages are ``csrc/maskops.hip``'s own kernels over
-``mwords::CropWords``): tile placement, gather, pair counts, the contour trace and the gray
+``mwords::CropWords``): tile placement, gather, the move to other rooms (``reroom``: how a set becomes an instance table,
+``to_table``, and a gathered table a set again, ``from_table`` -- the exchange of the ranks without a plane), pair counts, the contour trace and the gray
 histogram on the words in place (``CropMaskSet.trace`` / ``contours`` / ``gray_histogram``: ``mask_frame: crop_direct``), and the
 chunked way back to planes for the plane kernels (``trace_chunks`` / ``crop_contours`` / ``crop_gray_histogram``: ``mask_frame: crop``).
 
@@ -16,6 +17,7 @@ import torch
 
 from . import _lib
 from .maskset import _WORKLISTS, ContourSet, MaskOps, PlanePool
+from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
 
@@ -220,6 +222,87 @@ class CropMaskSet:
             _lib.check(ops.lib.demia_crop_gather(_lib.ptr(s.payload), _lib.ptr(s.offsets), _lib.ptr(idx), _lib.ptr(out.room[pos:pos + k]),
                                                  _lib.ptr(out.offsets[pos:pos + k]), k, _lib.ptr(out.payload), ops._stream()), "demia_crop_gather")
             pos += k
+        return out
+
+    # -- other rooms, instance tables ----------------------------------------------------------------------------------
+    def reroom(self, room_h: np.ndarray) -> "CropMaskSet":
+        """The same masks stored for the rooms ``room_h`` [M, 4] (``demia_crop_reroom``, one launch): words of a new room that lie
+        in the old one are copied, the others are zero -- the same masks wherever the new room contains the tight box."""
+        room_h = np.ascontiguousarray(room_h, dtype=np.int32).reshape(-1, 4)
+        assert room_h.shape[0] == len(self)
+        out = CropMaskSet(self.ops, self.hw, room_h, None, self.bbox, self.area)
+        out.payload = self._payload(self.ops, out.words)
+        if out.words:
+            _lib.check(self.ops.lib.demia_crop_reroom(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), 0, _lib.ptr(out.room),
+                                                      _lib.ptr(out.offsets), len(self), int(room_lengths(room_h).max()), _lib.ptr(out.payload),
+                                                      self.ops._stream()), "demia_crop_reroom")
+        return out
+
+    def tighten(self, bbox_h: np.ndarray) -> "CropMaskSet":
+        """:meth:`reroom` to the tight boxes ``bbox_h`` the caller has on the host; ``self`` when the rooms already are the boxes
+        (tiles that were not upscaled: the placement's rooms are exact)."""
+        bbox_h = np.asarray(bbox_h, dtype=np.int32).reshape(-1, 4)
+        return self if np.array_equal(self.room_h, bbox_h) else self.reroom(bbox_h)
+
+    def to_table(self, scores: Sequence[float], classes: Sequence[int], unit_ids: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The instance table of this set, ``(header [n, 10] i32, payload i32)`` on the device -- bit for bit what
+        ``parallel.encode_instance_table`` makes of the same masks' planes, without a plane: the payload is the tightened set's
+        words.  ONE device-to-host wait: the tight boxes and pixel counts, in a single copy."""
+        n = len(self)
+        hdr = np.zeros((n, HDR), dtype=np.int32)
+        if n == 0:
+            return torch.from_numpy(hdr).to(self.ops.device), torch.zeros((0,), dtype=torch.int32, device=self.ops.device)
+        tab = torch.cat([self.bbox.reshape(-1), self.area]).cpu().numpy()
+        hdr[:, 0] = np.asarray(unit_ids, dtype=np.int32)
+        hdr[:, 1] = np.asarray(classes, dtype=np.int32)
+        hdr[:, 2:4] = np.asarray(scores, dtype=np.float64).reshape(n, 1).view(np.int32)
+        hdr[:, 4:8] = tab[:4 * n].reshape(n, 4)
+        hdr[:, 8] = tab[4 * n:]
+        tight = self.tighten(hdr[:, 4:8])
+        return self.ops.upload(hdr), tight.payload[:tight.words]
+
+    @staticmethod
+    def table_layout(host_header: np.ndarray, offsets: Optional[np.ndarray] = None, rows: Optional[np.ndarray] = None):
+        """Host arithmetic of :meth:`from_table`: (rows [k] i64, every header row's first word in the exchange buffer [n] i64, the
+        words of every header row [n] i64).  Rows with box -1 (empty masks, the N4 marker) have no words."""
+        hdr = np.asarray(host_header, dtype=np.int32).reshape(-1, HDR)
+        lens = room_lengths(hdr[:, 4:8])
+        if offsets is None:
+            src_off = np.zeros(len(lens), dtype=np.int64)
+            if len(lens):
+                np.cumsum(lens[:-1], out=src_off[1:])
+        else:
+            src_off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        assert len(src_off) == len(lens)
+        rows = np.arange(len(lens), dtype=np.int64) if rows is None else np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        return rows, src_off, lens
+
+    @classmethod
+    def from_table(cls, ops: MaskOps, hw: Tuple[int, int], host_header: np.ndarray, payload: torch.Tensor, offsets: Optional[np.ndarray] = None,
+                   rows: Optional[np.ndarray] = None) -> "CropMaskSet":
+        """The set of the rows ``rows`` (default: all, in order) of an instance table whose header is on the host
+        (``GlobalTable.host_header``): rooms, boxes and pixel counts are the header's, the words come out of the exchange buffer
+        ``payload`` where ``offsets`` (``GlobalTable.offsets``; default: back to back in header order) says they are -- one
+        ``demia_crop_reroom`` with the rows as its index, no plane and no wait."""
+        hdr = np.asarray(host_header, dtype=np.int32).reshape(-1, HDR)
+        rows, src_off, lens = cls.table_layout(hdr, offsets, rows)
+        k = len(rows)
+        if k == 0:
+            return cls.empty(ops, hw)
+        n = hdr.shape[0]
+        assert payload.dtype == torch.int32 and payload.is_contiguous() and payload.is_cuda
+        # (the kernel reads what these tables say: every listed row's words must lie inside the buffer)
+        assert rows.min() >= 0 and rows.max() < n and src_off.min() >= 0 and int((src_off + lens).max()) <= payload.numel()
+        tab = ops.upload(np.concatenate([hdr[:, 4:8].reshape(-1), src_off.view(np.int32), rows.view(np.int32), hdr[rows, 8]]))     # one copy
+        src_room_d, src_off_d = tab[:4 * n].view(n, 4), tab[4 * n:6 * n].view(torch.int64)
+        rows_d, area_d = tab[6 * n:6 * n + 2 * k].view(torch.int64), tab[6 * n + 2 * k:]
+        out = cls(ops, hw, hdr[rows, 4:8], None, None, area_d)
+        out.bbox = out.room                                                       # (a table's rooms ARE the tight boxes)
+        out.payload = cls._payload(ops, out.words)
+        if out.words:
+            _lib.check(ops.lib.demia_crop_reroom(_lib.ptr(payload), _lib.ptr(src_room_d), _lib.ptr(src_off_d), _lib.ptr(rows_d), _lib.ptr(out.room),
+                                                 _lib.ptr(out.offsets), k, int(lens[rows].max()), _lib.ptr(out.payload), ops._stream()),
+                       "demia_crop_reroom")
         return out
 
     def host_crops(self):

@@ -7,7 +7,7 @@
 // Bit (x & 31) of word (x >> 5), as in the planes: two sets over one frame share the word alignment, so |a & b| needs
 // no shifts.  bbox[m] is the TIGHT box (inside the room); bits outside it and beyond column W - 1 are zero.
 //
-// Here: what exists only for crops -- placing tile masks into rooms, and moving rooms between sets.  The stages that only READ
+// Here: what exists only for crops -- placing tile masks into rooms, moving rooms between sets, and storing a mask for another room.  The stages that only READ
 // a set (pair counts, gray histogram, pooled unpack) are the plane kernels of maskops.hip instantiated for
 // mwords::CropWords (maskwords.h), the contour trace is contours.hip's CropContourP.
 #include "common.h"
@@ -77,6 +77,31 @@ __global__ __launch_bounds__(256) void crop_gather_kernel(const uint32_t* __rest
     for (int t = threadIdx.x; t < g.rows * g.cols; t += 256) d[t] = s[t];
 }
 
+// ---- dst[i] = src[index[i]] stored for ANOTHER room: both rooms lie on the global word grid, so a destination word inside the
+// source room is that source word and every other one is zero -- a dword copy with a stride change, no shifts.  The grid is
+// masks x slabs of REROOM_SLAB destination words (a frame-filling 8192^2 mask is 2 M words: not one workgroup's job); a slab
+// past the end of its mask's room has nothing to do.  Writes dst[dst_off[i] .. + rows * cols) and nothing else.
+constexpr int REROOM_SLAB = 256 * 16;
+
+__global__ __launch_bounds__(256) void crop_reroom_kernel(const uint32_t* __restrict__ src, const int* __restrict__ src_room,
+                                                          const long* __restrict__ src_off, const long* __restrict__ index,
+                                                          const int* __restrict__ dst_room, const long* __restrict__ dst_off,
+                                                          uint32_t* __restrict__ dst) {
+    const long i = blockIdx.x;
+    const mwords::View d = CropWords{dst, dst_room, dst_off}.view(i);
+    const int n = d.rows * d.cols;
+    const int t0 = (int)blockIdx.y * REROOM_SLAB;
+    if (t0 >= n) return;
+    const mwords::View s = CropWords{src, src_room, src_off}.view(index ? index[i] : i);
+    uint32_t* out = dst + dst_off[i];
+    const int t1 = min(n, t0 + REROOM_SLAB);
+    for (int t = t0 + threadIdx.x; t < t1; t += 256) {
+        const int ly = t / d.cols, lx = t - ly * d.cols;
+        const int sy = d.y0 + ly - s.y0, sx = d.c0 + lx - s.c0;
+        out[t] = (sy >= 0 && sy < s.rows && sx >= 0 && sx < s.cols) ? s.p[(long)sy * s.cols + sx] : 0u;
+    }
+}
+
 }  // namespace
 
 extern "C" int demia_crop_place_tiles(const uint32_t* src, const int32_t* x_off, const int32_t* y_off, int64_t M, int src_h, int src_w,
@@ -102,5 +127,22 @@ extern "C" int demia_crop_gather(const uint32_t* src, const int64_t* src_offsets
                        reinterpret_cast<const long*>(src_offsets), reinterpret_cast<const long*>(index), dst_room,
                        reinterpret_cast<const long*>(dst_offsets), dst);
     DEMIA_CHECK_LAUNCH("crop_gather_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_crop_reroom(const uint32_t* src, const int32_t* src_room, const int64_t* src_offsets, const int64_t* index,
+                                 const int32_t* dst_room, const int64_t* dst_offsets, int64_t M, int64_t max_dst_words, uint32_t* dst,
+                                 void* stream) {
+    DEMIA_REQUIRE(M >= 0 && max_dst_words >= 0, "M");
+    if (M == 0 || max_dst_words == 0) return DEMIA_OK;
+    DEMIA_REQUIRE(src && src_room && src_offsets && dst_room && dst_offsets && dst, "args");
+    DEMIA_REQUIRE(src != dst, "src and dst must not alias");
+    DEMIA_REQUIRE(M <= 0x7fffffffL, "M");
+    const long slabs = (max_dst_words + REROOM_SLAB - 1) / REROOM_SLAB;
+    DEMIA_REQUIRE(slabs <= 65535, "max_dst_words");
+    hipLaunchKernelGGL(crop_reroom_kernel, dim3((unsigned)M, (unsigned)slabs), dim3(256), 0, (hipStream_t)stream, src, src_room,
+                       reinterpret_cast<const long*>(src_offsets), reinterpret_cast<const long*>(index), dst_room,
+                       reinterpret_cast<const long*>(dst_offsets), dst);
+    DEMIA_CHECK_LAUNCH("crop_reroom_kernel");
     return DEMIA_OK;
 }

@@ -308,6 +308,23 @@ def mask_frame_setting(inf_settings: dict) -> str:
     return frame
 
 
+RANK_EXCHANGES = ("planes", "crops")
+
+
+def rank_exchange_setting(inf_settings: dict) -> str:
+    """``inference_settings.rank_exchange`` (per dataset): what the merge after the ranks' exchange of instance tables
+    (``gather_and_merge``) works on.  ``planes`` (the default) unpacks the gathered table to full-frame planes and therefore runs
+    with ``mask_frame: full`` only; ``crops`` builds a :class:`CropMaskSet` from the table's words and needs ``mask_frame: crop`` or
+    ``crop_direct`` -- with it a crop frame runs at any world size.  An unknown value, and ``crops`` with ``mask_frame: full``, are
+    configuration errors."""
+    ex = str((inf_settings or {}).get("rank_exchange", "planes"))
+    if ex not in RANK_EXCHANGES:
+        raise ValueError(f"inference_settings.rank_exchange must be 'planes' or 'crops', got {ex!r}")
+    if ex == "crops" and mask_frame_setting(inf_settings) == "full":
+        raise ValueError("inference_settings.rank_exchange: crops needs mask_frame: crop or crop_direct (mask_frame: full exchanges planes)")
+    return ex
+
+
 class EmptyEnsembleTypeError(ValueError):
     """Reference behaviour N4: ``np.array([]) + [masks...]`` raises and the image is skipped."""
 
@@ -348,6 +365,7 @@ class InferencePipeline:
         # opt-in: the stages after the tile -> global mapping on crop-framed mask sets instead of full-frame planes (same decisions,
         # same files)
         self.mask_frame = mask_frame_setting(inf_settings)
+        self.rank_exchange = rank_exchange_setting(inf_settings)     # what the merge after the ranks' exchange works on
         self.last_image_stats = None             # {"mask_frame", "full_frame_planes_peak", "plane_pool_capacity"} of the image finished last
         if self.merge_mode == "soft_nms":
             system_logger.warning("merge_mode: soft_nms -- NON-PARITY mode: the reference has no soft-NMS (hard greedy dedup only)")
@@ -377,9 +395,10 @@ class InferencePipeline:
         self.rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.exchange = parallel.ExchangeState()     # this job's agreed capacities: every rank builds its pipeline at the same point
-        if self.crop and self.world > 1:
+        if self.crop and self.world > 1 and self.rank_exchange != "crops":
             raise ValueError(f"inference_settings.mask_frame: {self.mask_frame} runs in one process only (WORLD_SIZE = "
-                             f"{self.world}): the gathered instance tables are unpacked to full-frame planes; use mask_frame: full")
+                             f"{self.world}): the gathered instance tables are unpacked to full-frame planes; use mask_frame: full, "
+                             f"or rank_exchange: crops (the merge after the exchange then stays on the cropped words)")
 
     @property
     def crop(self) -> bool:
@@ -1154,7 +1173,11 @@ class InferencePipeline:
 
         ``status`` != 0: this rank's local passes of the image FAILED (its ``locals_by_class`` is empty).  It still takes part
         in the exchange, and every rank -- the failed one included -- raises :class:`PeerImageFailure` right after it, so the
-        image is skipped by all ranks together and the next image's exchange finds every rank at the same collective."""
+        image is skipped by all ranks together and the next image's exchange finds every rank at the same collective.
+
+        ``rank_exchange: crops``: the same contract on crop-framed sets, without a plane (:meth:`_gather_and_merge_crops`)."""
+        if self.rank_exchange == "crops":
+            return self._gather_and_merge_crops(locals_by_class, hw, ensemble_by_class, status)
         h, w = hw
         hdrs, pays = [], []
         try:
@@ -1207,6 +1230,81 @@ class InferencePipeline:
             if not ensemble_by_class.get(cls, False):
                 sc = [np.float32(v) for v in sc]      # single-model scores are the predictor's float32 values
             out[cls] = self.deduplicate_masks_smart(packed_all[sel].contiguous(), sc, [cls] * len(rows), 0.4)
+        return out
+
+    @staticmethod
+    def _crop_table(cset: CropMaskSet, scores, classes, unit_ids):      # (a seam like _encode_table, for the crop branch)
+        return cset.to_table(scores, classes, unit_ids)
+
+    def _gather_and_merge_crops(self, locals_by_class: Dict[int, tuple], hw: Tuple[int, int], ensemble_by_class: Dict[int, bool], status: int = 0):
+        """:meth:`gather_and_merge` under ``rank_exchange: crops``: the same table, the same exchange and the same decisions with no
+        full-frame plane on either side of it.  This rank's parts are ONE :class:`CropMaskSet` whose table is its own tightened
+        words (``CropMaskSet.to_table``: one wait, for the boxes of all classes); the gathered table becomes ONE set straight from
+        the exchange buffer (``CropMaskSet.from_table``, rows class-major, the global order kept inside a class), and the per-class
+        0.4 merges are the segments of one ``deduplicate_masks_smart_segments`` call.  Three device-to-host waits -- table, exchange,
+        merge -- however many instances or classes.  Returns {class: (CropMaskSet | None, scores, classes)}."""
+        hdrs, sets, sc, cl, un = [], [], [], [], []
+        try:
+            for cls, (fm, fs, fc, tm, ts, tc, tu) in (locals_by_class.items() if status == 0 else ()):
+                empty_full = isinstance(fm, str)
+                parts = ([fm] if (fm is not None and not empty_full and fm.shape[0]) else []) + [t for t in tm if t.shape[0]]
+                sc_c = ([] if (fm is None or empty_full) else list(fs)) + list(ts)
+                if self.rank == 0 and empty_full:   # N4 marker travels too: unit -1 row of this class, no payload
+                    mark = torch.zeros((1, parallel.HDR), dtype=torch.int32, device=self.dev)
+                    mark[0, 0] = -1
+                    mark[0, 1] = cls
+                    mark[0, 4:8] = -1
+                    hdrs.append(mark)
+                if parts:
+                    sets += parts
+                    sc += sc_c
+                    cl += [cls] * len(sc_c)
+                    un += [0] * (len(sc_c) - len(ts)) + list(tu)
+            pay = torch.zeros((0,), dtype=torch.int32, device=self.dev)
+            if sets:
+                # (a marker row may stand before its class's rows or after another class's: the merged table is ordered by unit
+                # id, and the rows are picked per class below -- only the order inside a class counts)
+                hdr, pay = self._crop_table(CropMaskSet.cat(sets), sc, cl, un)
+                self.d2h_waits += 1
+                hdrs.append(hdr)
+            hdr = torch.cat(hdrs, dim=0) if hdrs else torch.zeros((0, parallel.HDR), dtype=torch.int32, device=self.dev)
+        except Exception as e:
+            system_logger.error(f"Rank {self.rank}: building the instance table of an image failed: {e}", exc_info=True)
+            status = 1
+            hdr = torch.zeros((0, parallel.HDR), dtype=torch.int32, device=self.dev)
+            pay = torch.zeros((0,), dtype=torch.int32, device=self.dev)
+        gt = parallel.all_gather_instance_tables(hdr, pay, status=status, state=self.exchange)
+        self.d2h_waits += 1
+        if bool((gt.status != 0).any()):
+            raise PeerImageFailure(f"local passes failed on rank(s) {np.nonzero(gt.status)[0].tolist()}: every rank skips this image")
+        hn = gt.host_header
+        s_all = np.ascontiguousarray(hn[:, 2:4]).view(np.float64).reshape(-1) if hn.shape[0] else np.zeros((0,), dtype=np.float64)
+        c_arr, u_arr = hn[:, 1].astype(np.int64), hn[:, 0].astype(np.int64)
+        out, todo, rows_all, scores, classes, segments = {}, [], [], [], [], []
+        for cls in locals_by_class:
+            rows = np.nonzero(c_arr == cls)[0]
+            marker = rows[u_arr[rows] == -1]
+            rows = rows[u_arr[rows] != -1]
+            if len(marker):
+                out[cls] = (EmptyEnsembleTypeError("operands could not be broadcast together (empty ensemble result + tile masks)")
+                            if len(rows) else (None, [], []))
+                continue
+            out[cls] = (None, [], [])
+            if len(rows) == 0:
+                continue
+            sc_c = s_all[rows].tolist()
+            if not ensemble_by_class.get(cls, False):
+                sc_c = [np.float32(v) for v in sc_c]      # single-model scores are the predictor's float32 values
+            segments.append((len(scores), len(scores) + len(rows)))
+            todo.append(cls)
+            rows_all.append(rows)
+            scores += sc_c
+            classes += [cls] * len(rows)
+        if todo:
+            self.ops.set_frame_width(int(hw[1]))
+            cset = CropMaskSet.from_table(self.ops, hw, hn, gt.payload.contiguous(), offsets=gt.offsets, rows=np.concatenate(rows_all))
+            for cls, m in zip(todo, self.deduplicate_masks_smart_segments(cset, scores, classes, segments, 0.4)):
+                out[cls] = m[:3]
         return out
 
     def tile_pipeline_all_classes(self, image_key: str, image_dev: torch.Tensor, class_params: Dict[int, Tuple[float, float]], small_classes,
@@ -2007,6 +2105,7 @@ class PipelineSettings:
         self.ensemble_small_only = ens.get("small_classes_only", gens.get("small_classes_only", True))
         self.classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
         self.mask_frame = mask_frame_setting(inf)
+        self.rank_exchange = rank_exchange_setting(inf)
 
     def target_classes(self, num_classes: int) -> List[int]:
         return list(range(num_classes) if self.classes_to_infer is None else [c for c in self.classes_to_infer if c < num_classes])
@@ -2358,6 +2457,8 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                                                     crop_direct=pipe.crop_direct)
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
+            elif n_final and pipe.crop:
+                texts = rle_text_from_payload(packed.payload[:packed.words].cpu().numpy(), packed.room_h, packed.offsets_h, int(packed.shape[1]))
             elif n_final:
                 texts = rle_text_packed(pipe.ops, packed, area=tabs[0], bbox=tabs[1])
             if not keep_masks:

@@ -438,6 +438,11 @@ int demia_mask_crop_unpack(const uint32_t* payload, const int32_t* bbox, const i
  *   at (x_off, y_off), same clip at the frame edge) into each mask's room -- the caller's upper bound of its tight box --
  *   with area / tight bbox reduced on the way out; one workgroup per mask, which writes its own room only.
  * gather: dst[i] = src[index[i]] (dst_room[i] is the room of src mask index[i]).
+ * reroom: dst[i] = src mask index[i] (i when index is NULL) stored for dst_room[i], in the same layout at dst[dst_offsets[i]]: a
+ *   destination word inside the source room is a copy of the source word, any other destination word is zero (both rooms lie
+ *   on the global word grid: no bit shifts); an empty destination room (-1) writes nothing.  max_dst_words >= the words of the
+ *   largest destination room (the caller knows it from its own room tables): the grid is masks x slabs of it.  src and dst must
+ *   not alias.  How a set is tightened to its boxes for the instance tables, and rebuilt from a gathered table's rows.
  * pair_matrix / pair_intersections: contract and output layout of demia_mask_pair_matrix / demia_mask_pair_intersections.
  * unpack_pooled: masks [first, first + n) into slots 0 .. n - 1 of a plane pool that stays zero outside prev (the rule of
  *   demia_mask_gather_regions_pooled): how the plane kernels (contours, measurements, histograms, programs) reach a set.
@@ -447,6 +452,8 @@ int demia_crop_place_tiles(const uint32_t* src, const int32_t* x_off, const int3
                            int32_t* area, int32_t* bbox, void* stream);
 int demia_crop_gather(const uint32_t* src, const int64_t* src_offsets, const int64_t* index, const int32_t* dst_room,
                       const int64_t* dst_offsets, int64_t M, uint32_t* dst, void* stream);
+int demia_crop_reroom(const uint32_t* src, const int32_t* src_room, const int64_t* src_offsets, const int64_t* index,
+                      const int32_t* dst_room, const int64_t* dst_offsets, int64_t M, int64_t max_dst_words, uint32_t* dst, void* stream);
 int demia_crop_pair_matrix(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
                            const int32_t* first, const int32_t* count, const int32_t* label, int32_t* out, int64_t M, int ld,
                            void* stream);
