@@ -3,7 +3,8 @@ with the per-pixel and per-pair work on the MI355X and the greedy matching in na
 
 Device (``csrc/evaluate.hip``): polygon rasterisation with ``rleFrPoly``'s rule (``rasterize_polygons``), the detection x
 ground-truth intersection matrix of one image (``cross_matrix``), column-major run lengths of packed masks
-(``rle_counts``).  Host native (``csrc/hostloops.hip``): ``evaluateImg`` for every (task, category, image, area range, IoU
+(``rle_counts``) -- each on full-frame planes and, with the ``_crop`` suffix, on crop-framed sets (:class:`CropMaskSet`: rooms,
+never planes; the same kernels over another word source).  Host native (``csrc/hostloops.hip``): ``evaluateImg`` for every (task, category, image, area range, IoU
 threshold) in one call (``match``) and ``rleToString`` (``rle_strings``).  numpy: the IoU tables, ``accumulate`` and
 ``summarize``.
 """
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .cropset import CropMaskSet, room_lengths
 
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
@@ -30,6 +32,49 @@ def _ptr(a: np.ndarray) -> int:
 
 
 # ---- device ----------------------------------------------------------------------------------------------------------------
+class _PolygonTables:
+    """The host tables of the rasteriser for ``masks[m]`` = the polygons of mask m, uploaded: vertices, the polygon and vertex
+    index of every edge, the polygons of every mask, the room of every polygon's boundary points, and the zeroed counters with
+    the error word behind them."""
+
+    def __init__(self, ops, masks):
+        verts, vert_off, mask_poly = [], [0], [0]
+        for polys in masks:
+            for p in polys:
+                a = np.asarray(p, dtype=np.float64).reshape(-1, 2)
+                verts.append(a)
+                vert_off.append(vert_off[-1] + len(a))
+            mask_poly.append(len(vert_off) - 1)
+        xy = np.ascontiguousarray(np.concatenate(verts) if verts else np.zeros((0, 2)), dtype=np.float64)
+        vo = np.asarray(vert_off, dtype=np.int64)
+        k = np.diff(vo)
+        P, E = len(k), int(vo[-1])
+        edge_poly = np.repeat(np.arange(P), k)
+        edge_idx = np.arange(E) - np.repeat(vo[:-1], k)
+        nxt = np.where(edge_idx + 1 == np.repeat(k, k), np.repeat(vo[:-1], k), np.arange(E) + 1)
+        # room for the kept boundary points: at most one per walk point, max(|dx|, |dy|) + 1 of the x5 lattice per edge
+        span = np.abs(xy[nxt] - xy[np.arange(E)]).max(axis=1) if E else np.zeros((0,))
+        room = np.floor(5.0 * span).astype(np.int64) + 3
+        bnd_off = np.zeros(P + 1, dtype=np.int64)
+        np.cumsum(np.bincount(edge_poly, weights=room, minlength=P).astype(np.int64), out=bnd_off[1:])
+        tab = np.concatenate([vo.astype(np.int32), edge_poly.astype(np.int32), edge_idx.astype(np.int32),
+                              np.asarray(mask_poly, dtype=np.int32)])
+        self.P, self.E = P, E
+        self.t_tab = torch.from_numpy(tab).to(ops.device)
+        self.t_xy = torch.from_numpy(xy if len(xy) else np.zeros((1, 2))).to(ops.device)
+        self.t_off = torch.from_numpy(bnd_off).to(ops.device)
+        self.bnd = torch.empty((max(1, int(bnd_off[-1])), 2), dtype=torch.int32, device=ops.device)
+        self.cnt = torch.zeros((P + 1,), dtype=torch.int32, device=ops.device)           # [P] counters + the error word
+        self.err = self.cnt[P:]
+
+    def args(self):
+        """The arguments that ``demia_poly_rasterize`` and ``demia_crop_poly_rasterize`` share, up to ``mask_poly``."""
+        P, E, t = self.P, self.E, self.t_tab
+        o_e, o_i, o_m = P + 1, P + 1 + E, P + 1 + 2 * E
+        return (_lib.ptr(self.t_xy), _lib.ptr(t), _lib.ptr(t[o_e:]) if E else _lib.ptr(t), _lib.ptr(t[o_i:]) if E else _lib.ptr(t),
+                _lib.ptr(self.t_off), _lib.ptr(self.bnd), _lib.ptr(self.cnt), _lib.ptr(self.err), E, _lib.ptr(t[o_m:]))
+
+
 def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, W: int, err_out: Optional[list] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``masks[m]`` = the polygons of mask m, each a flat ``[x0, y0, x1, y1, ...]`` list -> packed ``[M, H, ceil(W/32)]`` int32
@@ -43,47 +88,105 @@ def rasterize_polygons(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, 
     bbox = torch.empty((M, 4), dtype=torch.int32, device=ops.device)
     if M == 0:
         return out, area, bbox
-    verts, vert_off, mask_poly = [], [0], [0]
-    for polys in masks:
-        for p in polys:
-            a = np.asarray(p, dtype=np.float64).reshape(-1, 2)
-            verts.append(a)
-            vert_off.append(vert_off[-1] + len(a))
-        mask_poly.append(len(vert_off) - 1)
-    xy = np.ascontiguousarray(np.concatenate(verts) if verts else np.zeros((0, 2)), dtype=np.float64)
-    vo = np.asarray(vert_off, dtype=np.int64)
-    k = np.diff(vo)
-    P, E = len(k), int(vo[-1])
-    edge_poly = np.repeat(np.arange(P), k)
-    edge_idx = np.arange(E) - np.repeat(vo[:-1], k)
-    nxt = np.where(edge_idx + 1 == np.repeat(k, k), np.repeat(vo[:-1], k), np.arange(E) + 1)
-    # room for the kept boundary points: at most one per walk point, max(|dx|, |dy|) + 1 of the x5 lattice per edge
-    span = np.abs(xy[nxt] - xy[np.arange(E)]).max(axis=1) if E else np.zeros((0,))
-    room = np.floor(5.0 * span).astype(np.int64) + 3
-    bnd_off = np.zeros(P + 1, dtype=np.int64)
-    np.cumsum(np.bincount(edge_poly, weights=room, minlength=P).astype(np.int64), out=bnd_off[1:])
-    tab = np.concatenate([vo.astype(np.int32), edge_poly.astype(np.int32), edge_idx.astype(np.int32),
-                          np.asarray(mask_poly, dtype=np.int32)])
-    t_tab = torch.from_numpy(tab).to(ops.device)
-    t_xy = torch.from_numpy(xy if len(xy) else np.zeros((1, 2))).to(ops.device)
-    t_off = torch.from_numpy(bnd_off).to(ops.device)
-    bnd = torch.empty((max(1, int(bnd_off[-1])), 2), dtype=torch.int32, device=ops.device)
-    cnt = torch.zeros((P + 1,), dtype=torch.int32, device=ops.device)           # [P] counters + the error word
-    o_e, o_i, o_m = P + 1, P + 1 + E, P + 1 + 2 * E
-    _lib.check(ops.lib.demia_poly_rasterize(_lib.ptr(t_xy), _lib.ptr(t_tab), _lib.ptr(t_tab[o_e:]) if E else _lib.ptr(t_tab),
-                                            _lib.ptr(t_tab[o_i:]) if E else _lib.ptr(t_tab), _lib.ptr(t_off), _lib.ptr(bnd),
-                                            _lib.ptr(cnt), _lib.ptr(cnt[P:]), E, _lib.ptr(t_tab[o_m:]), M, H, W, _lib.ptr(out),
-                                            _lib.ptr(area), _lib.ptr(bbox), ops._stream()), "demia_poly_rasterize")
+    tabs = _PolygonTables(ops, masks)
+    _lib.check(ops.lib.demia_poly_rasterize(*tabs.args(), M, H, W, _lib.ptr(out), _lib.ptr(area), _lib.ptr(bbox), ops._stream()),
+               "demia_poly_rasterize")
     if err_out is not None:
-        err_out.append(cnt[P:])
+        err_out.append(tabs.err)
     else:
-        check_rasterize_error(int(cnt[P].item()))
+        check_rasterize_error(int(tabs.err[0].item()))
     return out, area, bbox
 
 
+def polygon_rooms(masks: Sequence[Sequence[Sequence[float]]], H: int, W: int) -> np.ndarray:
+    """The rooms ``[M, 4]`` i32 (y0, x0, y1, x1, -1 = empty) that :func:`rasterize_polygons_crop` stores the masks for, from the
+    vertices alone (host arithmetic, nothing is waited for): columns ``max(0, floor(min x) - 1) .. min(W - 1, ceil(max x))``,
+    rows ``max(0, floor(min y) - 1) .. min(H - 1, ceil(max y))`` over all vertices of the mask's polygons, empty when that
+    rectangle is.  ``rleFrPoly`` rounds a vertex to the nearest fifth of a pixel and sets pixel centres, so no set pixel lies
+    more than one pixel outside the vertices' hull; the rasteriser's error word reports a mask this rule would not hold."""
+    out = np.full((len(masks), 4), -1, dtype=np.int32)
+    for m, polys in enumerate(masks):
+        pts = [np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in polys]
+        pts = np.concatenate(pts) if pts else np.zeros((0, 2))
+        if len(pts) == 0 or not np.isfinite(pts).all():
+            continue
+        lo, hi = np.floor(pts.min(axis=0)) - 1, np.ceil(pts.max(axis=0))
+        x0, y0 = int(max(0.0, lo[0])) if lo[0] < W else W, int(max(0.0, lo[1])) if lo[1] < H else H
+        x1, y1 = int(min(float(W - 1), hi[0])) if hi[0] >= 0 else -1, int(min(float(H - 1), hi[1])) if hi[1] >= 0 else -1
+        if x0 <= x1 and y0 <= y1:
+            out[m] = (y0, x0, y1, x1)
+    return out
+
+
+def rasterize_polygons_crop(ops, masks: Sequence[Sequence[Sequence[float]]], H: int, W: int, rooms: Optional[np.ndarray] = None
+                            ) -> Tuple[CropMaskSet, torch.Tensor]:
+    """:func:`rasterize_polygons` into the rooms of a :class:`CropMaskSet` (``demia_crop_poly_rasterize``): the same bits, the
+    pixel counts and the tight boxes, and no ``[M, H, wpr]`` tensor.  ``rooms`` default to :func:`polygon_rooms`.  Nothing is
+    waited for: the second value is the kernel's error word (a 1-element device tensor) for the caller to fetch with its own
+    tables and hand to :func:`check_rasterize_error`."""
+    M = len(masks)
+    if M == 0:
+        return CropMaskSet.empty(ops, (H, W)), torch.zeros((1,), dtype=torch.int32, device=ops.device)
+    room_h = polygon_rooms(masks, H, W) if rooms is None else np.ascontiguousarray(rooms, dtype=np.int32).reshape(M, 4)
+    area = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    bbox = torch.empty((M, 4), dtype=torch.int32, device=ops.device)
+    out = CropMaskSet(ops, (H, W), room_h, None, bbox, area)
+    out.payload = CropMaskSet._payload(ops, out.words)
+    tabs = _PolygonTables(ops, masks)
+    _lib.check(ops.lib.demia_crop_poly_rasterize(*tabs.args(), M, H, W, _lib.ptr(out.room), _lib.ptr(out.offsets),
+                                                 int(room_lengths(room_h).max()), _lib.ptr(out.payload), _lib.ptr(area), _lib.ptr(bbox),
+                                                 ops._stream()), "demia_crop_poly_rasterize")
+    return out, tabs.err
+
+
 def check_rasterize_error(word: int) -> None:
-    if word:
+    """Raise for the rasteriser's error word: bit 1 = a boundary list overflowed, bit 2 (rooms only) = a mask's boundary points
+    could set a pixel outside its room."""
+    if word & 1:
         raise _lib.HipKernelError("demia_poly_rasterize: a boundary list overflowed its room")
+    if word:
+        raise _lib.HipKernelError("demia_crop_poly_rasterize: a polygon's boundary points reach outside its mask's room")
+
+
+def rle_host_crop(counts: Sequence[int], H: int, W: int):
+    """Run lengths (background first, column-major, as ``rle_decode`` takes them) -> ``(box (y0, x0, y1, x1), words uint32, pixel
+    count)`` on the host: the tight box from the runs, then the box's rows packed in the layout of a room (rows x word columns
+    ``x0 >> 5 .. x1 >> 5``).  Only the box's columns are ever dense; an empty mask gives ``((-1,) * 4, no words, 0)``."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    end = np.cumsum(c)
+    fg = ((np.arange(len(c)) & 1) == 1) & (c > 0)
+    s, e = (end - c)[fg], end[fg]                                     # foreground runs [s, e) in column-major positions
+    if len(s) == 0:
+        return (-1, -1, -1, -1), np.zeros((0,), np.uint32), 0
+    if int(e.max()) > H * W:
+        raise ValueError(f"run lengths cover {int(e.max())} pixels, the frame has {H * W}")
+    xs, xe = s // H, (e - 1) // H
+    cross = xs < xe                                                   # (a run that goes on into the next column has rows H - 1 and 0)
+    x0, x1 = int(xs.min()), int(xe.max())
+    y0, y1 = int(np.where(cross, 0, s % H).min()), int(np.where(cross, H - 1, (e - 1) % H).max())
+    bw = x1 - x0 + 1
+    delta = np.zeros(bw * H + 1, dtype=np.int32)
+    np.add.at(delta, s - x0 * H, 1)
+    np.add.at(delta, e - x0 * H, -1)
+    cols = (np.cumsum(delta[:-1]) > 0).reshape(bw, H).T[y0:y1 + 1]     # [rows, bw]
+    c0, wc = x0 >> 5, (x1 >> 5) - (x0 >> 5) + 1
+    bits = np.zeros((y1 - y0 + 1, wc * 32), dtype=bool)
+    bits[:, x0 - 32 * c0: x0 - 32 * c0 + bw] = cols
+    words = np.packbits(bits.reshape(-1, wc, 32), axis=-1, bitorder="little").view("<u4").reshape(-1)
+    return (y0, x0, y1, x1), words.astype(np.uint32), int((e - s).sum())
+
+
+def rle_crop_set(ops, runs: Sequence[Sequence[int]], H: int, W: int) -> CropMaskSet:
+    """The masks given as run lengths (ground truth with ``segmentation`` as a dict) as a :class:`CropMaskSet` whose rooms are
+    the tight boxes: packed on the host (:func:`rle_host_crop`), words, boxes and pixel counts uploaded in one copy."""
+    M = len(runs)
+    if M == 0:
+        return CropMaskSet.empty(ops, (H, W))
+    got = [rle_host_crop(r, H, W) for r in runs]
+    room_h = np.asarray([g[0] for g in got], dtype=np.int32).reshape(M, 4)
+    words = np.concatenate([g[1] for g in got] + [np.zeros((1,), np.uint32)]).view(np.int32)      # (never empty)
+    tab = ops.upload(np.concatenate([room_h.reshape(-1), np.asarray([g[2] for g in got], dtype=np.int32), words]))
+    return CropMaskSet(ops, (H, W), room_h, tab[5 * M:], tab[:4 * M].view(M, 4), tab[4 * M:5 * M])
 
 
 def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Optional[np.ndarray], gt: torch.Tensor,
@@ -102,6 +205,28 @@ def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Opti
     _lib.check(ops.lib.demia_mask_cross_matrix(_lib.ptr(det), _lib.ptr(det_bbox), _lib.ptr(tt[2 * D:]) if lab else 0, _lib.ptr(gt),
                                                _lib.ptr(gt_bbox), _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]),
                                                _lib.ptr(out), D, G, H, W, ops._stream()), "demia_mask_cross_matrix")
+    return out
+
+
+def cross_matrix_crop(ops, det: CropMaskSet, det_label: Optional[np.ndarray], gt: CropMaskSet, gt_label: Optional[np.ndarray],
+                      det_bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`cross_matrix` of two crop-framed sets over one frame (``demia_crop_cross_matrix``): the same ``[D, G]`` counts.
+    ``det_bbox``: the detections' tight boxes on the device when the caller has its own copy (default: the set's)."""
+    D, G = len(det), len(gt)
+    out = torch.zeros((D, max(G, 1)), dtype=torch.int32, device=ops.device)
+    if D == 0 or G == 0:
+        return out[:, :G]
+    assert det.hw == gt.hw
+    tab = np.concatenate([np.zeros(D, np.int32), np.full(D, G, np.int32),
+                          np.asarray(det_label if det_label is not None else np.zeros(D), dtype=np.int32),
+                          np.asarray(gt_label if gt_label is not None else np.zeros(G), dtype=np.int32)])
+    tt = torch.from_numpy(tab).to(ops.device)
+    lab = det_label is not None
+    _lib.check(ops.lib.demia_crop_cross_matrix(_lib.ptr(det.payload), _lib.ptr(det.room), _lib.ptr(det.offsets),
+                                               _lib.ptr(det.bbox if det_bbox is None else det_bbox), _lib.ptr(tt[2 * D:]) if lab else 0,
+                                               _lib.ptr(gt.payload), _lib.ptr(gt.room), _lib.ptr(gt.offsets), _lib.ptr(gt.bbox),
+                                               _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]), _lib.ptr(out), D, G,
+                                               ops._stream()), "demia_crop_cross_matrix")
     return out
 
 
@@ -149,6 +274,46 @@ def rle_counts_launch(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int, roo
     off.clamp_(max=int(counts.shape[0]))
     _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(off), _lib.ptr(counts), M, H, W,
                                                ops._stream()), "demia_mask_rle_colmajor")
+    return n, counts
+
+
+def _crop_rle(ops, cset: CropMaskSet, bbox: torch.Tensor, n, off, counts) -> None:
+    H, W = cset.hw
+    _lib.check(ops.lib.demia_crop_rle_colmajor(_lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets), _lib.ptr(bbox), _lib.ptr(n),
+                                               _lib.ptr(off), _lib.ptr(counts), len(cset), H, W, ops._stream()), "demia_crop_rle_colmajor")
+
+
+def rle_counts_crop(ops, cset: CropMaskSet, bbox: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """:func:`rle_counts` of a crop-framed set (``demia_crop_rle_colmajor``): the same ``(counts, offsets)``, the masks read in
+    their rooms.  ``bbox``: the tight boxes on the device when the caller has its own copy (default: the set's)."""
+    M = len(cset)
+    if M == 0:
+        return np.zeros((0,), np.uint32), np.zeros((1,), np.int64)
+    bbox = cset.bbox if bbox is None else bbox
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    _crop_rle(ops, cset, bbox, n, None, None)
+    off = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(n.cpu().numpy(), out=off[1:])
+    t_off = torch.from_numpy(off).to(ops.device)
+    counts = torch.empty((int(off[-1]),), dtype=torch.int32, device=ops.device)
+    _crop_rle(ops, cset, bbox, None, t_off, counts)
+    return counts.cpu().numpy().view(np.uint32), off
+
+
+def rle_counts_launch_crop(ops, cset: CropMaskSet, room: int, bbox: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`rle_counts_launch` of a crop-framed set: both passes enqueued without a wait, the offsets cut at ``room`` counts;
+    the same ``(n_counts, counts)`` device tensors for :func:`rle_counts_finish`."""
+    M = len(cset)
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    counts = torch.zeros((max(1, int(room)),), dtype=torch.int32, device=ops.device)
+    if M == 0:
+        return n, counts
+    bbox = cset.bbox if bbox is None else bbox
+    _crop_rle(ops, cset, bbox, n, None, None)
+    off = torch.zeros((M + 1,), dtype=torch.int64, device=ops.device)
+    off[1:] = torch.cumsum(n, 0, dtype=torch.int64)
+    off.clamp_(max=int(counts.shape[0]))
+    _crop_rle(ops, cset, bbox, None, off, counts)
     return n, counts
 
 

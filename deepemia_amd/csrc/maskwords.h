@@ -1,5 +1,6 @@
-// Where the packed words of a mask live, as a type: the kernels of maskops.hip that only READ masks (pair counts, gray
-// histogram, pooled gather) are written once over a word SOURCE and instantiated for both layouts,
+// Where the packed words of a mask live, as a type: the kernels that only READ masks (maskops.hip: pair counts, gray
+// histogram, pooled gather; evaluate.hip: cross matrix, run lengths) are written once over a word SOURCE and instantiated for
+// both layouts,
 //
 //   PlaneWords   full-frame planes [M, H, wpr]
 //   CropWords    crop-framed sets (cropops.hip: room, offsets, payload)
@@ -34,6 +35,14 @@ struct CropWords {
         return View{payload + offsets[m], r.x, c0, r.x < 0 ? 0 : r.z - r.x + 1, r.x < 0 ? 0 : (r.w >> 5) - c0 + 1};
     }
 };
+
+// Pixel (y, x) of the frame as view v stores it: 0 for every pixel outside the view, so a kernel that looks one pixel past
+// a mask's box (the run-length encoder reads the last row of the column before it) never reads another mask's words.
+__device__ __forceinline__ uint32_t pixel(const View v, int y, int x) {
+    const int ly = y - v.y0, lx = (x >> 5) - v.c0;
+    if (ly < 0 || ly >= v.rows || lx < 0 || lx >= v.cols) return 0u;
+    return (v.p[(long)ly * v.cols + lx] >> (x & 31)) & 1u;
+}
 
 // popcount(a & b) over the intersection of two tight boxes (y0, x0, y1, x1), each operand addressed with its own view's
 // stride; the lanes of the caller share the words (it reduces the result over them).  The window is clipped to both

@@ -13,7 +13,9 @@ plus the upscaled tiles, the merges, the 0.7 cross-class pass and the spatial co
 where ``--rcnn combo`` is given and the dataset's settings enable it -- and the final masks are scored.  The pipeline has
 no regressed box: a detection's box is ``toBbox`` of its mask's run lengths (``cocoeval.rle_to_bbox``).
 ``evaluation.max_dets`` (default ``[1, 10, 100]``) is COCOeval's ``maxDets``; micrographs with several hundred particles
-need its last entry raised.
+need its last entry raised.  ``evaluation.score_frame`` (pipeline mode only) says what the scoring reads: ``planes`` (the
+default) full-frame planes, with ``mask_frame: full``; ``crops`` the image's final :class:`CropMaskSet` and a ground truth built
+as one too, with ``mask_frame: crop`` or ``crop_direct`` -- rooms are scored, no ``[*, H, W/32]`` tensor is allocated.
 
 Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task), ``coco_instances_results.json``
 (``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``.  Not provided: prediction
@@ -33,6 +35,7 @@ import numpy as np
 import torch
 
 from .. import cocoeval as CE
+from ..cropset import CropMaskSet
 from ..data.datasets import (MetadataCatalog, get_split_dicts, load_coco_test, load_or_create_split, read_dataset_info,
                              register_datasets, rle_counts_of)
 from ..data.models import choose_and_use_model, get_trained_model_paths
@@ -43,6 +46,7 @@ from ..utils.logger_utils import system_logger
 SCORE_THRESH = 0.45          # evaluate_model.py:78 (--threshold does not apply)
 BATCH = 4                    # same-size test images per forward
 MODES = ("predictor", "pipeline")
+SCORE_FRAMES = ("planes", "crops")
 
 
 def evaluation_settings(dataset_name: Optional[str] = None) -> Tuple[str, List[int]]:
@@ -56,6 +60,29 @@ def evaluation_settings(dataset_name: Optional[str] = None) -> Tuple[str, List[i
     if mode not in MODES:
         raise ValueError(f"evaluation mode must be one of {MODES}, got {mode!r}")
     return mode, CE.check_max_dets(cfg.get("max_dets"))
+
+
+def score_frame_setting(dataset_name: Optional[str] = None, mask_frame: Optional[str] = None) -> str:
+    """``evaluation.score_frame`` (global, or in the dataset's file, next to ``mode`` and ``max_dets``): what the pipeline mode's
+    scoring reads, ``planes`` (the default) or ``crops``; the predictor mode never asks.  ValueError for an unknown value and,
+    when the dataset's ``mask_frame`` is given, for a pair that does not go together: ``crops`` scores the pipeline's
+    :class:`CropMaskSet` and needs ``mask_frame: crop`` or ``crop_direct``; ``planes`` scores planes and needs ``mask_frame: full``."""
+    try:
+        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
+    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
+        cfg = {}
+    frame = str(cfg.get("score_frame", "planes")).strip().lower()
+    if frame not in SCORE_FRAMES:
+        raise ValueError(f"evaluation.score_frame must be 'planes' or 'crops', got {frame!r}")
+    if mask_frame is not None:
+        if frame == "crops" and mask_frame == "full":
+            raise ValueError("evaluation.score_frame: crops needs inference_settings.mask_frame: crop or crop_direct "
+                             "(mask_frame: full hands the scoring planes)")
+        if frame == "planes" and mask_frame != "full":
+            raise ValueError(f"inference_settings.mask_frame: {mask_frame} is not supported by the evaluate task's pipeline mode with "
+                             "evaluation.score_frame: planes (that scoring runs on full-frame planes only); use evaluation.score_frame: "
+                             "crops, or mask_frame: full, for this dataset")
+    return frame
 
 
 def read_image_bgr(path: str) -> np.ndarray:
@@ -95,6 +122,25 @@ def _gt_masks(ops: MaskOps, anns: List[dict], H: int, W: int):
     allm[torch.tensor(rle_idx, device=ops.device)] = ops.from_dense(dense)
     area, bbox = ops.area_bbox(allm)
     return allm, area, bbox
+
+
+def _gt_crops(ops: MaskOps, anns: List[dict], H: int, W: int) -> Tuple[CropMaskSet, torch.Tensor]:
+    """The ground truth of one image as a :class:`CropMaskSet` in annotation order (its ``area`` / ``bbox``: pixel counts and
+    boxes on the device) and the rasteriser's error word: polygons are rasterised into rooms, run-length annotations are packed
+    on the host.  Nothing is waited for."""
+    if any(a.get("segmentation") is None for a in anns):
+        raise ValueError("ground truth without a segmentation cannot be scored for masks")
+    poly_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), list)]
+    rle_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), dict)]
+    polys, err = CE.rasterize_polygons_crop(ops, [anns[i]["segmentation"] for i in poly_idx], H, W)
+    if not rle_idx:
+        return polys, err
+    runs = CE.rle_crop_set(ops, [rle_counts_of(anns[i]["segmentation"]) for i in rle_idx], H, W)
+    if not poly_idx:
+        return runs, err
+    place = np.empty(len(anns), dtype=np.int64)
+    place[poly_idx + rle_idx] = np.arange(len(anns))
+    return CropMaskSet.cat([polys, runs]).select(place), err
 
 
 def _gt_box_xywh(a: dict) -> List[float]:
@@ -270,10 +316,8 @@ class PipelineRunner:
 
         self.INF = INF
         self.st = INF.PipelineSettings(dataset_name)
-        if self.st.mask_frame != "full":
-            # (the scoring below -- cross matrix, COCO RLE -- reads full-frame planes)
-            raise ValueError(f"inference_settings.mask_frame: {self.st.mask_frame} is not supported by the evaluate task's pipeline mode "
-                             "(its scoring runs on full-frame planes only); use mask_frame: full for this dataset")
+        # (what the scoring reads -- planes or the pipeline's crop set -- must be what the pipeline hands it: checked before any model is loaded)
+        self.score_frame = score_frame_setting(dataset_name, self.st.mask_frame)
         predictors, models = [], []
         for r in ((50, 101) if str(rcnn) == "combo" else (int(rcnn),)):
             paths = get_trained_model_paths(split_dir, r)
@@ -303,8 +347,10 @@ class PipelineRunner:
         return torch.from_numpy(img).to(self.dev)
 
     def instances(self, paths: Sequence[str]):
-        """Generator over ``paths`` in order: ``(path, (H, W), packed, scores, classes, tabs)`` -- the image's final packed masks on
-        the device (None or empty when nothing is left), its scores and classes, ``tabs = (pixel counts, boxes)`` on the host."""
+        """Generator over ``paths`` in order: ``(path, (H, W), packed, scores, classes, tabs)`` -- the image's final masks on the
+        device (None or empty when nothing is left), its scores and classes, ``tabs = (pixel counts, boxes)`` on the host.
+        ``packed`` is what ``final_instances`` keeps in the dataset's ``mask_frame``: full-frame planes ``[n, H, W/32]`` int32 under
+        ``full`` (``score_frame: planes``), a :class:`CropMaskSet` under ``crop`` and ``crop_direct`` (``score_frame: crops``)."""
         INF, st, pipe = self.INF, self.st, self.pipe
         t0, r0 = time.perf_counter(), self.t_read
         on_dev = {p: self._load(p) for p in paths[:5]}
@@ -345,30 +391,37 @@ def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tabl
     t_score = 0.0
     for ri, (_, hw, packed, scores, classes, tabs) in enumerate(runner.instances([rec["file_name"] for rec in recs])):
         t0 = time.perf_counter()
-        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id)
+        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame)
         t_score += time.perf_counter() - t0
     return per_image, (runner.t_read, runner.t_pipe, t_score)
 
 
-def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id) -> dict:
+def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None) -> dict:
     """Device work of one image's final instances (ground-truth masks, intersections, run lengths) and its rows of the IoU
     tables.  Everything the host needs comes over in ONE device-to-host copy; the detections' pixel counts and boxes are
-    already on the host (``tabs``)."""
+    already on the host (``tabs``).  Dispatches on what ``final_instances`` handed over: planes are scored on planes, a
+    :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no instance)."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(int(v) for v in hw) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
-    anns = rec["annotations"]
     n = 0 if packed is None else int(packed.shape[0])
-    G = len(anns)
     if n == 0:
-        packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
         d_area, d_bbox = np.zeros((0,), np.int64), np.zeros((0, 4), np.int32)
     else:
         d_area, d_bbox = np.asarray(tabs[0]).astype(np.int64), np.ascontiguousarray(np.asarray(tabs[1]).reshape(-1, 4), dtype=np.int32)
-    packed = packed.contiguous()
+    det = (np.asarray([int(c) for c in classes][:n], dtype=np.int64), np.asarray([float(v) for v in scores][:n], dtype=np.float64), d_area, d_bbox)
+    if isinstance(packed, CropMaskSet) or (n == 0 and score_frame == "crops"):
+        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id)
+    if n == 0:
+        packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
+    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id)
+
+
+def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id) -> dict:
+    """``score_frame: planes``: the detections are full-frame planes and every annotation is rasterised into one."""
+    anns = rec["annotations"]
+    classes, _, _, d_bbox = det
     ops.set_frame_width(W)
-    classes_l = [int(c) for c in classes][:n]
-    scores64 = np.asarray([float(v) for v in scores][:n], dtype=np.float64)
     d_bbox_t = torch.from_numpy(d_bbox).to(ops.device)
     if any(isinstance(a.get("segmentation"), dict) for a in anns):
         g_packed, g_area_t, g_bbox_t = _gt_masks(ops, anns, H, W)          # (RLE ground truth: its own waits)
@@ -379,22 +432,47 @@ def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, 
         err = []
         g_packed, g_area_t, g_bbox_t = CE.rasterize_polygons(ops, [a["segmentation"] for a in anns], H, W, err_out=err)
     g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
-    inter_t = CE.cross_matrix(ops, packed, d_bbox_t, np.asarray(classes_l, dtype=np.int64), g_packed, g_bbox_t, g_cat, W)
+    inter_t = CE.cross_matrix(ops, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat, W)
     n_t, counts_t = CE.rle_counts_launch(ops, packed, d_bbox_t, W, CE.rle_room(d_bbox))
-    room = int(counts_t.shape[0])
     host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [counts_t]).cpu().numpy()   # the ONE wait
+    return _finish_pipeline_image(rec, H, det, g_cat, host, bool(err), int(counts_t.shape[0]), tables, to_dataset_id,
+                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W))
+
+
+def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id) -> dict:
+    """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too, the cross
+    matrix and the run lengths read both sets' words in place.  No ``[*, H, W/32]`` tensor exists here."""
+    anns = rec["annotations"]
+    classes, _, _, d_bbox = det
+    d_bbox_t = ops.upload(d_bbox) if len(cset) else cset.bbox
+    gt, err = _gt_crops(ops, anns, H, W)
+    g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
+    inter_t = CE.cross_matrix_crop(ops, cset, classes, gt, g_cat, det_bbox=d_bbox_t)
+    n_t, counts_t = CE.rle_counts_launch_crop(ops, cset, CE.rle_room(d_bbox), bbox=d_bbox_t)
+    host = torch.cat([n_t, inter_t.reshape(-1), gt.area.reshape(-1), err.reshape(-1), counts_t]).cpu().numpy()                       # the ONE wait
+    return _finish_pipeline_image(rec, H, det, g_cat, host, True, int(counts_t.shape[0]), tables, to_dataset_id,
+                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t))
+
+
+def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_err: bool, room: int, tables, to_dataset_id, encode_again) -> dict:
+    """Host side of both scorers, from the one copy ``host`` = run-length sizes [n], intersections [n, G], ground-truth pixel
+    counts [G], the rasteriser's error word (``has_err``), the run-length room: the result rows and the image's rows of the IoU
+    tables.  ``encode_again`` runs the two-pass encoder (one more wait) when the room was too small."""
+    classes, scores64, d_area, _ = det
+    n, G, W = len(classes), len(g_cat), int(rec["width"])
+    classes_l = classes.tolist()
     n_host, pos = host[:n], n
     inter = host[pos:pos + n * G].reshape(n, G).astype(np.int64)
     pos += n * G
     g_px = host[pos:pos + G].astype(np.int64)
     pos += G
-    if err:
+    if has_err:
         CE.check_rasterize_error(int(host[pos]))
         pos += 1
     runs = CE.rle_counts_finish(n_host, host[pos:pos + room]) if n else (np.zeros((0,), np.uint32), np.zeros((1,), np.int64))
     if runs is None:
         system_logger.debug(f"{rec['file_name']}: run lengths need more than {room} counts; encoding again")
-        runs = CE.rle_counts(ops, packed, d_bbox_t, W)
+        runs = encode_again()
     strings = CE.rle_strings(*runs)
     xywh = CE.rle_to_bbox(runs[0], runs[1], H)
     xywh_l, scores_l = xywh.tolist(), scores64.tolist()

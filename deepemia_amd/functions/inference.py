@@ -2106,6 +2106,8 @@ class PipelineSettings:
         self.classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
         self.mask_frame = mask_frame_setting(inf)
         self.rank_exchange = rank_exchange_setting(inf)
+        # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
+        self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
 
     def target_classes(self, num_classes: int) -> List[int]:
         return list(range(num_classes) if self.classes_to_infer is None else [c for c in self.classes_to_infer if c < num_classes])

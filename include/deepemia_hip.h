@@ -531,7 +531,21 @@ int demia_contour_measure(const int32_t* select /* [M] or NULL */, const int32_t
  *   pairs with disjoint boxes (no mask read) or, with labels, different labels.  det and gt share H and W.
  * mask_rle_colmajor: column-major run lengths, the background run first (pycocotools' encode).  offsets == NULL: count
  *   pass, n_counts [M] = number of runs; else write pass into counts[offsets[m] .. offsets[m + 1]) (offsets [M + 1] i64 on
- *   the device, from the count pass).  H * W < 2^32.
+ *   the device, from the count pass).  H * W < 2^32.  A slot whose size (offsets[m + 1] - offsets[m]) disagrees with the mask's
+ *   run count is left alone, so offsets cut at the end of a sized buffer never make the kernel write past it.
+ * The same three for a crop-framed set (payload, room, offsets, bbox as the demia_crop_* entries take them): the evaluate
+ * task scores rooms, never planes.
+ *   crop_poly_rasterize: the rasteriser's words go to the rooms instead of planes: word t of mask m's room is row
+ *     room.y0 + t / cols, word column (room.x0 >> 5) + t % cols, written to payload[offsets[m] + t] by exactly one thread, and no
+ *     other word of payload is written; max_room_words >= the words of the largest room (the grid is masks x slabs of it).
+ *     The boundary points stay in frame coordinates, so the bits are those of poly_rasterize's plane inside the room.  area
+ *     [M] / bbox [M, 4] (required): pixel count and tight box of the room's words, reduced on the device.  The rooms come from
+ *     the caller, from the vertices alone; err bit 2 is set when a mask's kept boundary points could set a pixel outside its
+ *     room (their rectangle, columns min px .. max px x rows min py .. max py - 1, is not inside it) -- the pixels of such
+ *     a mask are NOT all stored and the caller must not use the result.  An empty room (-1) stores nothing.
+ *   crop_cross_matrix: mask_cross_matrix with both sides crop-framed sets over one frame (same kernel, same counts).
+ *   crop_rle_colmajor: mask_rle_colmajor of a set, same two-pass protocol (room_offsets: the set's word offsets; offsets: the
+ *     run offsets of the write pass).  A pixel outside a mask's room reads as 0.
  * host_coco_match / host_rle_string: host code (nothing touches the GPU), see hostloops.hip. */
 int demia_poly_rasterize(const double* xy, const int32_t* vert_off, const int32_t* edge_poly, const int32_t* edge_idx,
                          const int64_t* bnd_off, int32_t* bnd, int32_t* bnd_cnt, int32_t* err, int64_t E,
@@ -542,6 +556,16 @@ int demia_mask_cross_matrix(const uint32_t* det, const int32_t* det_bbox, const 
                             int32_t* out, int64_t D, int ld, int H, int W, void* stream);
 int demia_mask_rle_colmajor(const uint32_t* masks, const int32_t* bbox, int32_t* n_counts, const int64_t* offsets,
                             uint32_t* counts, int64_t M, int H, int W, void* stream);
+int demia_crop_poly_rasterize(const double* xy, const int32_t* vert_off, const int32_t* edge_poly, const int32_t* edge_idx,
+                              const int64_t* bnd_off, int32_t* bnd, int32_t* bnd_cnt, int32_t* err, int64_t E,
+                              const int32_t* mask_poly, int64_t M, int H, int W, const int32_t* room, const int64_t* offsets,
+                              int64_t max_room_words, uint32_t* payload, int32_t* area, int32_t* bbox, void* stream);
+int demia_crop_cross_matrix(const uint32_t* det_payload, const int32_t* det_room, const int64_t* det_offsets,
+                            const int32_t* det_bbox, const int32_t* det_label, const uint32_t* gt_payload, const int32_t* gt_room,
+                            const int64_t* gt_offsets, const int32_t* gt_bbox, const int32_t* gt_label, const int32_t* gt_first,
+                            const int32_t* gt_count, int32_t* out, int64_t D, int ld, void* stream);
+int demia_crop_rle_colmajor(const uint32_t* payload, const int32_t* room, const int64_t* room_offsets, const int32_t* bbox,
+                            int32_t* n_counts, const int64_t* offsets, uint32_t* counts, int64_t M, int H, int W, void* stream);
 int demia_host_coco_match(int64_t G, const int64_t* dt_off, const int64_t* gt_off, const double* dt_score,
                           const double* dt_area, const int64_t* dt_row, const double* gt_area, const uint8_t* gt_crowd,
                           const int64_t* gt_col, const double* iou, const double* area_rng, int A, const double* thr, int T,
