@@ -64,8 +64,14 @@ __device__ void flood(const uint32_t* P, uint32_t inv, uint32_t* R, int stride, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int rpb = (rh + nw - 1) / nw;
     const int yb0 = min(wave * rpb, rh), yb1 = min(yb0 + rpb, rh);     // this wave's band of rows
-    const int max_rounds = 2 * (rh + 32 * rw) + 8;
-    for (int round = 0; round < max_rounds; ++round) {
+    // The loop ends with the first round in which no wave changes a word.  Every round before that one sets at least one
+    // bit of R, bits are never cleared, and R has 32 * rh * rw of them: this many rounds always suffice, in whatever order the
+    // waves run, so the limit only bounds the loop and never cuts a flood short.  (A front crosses from one wave's band into
+    // the next about once per round -- a wave reads its neighbour's row when its sweep starts -- so a 1-px channel that winds
+    // up and down through all bands takes legs x bands rounds: a limit of 2 * (rh + 32 * rw) + 8, the region's perimeter,
+    // stopped such floods half way and fill_holes then filled background that was connected to the outside.)
+    const long max_rounds = 32L * rh * rw + 1;
+    for (long round = 0; round < max_rounds; ++round) {
         if (threadIdx.x == 0) *s_changed = 0;
         __syncthreads();
         bool ch = false;
