@@ -34,7 +34,9 @@ __global__ __launch_bounds__(256) void paste_kernel(const PasteP p) {
     __shared__ float sm[28 * 28];
     __shared__ float sbox[4];
     __shared__ int sflag;
-    const int inst = blockIdx.y;  // n * D + i
+    // n * D + i; a grid dimension ends at 65535, so the instances beyond that many continue in grid z
+    const int inst = blockIdx.z * gridDim.y + blockIdx.y;
+    if (inst >= p.N * p.D) return;                   // (block-uniform) the last z layer is partly empty
     const int n = inst / p.D, i = inst - n * p.D;
     const int tid = threadIdx.x;
     const int wpr = (p.out_w + 31) >> 5;  // words per row
@@ -278,7 +280,7 @@ extern "C" int demia_paste_masks(const demia_paste_desc* d, void* stream) {
     DEMIA_REQUIRE(d && d->mask_prob && d->det_boxes && d->det_classes && d->det_count && d->out_boxes && d->valid &&
                       d->packed, "null pointer");
     DEMIA_REQUIRE(d->out_w > 0 && d->out_h > 0, "output size");
-    DEMIA_REQUIRE(d->N * d->D <= 65535, "N*D <= 65535");
+    DEMIA_REQUIRE(d->N >= 0 && d->D >= 0 && (long)d->N * d->D <= 0x7fffffffL, "N*D");
     PasteP p;
     p.mask_prob = d->mask_prob; p.ld = d->ld; p.det_boxes = d->det_boxes; p.det_classes = d->det_classes;
     p.det_count = d->det_count; p.N = d->N; p.D = d->D; p.img_h = d->img_h; p.img_w = d->img_w;
@@ -289,7 +291,8 @@ extern "C" int demia_paste_masks(const demia_paste_desc* d, void* stream) {
     if (d->N * d->D == 0) return DEMIA_OK;
     // whole planes: one block per 16-row chunk; incremental: eight blocks share the chunks of an instance's two boxes
     const int gx = d->prev_bbox ? 2 : cdiv(d->out_h, PASTE_ROWS);     // incremental: two rectangles of a few hundred words per instance
-    hipLaunchKernelGGL(paste_kernel, dim3(gx, d->N * d->D), dim3(256), 0, (hipStream_t)stream, p);
+    const int inst = d->N * d->D, gy = inst < 65535 ? inst : 65535;
+    hipLaunchKernelGGL(paste_kernel, dim3(gx, gy, cdiv(inst, gy)), dim3(256), 0, (hipStream_t)stream, p);
     DEMIA_CHECK_LAUNCH("paste_kernel");
     return DEMIA_OK;
 }

@@ -384,7 +384,8 @@ struct DetP {
     int* det_count;
 };
 constexpr int DET_MAXC = 4096;
-constexpr int DET_MAXK = 128;
+constexpr int DET_MAXK = 1024;   // longest kept list (topk): 24 KiB of LDS beside the 32 KiB of keys
+constexpr int DET_WAVE0K = 128;  // up to this topk wave 0 alone scans the kept list; above it the block's waves share the scan
 
 // Class-specific box of proposal `pb` from its four deltas (weights 10, 10, 5, 5), clipped to the image; `fin` is cleared
 // when a coordinate is not finite BEFORE clipping (Detectron2 drops such rows).
@@ -400,17 +401,22 @@ __device__ __forceinline__ float4 det_class_box(const float* d, const float4& pb
     return make_float4(fminf(fmaxf(x1, 0.f), iw), fminf(fmaxf(y1, 0.f), ih), fminf(fmaxf(x2, 0.f), iw), fminf(fmaxf(y2, 0.f), ih));
 }
 
-// grid N, block 1024.  LDS: keys 32 KiB + kept list.  Only candidates whose score passes the threshold take a slot (a
-// softmax row has at most floor(1 / thresh) of them), so any number of classes fits as long as R * min(K, 1 / thresh)
-// stays within DET_MAXC; the sort key carries the row-major candidate id (proposal * K + class), so the order does not
+// grid N, block 1024.  LDS: keys 32 KiB + kept list (topk x 24 bytes, sized by the launch).  Only candidates whose score
+// passes the threshold take a slot (a softmax row has at most floor(1 / thresh) of them), so any number of classes fits
+// as long as R * min(K, 1 / thresh) stays within DET_MAXC; the sort key carries the row-major candidate id (proposal * K + class), so the order does not
 // depend on which slot a candidate landed in, and the NMS wave recomputes a candidate's box from its id.
+// WIDE (topk > DET_WAVE0K): the kept list grows to a thousand boxes, and one wave testing a chunk against it box after box
+// would be ~65 000 IoU tests in series; the scan is dealt to waves 1..15 instead (below).  Same tests on the same values,
+// so the kept set and its order are those of the one-wave path.
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void box_detections_kernel(const DetP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);   // [4096]
-    float4* kbox = reinterpret_cast<float4*>(keys + DET_MAXC);                // [128] kept boxes
-    int* kcls = reinterpret_cast<int*>(kbox + DET_MAXK);                      // [128]
-    float* kscore = reinterpret_cast<float*>(kcls + DET_MAXK);                // [128]
+    float4* kbox = reinterpret_cast<float4*>(keys + DET_MAXC);                // [topk] kept boxes
+    int* kcls = reinterpret_cast<int*>(kbox + p.topk);                        // [topk]
+    float* kscore = reinterpret_cast<float*>(kcls + p.topk);                  // [topk]
     __shared__ int nkept, ncand, maxc_bits;
+    __shared__ unsigned long long supw[16];                                   // WIDE: each wave's suppressed lanes of the chunk
     const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int K = p.K;
     const int R = p.prop_count[n] < p.R ? p.prop_count[n] : p.R;
@@ -457,7 +463,62 @@ __global__ __launch_bounds__(1024) void box_detections_kernel(const DetP p) {
         const float o = (float)cls * shift1;
         return make_float4(b.x + o, b.y + o, b.z + o, b.w + o);
     };
-    if (tid < 64) {
+    if (WIDE) {
+        // Every wave walks the chunks in step (the keys, and so the loop's exits, are the same for all of them).  Per chunk:
+        // waves 1..15 test the chunk against kept boxes w - 1, w + 14, ... and leave the lanes they found suppressed in supw[w];
+        // wave 0 meanwhile works out the intra-chunk rows, then -- after the barrier -- ORs the fifteen masks, runs the same
+        // serial resolve as the one-wave path and appends to the kept list; a second barrier publishes the list and its length.
+        const int wv = tid >> 6;
+        int kept_n = 0;
+        for (int base = 0; base < DET_MAXC && kept_n < p.topk; base += 64) {
+            const unsigned long long kk = keys[base + lane];
+            const bool live = kk != 0ull;
+            if (!__any(live)) break;
+            const int cand = live ? (int)(0xFFFFFFFFu - (unsigned)(kk & 0xFFFFFFFFull)) : 0;
+            const int cls = cand % K, prow = cand / K;
+            bool fin_unused = true;
+            const float4 b = det_class_box(p.logits + ((long)n * p.R + prow) * p.ld + K + 1 + 4 * cls,
+                                           reinterpret_cast<const float4*>(p.props)[(long)n * p.R + prow], iw, ih, fin_unused);
+            const float4 bs = shifted(b, cls);
+            unsigned long long row = 0ull;
+            if (wv == 0) {
+                for (int j = 0; j < 64; ++j) {
+                    const float4 bj = make_float4(__shfl(bs.x, j, 64), __shfl(bs.y, j, 64), __shfl(bs.z, j, 64), __shfl(bs.w, j, 64));
+                    const int cj = __shfl(cls, j, 64);
+                    const bool lj = __shfl((int)live, j, 64) != 0;
+                    if (j > lane && live && lj && cj == cls && iou_gt(bs, bj, p.nms_thresh)) row |= 1ull << j;
+                }
+            } else {
+                bool sup = false;
+                for (int j = wv - 1; j < kept_n && !sup; j += 15)
+                    if (live && kcls[j] == cls && iou_gt(shifted(kbox[j], cls), bs, p.nms_thresh)) sup = true;
+                const unsigned long long m = __ballot(sup);
+                if (lane == 0) supw[wv] = m;
+            }
+            __syncthreads();
+            if (wv == 0) {
+                unsigned long long rem = __ballot(!live);
+                for (int w = 1; w < 16; ++w) rem |= supw[w];
+                for (int bbit = 0; bbit < 64; ++bbit) {
+                    const unsigned long long rr = __shfl(row, bbit, 64);
+                    if (!((rem >> bbit) & 1ull)) rem |= rr;
+                }
+                const unsigned long long keptm = ~rem;
+                const bool me = (keptm >> lane) & 1ull;
+                const int pos = kept_n + __popcll(keptm & ((1ull << lane) - 1ull));
+                if (me && pos < p.topk) {
+                    kbox[pos] = b;
+                    kcls[pos] = cls;
+                    kscore[pos] = key2f((unsigned)(kk >> 32));
+                }
+                if (lane == 0) nkept = kept_n + __popcll(keptm);
+            }
+            __syncthreads();
+            kept_n = nkept;
+        }
+        __syncthreads();
+        if (tid == 0) nkept = kept_n < p.topk ? kept_n : p.topk;
+    } else if (tid < 64) {
         int kept_n = 0;
         for (int base = 0; base < DET_MAXC && kept_n < p.topk; base += 64) {
             const unsigned long long kk = keys[base + lane];
@@ -566,7 +627,7 @@ extern "C" int demia_box_detections(const demia_dets_desc* d, void* stream) {
         const long per_row = d->K < (long)(1.0f / d->score_thresh) ? d->K : (long)(1.0f / d->score_thresh);
         DEMIA_REQUIRE((long)d->R * per_row <= DET_MAXC, "R * min(K, floor(1 / score_thresh)) must stay within 4096 candidates");
     }
-    DEMIA_REQUIRE(d->topk > 0 && d->topk <= DET_MAXK, "topk <= 128");
+    DEMIA_REQUIRE(d->topk > 0 && d->topk <= DET_MAXK, "0 < topk <= 1024");
     DEMIA_REQUIRE(d->ld >= 5 * d->K + 1, "ld");
     DetP p;
     p.logits = d->logits; p.ld = d->ld; p.props = d->props; p.prop_count = d->prop_count;
@@ -574,13 +635,19 @@ extern "C" int demia_box_detections(const demia_dets_desc* d, void* stream) {
     p.score_thresh = d->score_thresh; p.nms_thresh = d->nms_thresh; p.topk = d->topk;
     p.det_boxes = d->det_boxes; p.det_scores = d->det_scores; p.det_classes = d->det_classes; p.det_count = d->det_count;
     if (d->N == 0) return DEMIA_OK;
-    const int smem = DET_MAXC * 8 + DET_MAXK * (16 + 4 + 4);
+    const int smem = DET_MAXC * 8 + d->topk * (16 + 4 + 4);
     static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute((const void*)box_detections_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (!done) {   // once, for the longest kept list either kernel can be launched with
+        (void)hipFuncSetAttribute((const void*)box_detections_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  DET_MAXC * 8 + DET_WAVE0K * (16 + 4 + 4));
+        (void)hipFuncSetAttribute((const void*)box_detections_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  DET_MAXC * 8 + DET_MAXK * (16 + 4 + 4));
         done = true;
     }
-    hipLaunchKernelGGL(box_detections_kernel, dim3(d->N), dim3(1024), smem, (hipStream_t)stream, p);
+    if (d->topk > DET_WAVE0K)
+        hipLaunchKernelGGL(box_detections_kernel<true>, dim3(d->N), dim3(1024), smem, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(box_detections_kernel<false>, dim3(d->N), dim3(1024), smem, (hipStream_t)stream, p);
     DEMIA_CHECK_LAUNCH("box_detections_kernel");
     return DEMIA_OK;
 }

@@ -43,11 +43,12 @@ def get_trained_model_paths(base_dir: str, rcnn: int = 101) -> dict:
     return out
 
 
-def _cfg(rcnn: int, threshold: float, num_classes: int, weights: str) -> SimpleNamespace:
-    """The three overrides of ``models.py:140-144`` on top of mask_rcnn_R_<rcnn>_FPN_3x."""
+def _cfg(rcnn: int, threshold: float, num_classes: int, weights: str, detections_per_image: int = 100) -> SimpleNamespace:
+    """The three overrides of ``models.py:140-144`` on top of mask_rcnn_R_<rcnn>_FPN_3x, and ``TEST.DETECTIONS_PER_IMAGE``
+    (the model zoo's 100, which the reference never overrides, unless ``inference_settings.detections_per_image`` says otherwise)."""
     roi = SimpleNamespace(SCORE_THRESH_TEST=threshold, NUM_CLASSES=num_classes)
     model = SimpleNamespace(DEVICE="cuda", ROI_HEADS=roi, WEIGHTS=weights, DEPTH=rcnn)
-    return SimpleNamespace(MODEL=model)
+    return SimpleNamespace(MODEL=model, TEST=SimpleNamespace(DETECTIONS_PER_IMAGE=detections_per_image))
 
 
 def read_d2_checkpoint(path: str) -> Dict[str, torch.Tensor]:
@@ -65,8 +66,12 @@ def load_model(cfg, model_path: str, dataset_name: str, is_quantized: bool = Fal
     cfg.MODEL.ROI_HEADS.NUM_CLASSES = len(metadata.thing_classes)
     sd = read_d2_checkpoint(model_path)
     device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cuda:0"
+    dets = int(getattr(getattr(cfg, "TEST", None), "DETECTIONS_PER_IMAGE", 100))
     eng = MaskRCNNEngine(sd, cfg.MODEL.DEPTH, cfg.MODEL.ROI_HEADS.NUM_CLASSES, cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST,
-                         device, DEFAULT_PRECISION, MIN_SIZE_TEST, MAX_SIZE_TEST)
+                         device, DEFAULT_PRECISION, MIN_SIZE_TEST, MAX_SIZE_TEST, dets_per_image=dets)
+    if dets != 100:
+        system_logger.warning(f"TEST.DETECTIONS_PER_IMAGE = {dets}: not the reference's 100 -- results are NOT comparable with "
+                              f"the reference's")
     if (MIN_SIZE_TEST, MAX_SIZE_TEST) != (800, 1333):
         system_logger.warning(f"INPUT.MIN_SIZE_TEST / MAX_SIZE_TEST = {MIN_SIZE_TEST} / {MAX_SIZE_TEST}: not the reference's "
                               f"800 / 1333 -- results are NOT comparable with the reference's")
@@ -82,6 +87,9 @@ def choose_and_use_model(model_paths: dict, dataset_name: str, threshold: float,
     if dataset_name not in model_paths:
         system_logger.error(f"No model found for dataset {dataset_name}")
         return None, None
-    cfg = _cfg(rcnn, threshold, len(metadata.thing_classes), model_paths[dataset_name])
+    from ..functions.inference import detections_per_image_setting      # (that module imports this one)
+    from ..utils.config import get_config
+    dets = detections_per_image_setting(get_config(dataset_name=dataset_name).get("inference_settings", {}))
+    cfg = _cfg(rcnn, threshold, len(metadata.thing_classes), model_paths[dataset_name], dets)
     system_logger.info(f"Using standard model for {dataset_name}")
     return load_model(cfg, model_paths[dataset_name], dataset_name, is_quantized=False), metadata

@@ -52,9 +52,18 @@ PRE_NMS_TOPK = 1000
 POST_NMS_TOPK = 1000
 RPN_NMS_THRESH = 0.7
 DET_NMS_THRESH = 0.5
-DETS_PER_IMAGE = 100
+DETS_PER_IMAGE = 100          # TEST.DETECTIONS_PER_IMAGE of the model-zoo config: the default of MaskRCNNEngine(dets_per_image=...)
+MAX_DETS_PER_IMAGE = 1000     # demia_box_detections keeps up to 1024 in LDS; the RPN hands it 1000 proposals
 
 EXPECTED_IGNORED_PREFIXES = ("proposal_generator.anchor_generator.", "pixel_mean", "pixel_std")
+
+
+def check_dets_per_image(value) -> int:
+    """``MaskRCNNEngine(dets_per_image=...)``: an integer in 1..1000 (needs no device)."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= MAX_DETS_PER_IMAGE:
+        raise ValueError(f"dets_per_image = {value!r}: an integer in 1..{MAX_DETS_PER_IMAGE} (the default, Detectron2's "
+                         f"TEST.DETECTIONS_PER_IMAGE, is {DETS_PER_IMAGE})")
+    return int(value)
 
 
 def resize_shape(h: int, w: int, short: int = 800, max_size: int = 1333) -> Tuple[int, int]:
@@ -232,9 +241,12 @@ class RawDetections:
 class MaskRCNNEngine:
     def __init__(self, state_dict: Dict[str, torch.Tensor], depth: int, num_classes: int, score_thresh: float,
                  device: str = "cuda:0", precision: str = "f16x2", min_size_test: int = 800, max_size_test: int = 1333,
-                 single_stages: Optional[Sequence[str]] = None):
+                 single_stages: Optional[Sequence[str]] = None, dets_per_image: int = DETS_PER_IMAGE):
         if depth not in RES_BLOCKS:
             raise ValueError(f"unsupported ResNet depth {depth}")
+        # detections kept per image and forward (TEST.DETECTIONS_PER_IMAGE): a constant of the engine -- the mask head runs all
+        # D slots of every image and the captured forward owns b x D paste planes, so the shapes stay static
+        self.dets_per_image = check_dets_per_image(dets_per_image)
         if not torch.cuda.is_available():
             raise _lib.HipExtensionMissing("no HIP device visible: the deepEMIA hot path has no CPU fallback")
         self.lib = _lib.load()
@@ -828,7 +840,7 @@ class MaskRCNNEngine:
 
     def detections(self, logits, props, prop_count, newh, neww):
         b, r, ld = logits.shape
-        D = DETS_PER_IMAGE
+        D = self.dets_per_image
         det_boxes = torch.empty((b, D, 4), dtype=torch.float32, device=self.device)
         det_scores = torch.empty((b, D), dtype=torch.float32, device=self.device)
         det_classes = torch.empty((b, D), dtype=torch.int32, device=self.device)
@@ -925,8 +937,8 @@ class MaskRCNNEngine:
                 for _ in range(slots):
                     static_in = torch.empty_like(images)
                     b, h, w = key
-                    planes = torch.zeros((b, DETS_PER_IMAGE, h, (w + 31) // 32), dtype=torch.int32, device=self.device)
-                    prev = torch.full((b, DETS_PER_IMAGE, 4), -1, dtype=torch.int32, device=self.device)
+                    planes = torch.zeros((b, self.dets_per_image, h, (w + 31) // 32), dtype=torch.int32, device=self.device)
+                    prev = torch.full((b, self.dets_per_image, 4), -1, dtype=torch.int32, device=self.device)
                     g = torch.cuda.CUDAGraph()
                     self._paste_static = (planes, prev)
                     try:

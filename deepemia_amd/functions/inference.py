@@ -308,6 +308,20 @@ def mask_frame_setting(inf_settings: dict) -> str:
     return frame
 
 
+DETECTIONS_PER_IMAGE_MAX = 1000
+
+
+def detections_per_image_setting(inf_settings: dict) -> int:
+    """``inference_settings.detections_per_image`` (global file or the dataset's): how many detections a forward keeps per image --
+    Detectron2's ``TEST.DETECTIONS_PER_IMAGE``, 100 unless set.  The model loader hands it to the engine, so the whole-image
+    pass, every tile pass and the predictor mode of the evaluate task follow it.  Anything but an integer in 1..1000 is a
+    configuration error."""
+    value = (inf_settings or {}).get("detections_per_image", 100)
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= DETECTIONS_PER_IMAGE_MAX:
+        raise ValueError(f"inference_settings.detections_per_image must be an integer in 1..{DETECTIONS_PER_IMAGE_MAX}, got {value!r}")
+    return value
+
+
 RANK_EXCHANGES = ("planes", "crops")
 
 
@@ -2106,6 +2120,7 @@ class PipelineSettings:
         self.classes_to_infer = inf.get("inference_settings", {}).get("classes_to_infer", None)
         self.mask_frame = mask_frame_setting(inf)
         self.rank_exchange = rank_exchange_setting(inf)
+        self.detections_per_image = detections_per_image_setting(inf)     # (the model loader reads it too: a bad value ends the run here)
         # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
         self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
 

@@ -279,7 +279,8 @@ int demia_roi_order(const float* boxes, const int32_t* count, int N, int R, int3
  *   logits [N, R, ld] f32: channels 0..K = class logits, K+1 .. K+4K = deltas
  *   props  [N, R, 4] f32, prop_count [N] i32
  *   det_boxes [N, topk, 4] f32 (network-input coords), det_scores [N, topk] f32,
- *   det_classes [N, topk] i32, det_count [N] i32;  topk <= 128; any number of classes K as long as
+ *   det_classes [N, topk] i32, det_count [N] i32;  0 < topk <= 1024 (Detectron2's TEST.DETECTIONS_PER_IMAGE; the kept list lives in LDS, 24 bytes per slot;
+ *   the rows of a smaller topk are the first rows of a larger one's); rows past det_count are zero; any number of classes K as long as
  *   R * min(K, floor(1 / score_thresh)) <= 4096 (a softmax row has at most floor(1 / thresh) scores above thresh;
  *   R = 1000: every K for thresholds above 0.2, K <= 4 below)                                            */
 typedef struct demia_dets_desc {
@@ -314,7 +315,7 @@ typedef struct demia_paste_desc {
     const float* det_boxes;
     const int32_t* det_classes;
     const int32_t* det_count;
-    int32_t N, D;
+    int32_t N, D;             /* any N * D that an int32 holds */
     int32_t img_h, img_w;     /* network-input size */
     int32_t out_h, out_w;     /* original image size */
     float* out_boxes;
