@@ -391,10 +391,11 @@ class CropMaskSet:
         return cs
 
     def contours(self, max_contours: int = 64, max_points: Optional[int] = None, um_pix: float = 1.0, measure: bool = True, total_area=None,
-                 extra: Optional[Sequence[torch.Tensor]] = None):
+                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False):
         """``MaskOps.contours`` for this set: one trace, the measurements of every mask's first four contours right behind it, ONE
         fetch (``extra`` rides on it); same records, same return value.  Without ``total_area`` the point pool is sized from the
-        mask count; if it overflows, the set is traced again with the pool sized from its own (device) areas -- one more wait."""
+        mask count; if it overflows, the set is traced again with the pool sized from its own (device) areas -- one more wait.
+        ``shape``: the records also carry the shape descriptors (``ContourSet.launch_shape``), in that same fetch."""
         if len(self) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
 
@@ -402,6 +403,8 @@ class CropMaskSet:
             cs = self.trace(max_contours, max_points, total_area=area)
             if measure:
                 cs.launch_measure(um_pix, slots=4)
+            if shape:
+                cs.launch_shape(um_pix, slots=4)
             return cs, cs.fetch(extra=extra, with_points=True)
         try:
             cs, got = run(total_area)
@@ -409,7 +412,7 @@ class CropMaskSet:
             if "overflow" not in str(e) or total_area is not None or max_points is not None:
                 raise
             cs, got = run(int(self.area.sum().item()))
-        recs = cs.records(um_pix=um_pix, measure=measure)
+        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape)
         return recs if extra is None else (recs, list(got))
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
@@ -475,14 +478,15 @@ def crop_planes(ops: MaskOps, hw: Tuple[int, int]) -> CropPlanes:
 
 
 def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256, um_pix: Optional[float] = None,
-                 total_area: Optional[np.ndarray] = None):
+                 total_area: Optional[np.ndarray] = None, shape: bool = False):
     """The contour trace of every mask of ``cset`` (``MaskOps.trace``, unchanged), ``planes.chunk`` masks at a time through the
     pool: yields (first, n, ContourSet) per chunk, each with its unpack + trace (+ the measurements of its first contours when
     ``um_pix`` is given) enqueued and NOT waited for, and with the NEXT chunk already enqueued behind it -- the pool is reused
     in stream order, every chunk's contour tables are its own -- so the consumer's fetch of one chunk overlaps the device's
     work on the next, and the contour tables of two chunks at most are alive.  ``total_area``: the masks' pixel counts when
     they are on the host -- sizes every chunk's point pool as ``MaskOps.trace`` does (else from the mask count; a caller that
-    meets an overflow traces that chunk again)."""
+    meets an overflow traces that chunk again).  ``shape``: with ``um_pix``, the shape descriptors are enqueued behind the
+    measurements (``ContourSet.launch_shape``)."""
     ops = cset.ops
     ops.set_frame_width(cset.hw[1])
     pending = None
@@ -496,6 +500,8 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
         cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], max_points=mp, scratch=planes.scratch[:n])
         if um_pix is not None:
             cs.launch_measure(um_pix, slots=4)
+            if shape:
+                cs.launch_shape(um_pix, slots=4)
         if pending is not None:
             yield pending
         pending = (f, n, cs)
@@ -504,16 +510,17 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
 
 
 def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, total_area: Optional[np.ndarray] = None,
-                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256):
+                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256, shape: bool = False):
     """``MaskOps.contours`` (trace + the 12 measurements, records in OpenCV's order) for a crop-framed set, chunk by chunk
     through the plane pool.  ``extra``: int32 device tensors that come to the host with the FIRST chunk's tables.
     ``total_area``: the masks' pixel counts on the host (sizes the point pools); without them the pools are sized from the mask
     count, and a chunk whose pool overflows is unpacked and traced again with the pool sized from its own (device) areas.
+    ``shape``: the records also carry the shape descriptors, in each chunk's one fetch.
     Returns (records per mask, host arrays of ``extra`` or None); one device-to-host wait per chunk."""
     ops = cset.ops
     area = None if total_area is None else np.asarray(total_area).reshape(-1)
     recs, got = [], None
-    for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area)):
+    for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area, shape=shape)):
         ex = extra if k == 0 else None
         try:
             g = cs.fetch(extra=ex, with_points=True)
@@ -524,10 +531,12 @@ def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, to
             cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], total_area=int(cset.area[f:f + n].sum().item()),
                            scratch=planes.scratch[:n])
             cs.launch_measure(um_pix, slots=4)
+            if shape:
+                cs.launch_shape(um_pix, slots=4)
             g = cs.fetch(extra=ex, with_points=True)
         if k == 0:
             got = list(g)
-        recs.extend(cs.records(um_pix=um_pix, measure=True))
+        recs.extend(cs.records(um_pix=um_pix, measure=True, shape=shape))
     if extra is not None and got is None:
         got = [e.cpu().numpy() for e in extra]
     return recs, (got if extra is not None else None)

@@ -989,6 +989,210 @@ __global__ __launch_bounds__(64) void contour_measure_kernel(const MeasureP p) {
     }
 }
 
+// ---- convex-hull shape descriptors (demia_contour_shape) ---------------------------------------------------------------
+struct ShapeP {
+    const int* select;    // [M] or NULL: masks with select[m] == 0 are skipped
+    const int* count;     // [M]
+    const int* info;      // [M, C, 4]
+    const double* red;    // [M, C, 2]
+    const int* points;
+    int M, C, max_points;
+    int* work_i;          // [4 * max_points]
+    double um_pix;
+    double* out;          // [M, out_c, SHAPE_COLS]
+    int out_c;
+};
+
+constexpr int SHAPE_COLS = 10;
+constexpr int SHAPE_NL = 256;     // contours up to this many points keep points, sorted points and hull in LDS
+constexpr int SHAPE_RANK = 4096;  // up to this many points the (x, y) order is a rank sort over the lanes, beyond a heap sort on lane 0
+
+__device__ inline bool xy_less(int ax, int ay, int bx, int by) { return ax < bx || (ax == bx && ay < by); }
+
+// In-place heap sort of n (x, y) pairs by (x, y): one lane, O(n log n), for the rare contour beyond SHAPE_RANK points.
+__device__ void heapsort_xy(int* s, int n) {
+    auto sift = [&](int root, int end) {
+        const int vx = s[2 * root], vy = s[2 * root + 1];
+        for (;;) {
+            int ch = 2 * root + 1;
+            if (ch >= end) break;
+            if (ch + 1 < end && xy_less(s[2 * ch], s[2 * ch + 1], s[2 * ch + 2], s[2 * ch + 3])) ++ch;
+            if (!xy_less(vx, vy, s[2 * ch], s[2 * ch + 1])) break;
+            s[2 * root] = s[2 * ch]; s[2 * root + 1] = s[2 * ch + 1];
+            root = ch;
+        }
+        s[2 * root] = vx; s[2 * root + 1] = vy;
+    };
+    for (int i = n / 2 - 1; i >= 0; --i) sift(i, n);
+    for (int end = n - 1; end > 0; --end) {
+        const int tx = s[0], ty = s[1];
+        s[0] = s[2 * end]; s[1] = s[2 * end + 1];
+        s[2 * end] = tx; s[2 * end + 1] = ty;
+        sift(0, end);
+    }
+}
+
+// (b - a) x (c - a), exact for coordinates below 2^30.
+__device__ inline long long cross3(int ax, int ay, int bx, int by, int cx, int cy) {
+    return (long long)(bx - ax) * (long long)(cy - ay) - (long long)(by - ay) * (long long)(cx - ax);
+}
+
+// Strict convex hull of the DISTINCT points of s (n pairs sorted by (x, y), repeats adjacent): Andrew's monotone chain, one
+// lane.  h has room for n + 1 pairs.  Returns k: 1 for one distinct point, 2 for collinear points (the two ends), else >= 3,
+// counter-clockwise in (x, y) as written (clockwise on a screen whose y grows downwards).
+__device__ int monotone_chain_xy(const int* s, int n, int* h) {
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        const int x = s[2 * i], y = s[2 * i + 1];
+        if (i > 0 && x == s[2 * i - 2] && y == s[2 * i - 1]) continue;
+        while (k >= 2 && cross3(h[2 * k - 4], h[2 * k - 3], h[2 * k - 2], h[2 * k - 1], x, y) <= 0) --k;
+        h[2 * k] = x; h[2 * k + 1] = y; ++k;
+    }
+    if (k == 1) return 1;
+    const int t = k + 1;
+    for (int i = n - 2; i >= 0; --i) {
+        const int x = s[2 * i], y = s[2 * i + 1];
+        if (x == s[2 * i + 2] && y == s[2 * i + 3]) continue;      // a repeat, or a member of the last (greatest) point's group
+        while (k >= t && cross3(h[2 * k - 4], h[2 * k - 3], h[2 * k - 2], h[2 * k - 1], x, y) <= 0) --k;
+        h[2 * k] = x; h[2 * k + 1] = y; ++k;
+    }
+    return k - 1;                                                   // the last vertex written is the first again
+}
+
+// Key of the max-Feret pair search: larger d2 wins, then the lexicographically smaller a, then the smaller b.
+struct FeretKey { long long d2; int ax, ay, bx, by; };
+
+__device__ inline bool feret_better(const FeretKey& p, const FeretKey& q) {
+    if (p.d2 != q.d2) return p.d2 > q.d2;
+    if (p.ax != q.ax || p.ay != q.ay) return xy_less(p.ax, p.ay, q.ax, q.ay);
+    return xy_less(p.bx, p.by, q.bx, q.by);
+}
+
+// One WAVE per contour, as contour_measure_kernel.  Rank sort by (x, y) over the lanes, monotone chain on lane 0, then the
+// O(k^2) searches over the k hull vertices -- farthest pair, width per edge -- over the lanes with wave reductions.  Every
+// decision is 64-bit integer arithmetic; f64 only turns the decided integers into lengths, ratios and the angle.
+__global__ __launch_bounds__(64) void contour_shape_kernel(const ShapeP p) {
+    __shared__ int l_pts[2 * SHAPE_NL], l_sorted[2 * SHAPE_NL], l_hull[2 * SHAPE_NL + 2];
+    __shared__ int sh_k;
+    const int m = blockIdx.x, lane = threadIdx.x;
+    if (p.select && !p.select[m]) return;
+    const int cnt = min(p.count[m], p.out_c);
+    for (int c = blockIdx.y; c < cnt; c += MEAS_CG) {
+        const long t = (long)m * p.C + c;
+        const int* inf = p.info + t * 4;
+        const int n = inf[2], off = inf[3];
+        double* o = p.out + ((long)m * p.out_c + c) * SHAPE_COLS;
+        const double area = p.red[2 * t], perimeter = p.red[2 * t + 1];
+        if (n <= 0) {                                            // no tracer leaves one; nothing to read
+            if (lane < SHAPE_COLS) o[lane] = 0.0;
+            continue;
+        }
+        const int* gpts = p.points + 2L * off;
+        const bool in_lds = n <= SHAPE_NL;
+        // scratch: LDS, or carved per contour by its point offset (contour t owns slots [off, off + n + 4) of the point pool,
+        // hence 2 n + 8 ints of either half of work_i)
+        int* sorted = in_lds ? l_sorted : p.work_i + 2L * off;
+        int* hull = in_lds ? l_hull : p.work_i + 2L * p.max_points + 2L * off;
+        __syncthreads();                                         // the previous contour of this block is done with LDS
+        if (in_lds) for (int i = lane; i < 2 * n; i += 64) l_pts[i] = gpts[i];
+        const int* pts = in_lds ? l_pts : gpts;
+        __syncthreads();
+        // ---- order the points by (x, y): equal points are interchangeable, so the index only makes the ranks distinct ------
+        if (n <= SHAPE_RANK) {
+            for (int i = lane; i < n; i += 64) {
+                const int xi = pts[2 * i], yi = pts[2 * i + 1];
+                int r = 0;
+                for (int j = 0; j < n; ++j) {
+                    const int xj = pts[2 * j], yj = pts[2 * j + 1];
+                    r += (xj < xi) || (xj == xi && (yj < yi || (yj == yi && j < i)));
+                }
+                sorted[2 * r] = xi; sorted[2 * r + 1] = yi;
+            }
+        } else {
+            for (int i = lane; i < 2 * n; i += 64) sorted[i] = pts[i];
+            __syncthreads();
+            if (lane == 0) heapsort_xy(sorted, n);
+        }
+        __syncthreads();
+        if (lane == 0) sh_k = monotone_chain_xy(sorted, n, hull);
+        __syncthreads();
+        const int k = sh_k;
+        // ---- S2 (fan from vertex 0: every term has the hull's orientation) and PH ------------------------------------------
+        long long s2 = 0;
+        double ph = 0.0;
+        const int x0 = hull[0], y0 = hull[1];
+        for (int i = lane; i < k; i += 64) {
+            const int j = i + 1 < k ? i + 1 : 0;
+            const int xi = hull[2 * i], yi = hull[2 * i + 1], xj = hull[2 * j], yj = hull[2 * j + 1];
+            if (k >= 3) s2 += cross3(x0, y0, xi, yi, xj, yj);
+            const long long dx = xj - xi, dy = yj - yi;
+            if (k >= 2) ph += sqrt((double)(dx * dx + dy * dy));
+        }
+        // ---- farthest pair of hull vertices (a point of P that ends a longest chord is a strict hull vertex) ----------------
+        FeretKey best{-1, 0, 0, 0, 0};
+        for (int i = lane; i < k; i += 64) {
+            const int xi = hull[2 * i], yi = hull[2 * i + 1];
+            for (int j = i + 1; j < k; ++j) {
+                const int xj = hull[2 * j], yj = hull[2 * j + 1];
+                const long long dx = xj - xi, dy = yj - yi;
+                FeretKey q;
+                q.d2 = dx * dx + dy * dy;
+                const bool ij = xy_less(xi, yi, xj, yj);
+                q.ax = ij ? xi : xj; q.ay = ij ? yi : yj; q.bx = ij ? xj : xi; q.by = ij ? yj : yi;
+                if (feret_better(q, best)) best = q;
+            }
+        }
+        // ---- width per hull edge: the farthest vertex from the edge's line, exact cross product; the quotient is f64 --------
+        double wmin = 1.0e300;
+        if (k >= 3) {
+            for (int i = lane; i < k; i += 64) {
+                const int j = i + 1 < k ? i + 1 : 0;
+                const int xi = hull[2 * i], yi = hull[2 * i + 1], xj = hull[2 * j], yj = hull[2 * j + 1];
+                long long far = 0;
+                for (int v = 0; v < k; ++v) {
+                    const long long cr = cross3(xi, yi, xj, yj, hull[2 * v], hull[2 * v + 1]);
+                    far = cr > far ? cr : far;                   // the hull lies on one side of each of its edges: cr >= 0
+                }
+                const long long dx = xj - xi, dy = yj - yi;
+                wmin = fmin(wmin, (double)far / sqrt((double)(dx * dx + dy * dy)));
+            }
+        }
+        // ---- wave reductions (xor butterfly: every lane ends with the same values) -----------------------------------------
+        for (int w = 32; w > 0; w >>= 1) {
+            s2 += __shfl_xor(s2, w, 64);
+            wmin = fmin(wmin, __shfl_xor(wmin, w, 64));
+            FeretKey q;
+            q.d2 = __shfl_xor(best.d2, w, 64);
+            q.ax = __shfl_xor(best.ax, w, 64); q.ay = __shfl_xor(best.ay, w, 64);
+            q.bx = __shfl_xor(best.bx, w, 64); q.by = __shfl_xor(best.by, w, 64);
+            if (feret_better(q, best)) best = q;
+        }
+        // the perimeter's terms are summed in a fixed tree (lane partials, then the butterfly): the same bits in every layout
+        for (int w = 32; w > 0; w >>= 1) ph += __shfl_xor(ph, w, 64);
+        if (lane != 0) continue;
+        const double um = p.um_pix;
+        double f2 = 0.0, maxf = 0.0, angle = 0.0;
+        if (k >= 2) {
+            f2 = (double)best.d2;
+            maxf = sqrt(f2);
+            angle = atan2((double)(-(best.by - best.ay)), (double)(best.bx - best.ax)) * (180.0 / 3.141592653589793238462643383279502884);
+            if (angle < 0.0) angle += 180.0;
+            if (angle >= 180.0) angle = 0.0;
+        }
+        const double harea = (double)s2 * 0.5;
+        o[0] = (double)s2;                                         // S2
+        o[1] = f2;                                                 // F2
+        o[2] = (double)k;                                          // hull vertices
+        o[3] = harea * um * um;                                    // Convex area
+        o[4] = ph * um;                                            // Convex perimeter
+        o[5] = s2 != 0 ? area / harea : 0.0;                       // Solidity
+        o[6] = perimeter != 0 ? ph / perimeter : 0.0;              // Convexity
+        o[7] = maxf * um;                                          // Max Feret diameter
+        o[8] = k >= 3 ? wmin * um : 0.0;                           // Min Feret diameter
+        o[9] = angle;                                              // Feret angle
+    }
+}
+
 // The small / worklist / large launch structure of a trace, for either source of the words.
 template <class P>
 int launch_contour_trace(const P& p, int32_t* worklist, hipStream_t st) {
@@ -1076,5 +1280,18 @@ extern "C" int demia_contour_measure(const int32_t* select, const int32_t* count
     MeasureP p{select, count, info, red, points, M, C, max_points, work_i, work_f, work_d, um_pix, out, out_c};
     hipLaunchKernelGGL(contour_measure_kernel, dim3(M, MEAS_CG), dim3(64), 0, (hipStream_t)stream, p);
     DEMIA_CHECK_LAUNCH("contour_measure_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int64_t demia_contour_shape_work_ints(int M, int C, int max_points) { return 4L * max_points + 16; }
+
+extern "C" int demia_contour_shape(const int32_t* select, const int32_t* count, const int32_t* info, const double* red,
+                                   const int32_t* points, int M, int C, int max_points, int32_t* work_i, double um_pix,
+                                   double* out, int out_c, void* stream) {
+    DEMIA_REQUIRE(count && info && red && points && work_i && out && out_c > 0 && max_points > 0, "args");
+    if (M * C == 0) return DEMIA_OK;
+    ShapeP p{select, count, info, red, points, M, C, max_points, work_i, um_pix, out, out_c};
+    hipLaunchKernelGGL(contour_shape_kernel, dim3(M, MEAS_CG), dim3(64), 0, (hipStream_t)stream, p);
+    DEMIA_CHECK_LAUNCH("contour_shape_kernel");
     return DEMIA_OK;
 }

@@ -20,6 +20,8 @@ from . import _lib
 # (A/B switch) 0: the large-region variants of the per-mask kernels run over all masks again instead of over a worklist
 _WORKLISTS = os.environ.get("DEEPEMIA_MASK_WORKLISTS", "1") != "0"
 
+SHAPE_COLS = 10          # values per contour of demia_contour_shape
+
 
 class PlanePool:
     """Mask planes that stay ZERO outside per-slot boxes (``demia_mask_gather_regions_pooled``): a gather into the pool
@@ -333,11 +335,12 @@ class MaskOps:
 
     def contours(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
                  um_pix: float = 1.0, measure: bool = True, bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None,
-                 extra: Optional[Sequence[torch.Tensor]] = None):
+                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False):
         """Per mask: external contours in OpenCV's order, with area, perimeter and the 12 measurement
         values.  Returns a list (per mask) of lists of dicts with keys ``points`` (P, 2) int32,
         ``area``, ``perimeter`` and (if ``measure``) ``values`` (12,) float64.  ``extra``: int32 device tensors that come to the
-        host in the SAME copy (e.g. the cropped words the RLE texts are made of); the call then returns (records, host arrays)."""
+        host in the SAME copy (e.g. the cropped words the RLE texts are made of); the call then returns (records, host arrays).
+        ``shape``: also ``shape`` (10,) float64, the convex-hull descriptors of ``demia_contour_shape``, in that same copy."""
         if int(packed.shape[0]) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
         cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area)
@@ -346,8 +349,10 @@ class MaskOps:
         # sliced copies of ContourSet.host(): five waits, rare)
         if measure:
             cs.launch_measure(um_pix, slots=4)
+        if shape:
+            cs.launch_shape(um_pix, slots=4)
         got = cs.fetch(extra=extra, with_points=True)
-        recs = cs.records(um_pix=um_pix, measure=measure)
+        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape)
         return recs if extra is None else (recs, list(got))
 
 
@@ -364,6 +369,8 @@ class ContourSet:
         self.counters = torch.zeros((4,), dtype=torch.int32, device=dev)
         self._host = None
         self._pts_host = None             # contour points brought over by fetch(with_points=True)
+        self._shape_dev = None            # [M, slots, 10] shape descriptors enqueued by launch_shape
+        self._shape_host = None
         self.blocking_point_copies = 0    # times records() had to fetch the points with a device-to-host copy of its own
 
     def host(self):
@@ -394,9 +401,23 @@ class ContourSet:
                                                  _lib.ptr(self.points), M, C, mp, _lib.ptr(self._wi), _lib.ptr(self._wf), _lib.ptr(self._wd),
                                                  float(um_pix), _lib.ptr(self._vals_dev), self._mslots, ops._stream()), "demia_contour_measure")
 
+    def launch_shape(self, um_pix: float = 1.0, slots: int = 4) -> None:
+        """:meth:`launch_measure` for the convex-hull shape descriptors (``demia_contour_shape``): the first ``slots`` contours of
+        EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one copy.  (Masks with more
+        contours than ``slots`` are computed again by :meth:`shape` on demand.)"""
+        ops = self.ops
+        M, C, mp = self.M, self.C, self.max_points
+        self._sslots, self._s_um = min(int(slots), C), float(um_pix)
+        self._swi = torch.empty((int(ops.lib.demia_contour_shape_work_ints(M, C, mp)),), dtype=torch.int32, device=ops.device)
+        self._shape_dev = torch.zeros((M, self._sslots, SHAPE_COLS), dtype=torch.float64, device=ops.device)
+        _lib.check(ops.lib.demia_contour_shape(0, _lib.ptr(self.count), _lib.ptr(self.info), _lib.ptr(self.red), _lib.ptr(self.points),
+                                               M, C, mp, _lib.ptr(self._swi), float(um_pix), _lib.ptr(self._shape_dev), self._sslots,
+                                               ops._stream()), "demia_contour_shape")
+
     def fetch(self, extra: Optional[Sequence[torch.Tensor]] = None, with_points: bool = False):
         """ONE device-to-host wait for everything the host decides on: counters, contour counts, the first ``slots``
-        contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran) and the
+        contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran, shape
+        descriptors when :meth:`launch_shape` ran) and the
         int32 device tensors in ``extra`` (returned as numpy arrays).  Falls back to the sliced copy of :meth:`host` when a
         mask has more contours than the slots fetched.  ``with_points``: the contour POINTS come over in the same copy --
         how many are in use is only known after the wait, so the copy takes as many as the previous trace of this
@@ -409,6 +430,8 @@ class ContourSet:
         f64 = [self.red[:, :k].reshape(-1)]
         if getattr(self, "_vals_dev", None) is not None:
             f64.append(self._vals_dev.reshape(-1))
+        if self._shape_dev is not None:
+            f64.append(self._shape_dev.reshape(-1))
         extra = list(extra or [])
         parts += [e.reshape(-1) for e in extra]
         n_pts = min(int(getattr(self.ops, "_points_hint", 0)), self.max_points) if with_points else 0
@@ -441,11 +464,17 @@ class ContourSet:
         if mc <= k:
             self.max_count = mc
             self._host = (count, info[:, :mc], red[:, :mc], int(cnt[0]))
+            dpos = M * k * 2
             if getattr(self, "_vals_dev", None) is not None:
-                self._vals_host = d[M * k * 2:].reshape(M, k, 12)[:, :mc]
+                self._vals_host = d[dpos:dpos + M * k * 12].reshape(M, k, 12)[:, :mc]
+                dpos += M * k * 12
+            if self._shape_dev is not None and mc <= self._sslots:
+                ks = self._sslots
+                self._shape_host = d[dpos:dpos + M * ks * SHAPE_COLS].reshape(M, ks, SHAPE_COLS)[:, :mc]
         else:                                                     # a mask with many contours: the general (two-wait) path
             self._host = None
             self._vals_host = None
+            self._shape_host = None
             self.host()
         return outs
 
@@ -484,9 +513,33 @@ class ContourSet:
                                                  float(um_pix), _lib.ptr(vals), mc, ops._stream()), "demia_contour_measure")
         return vals.cpu().numpy()
 
-    def records(self, um_pix: float = 1.0, measure: bool = True, select: Optional[Sequence[int]] = None, with_points: bool = True):
-        """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start)."""
+    def shape(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
+        """[M, max contours per mask, 10] shape descriptors (``demia_contour_shape``; only for the selected masks when ``select``
+        is given)."""
+        ops = self.ops
+        self.host()
+        pre = self._shape_host
+        if pre is not None and abs(getattr(self, "_s_um", um_pix) - um_pix) == 0.0:
+            return pre                                    # computed for every mask right behind the trace (launch_shape)
+        M, C, mp, mc = self.M, self.C, self.max_points, self.max_count
+        sel_t = None
+        if select is not None:
+            flags = np.zeros(M, dtype=np.int32)
+            flags[np.asarray(list(select), dtype=np.int64)] = 1
+            sel_t = torch.from_numpy(flags).to(ops.device)
+        wi = torch.empty((int(ops.lib.demia_contour_shape_work_ints(M, C, mp)),), dtype=torch.int32, device=ops.device)
+        vals = torch.zeros((M, mc, SHAPE_COLS), dtype=torch.float64, device=ops.device)
+        _lib.check(ops.lib.demia_contour_shape(_lib.ptr(sel_t), _lib.ptr(self.count), _lib.ptr(self.info), _lib.ptr(self.red),
+                                               _lib.ptr(self.points), M, C, mp, _lib.ptr(wi), float(um_pix), _lib.ptr(vals), mc,
+                                               ops._stream()), "demia_contour_shape")
+        return vals.cpu().numpy()
+
+    def records(self, um_pix: float = 1.0, measure: bool = True, select: Optional[Sequence[int]] = None, with_points: bool = True,
+                shape: bool = False):
+        """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start).  ``shape``: each
+        dict also holds ``shape``, the contour's 10 values of :meth:`shape`."""
         vals = self.measure(um_pix, select) if measure else None
+        shp = self.shape(um_pix, select) if shape else None
         count, info, red, used = self.host()
         pts = None
         if with_points:
@@ -505,6 +558,8 @@ class ContourSet:
                     rec["points"] = pts[off: off + n]             # views of this call's own host copies
                 if vals is not None:
                     rec["values"] = vals[m, c]
+                if shp is not None:
+                    rec["shape"] = shp[m, c]
                 recs.append(rec)
             if len(recs) > 1:
                 recs.sort(key=lambda r: (r["start"][1], r["start"][0]), reverse=True)

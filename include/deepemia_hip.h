@@ -520,6 +520,29 @@ int demia_contour_measure(const int32_t* select /* [M] or NULL */, const int32_t
                           int C, int max_points, int32_t* work_i, float* work_f, double* work_d, double um_pix,
                           double* out, int out_c, void* stream);
 
+/* demia_contour_shape = convex-hull shape descriptors per contour (not in the reference program; opt-in:
+ * inference_settings.shape_descriptors).  It reads the tables of a trace exactly as demia_contour_measure does (select, count,
+ * info, red, points, out_c) and writes nothing but `out` and its scratch.  For a contour with integer points P (n >= 1, repeats
+ * allowed), A = red[.., 0], L = red[.., 1], um = um_pix:
+ *   H   the strict convex hull of the distinct points (collinear points are no vertices); k = |H|: 1 for one distinct point,
+ *       2 for collinear points, else >= 3;
+ *   S2  twice the hull area, an exact integer (0 for k < 3);
+ *   PH  the hull perimeter in px (k = 2: twice the distance of the two points; k = 1: 0);
+ *   F2  the largest squared distance between two points of P, an exact integer; MaxFeret = sqrt(F2);
+ *   MinFeret  over the hull edges, the minimum of the largest distance of a hull vertex from the edge's line (0 for k < 3);
+ *   FeretAngle  direction of the max-Feret chord in degrees in [0, 180), y upwards: atan2(-(yb - ya), xb - xa), 180 folds to 0;
+ *       among the pairs at squared distance F2, ordered so that a < b by (x, y), the smallest a, then the smallest b; k = 1: 0.
+ *   out [M, out_c, 10] f64 = S2, F2, k, S2/2 * um^2, PH * um, A / (S2/2) (0 if S2 == 0), PH / L (0 if L == 0), MaxFeret * um,
+ *       MinFeret * um, FeretAngle.  Values 0-2 are integers held exactly; the two ratios carry no um.
+ * Hull, pair search and tie rule decide in 64-bit integers (exact for coordinates below 2^30); no f32 anywhere.
+ *   work_i [demia_contour_shape_work_ints(M, C, max_points)] i32: scratch of contours above 256 points, carved by point offset
+ *       (contour t owns [off, off + n + 4) of the point pool, as the tracer leaves it).
+ * One launch, no allocation, capturable. */
+int64_t demia_contour_shape_work_ints(int M, int C, int max_points);
+int demia_contour_shape(const int32_t* select /* [M] or NULL */, const int32_t* count, const int32_t* info, const double* red,
+                        const int32_t* points, int M, int C, int max_points, int32_t* work_i, double um_pix,
+                        double* out /* [M, out_c, 10] */, int out_c, void* stream);
+
 /* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
  * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
  *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at

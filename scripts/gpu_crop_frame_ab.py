@@ -2,12 +2,15 @@
 scripts/gpu_c3_large_image.py and of bench.py's one_8192_image leg) through the CLI's per-image path -- `final_instances` (class passes,
 tile placement, 0.4 merges, 0.7 cross-class pass, spatial constraints), the RLE texts and `measure_image` -- REPS times per frame in one
 process, the frames alternating (full, crop, full, crop, ...; the fourth argument names other frames to alternate, e.g.
-full,crop,crop_direct), same models, same image, same box.
+full,crop,crop_direct), same models, same image, same box.  A frame written as ``<frame>+shape`` runs with
+`inference_settings.shape_descriptors: true` (e.g. crop_direct,crop_direct+shape: the setting off and on, alternating).
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
-(`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`), the device-to-host waits of the post-processing, the most
-full-frame planes alive after the tile mapping, and whether all frames wrote the same rows and texts.
+(`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`), the device-to-host waits of the post-processing (the pipeline's
+own counter) and every `Tensor.cpu()` / `Tensor.item()` call of the image (counted here: `measure_image`'s waits are among them; a
+fetch that meets a mask with more contours than slots falls back to on-demand launches with copies of their own, counted apart), the
+most full-frame planes alive after the tile mapping, and whether all frames wrote the same rows (their 20 reference columns) and texts.
 
     python scripts/gpu_crop_frame_ab.py [size=8192] [reps=4] [out.json] [frames=full,crop]
 """
@@ -50,12 +53,26 @@ st = I.PipelineSettings(T.DATASET)
 pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"))
 spatial_cfg = load_spatial_constraints(T.DATASET)
 metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
-pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f), st.global_config) for f in frames}
+pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f.split("+")[0]), st.global_config) for f in frames}
+shape_on = {f: f.endswith("+shape") for f in frames}
+host_copies = [0]
+for _name in ("cpu", "item"):
+    def _counted(self, *a, _orig=getattr(torch.Tensor, _name), **k):
+        host_copies[0] += bool(self.is_cuda)
+        return _orig(self, *a, **k)
+    setattr(torch.Tensor, _name, _counted)
+from deepemia_amd.maskset import ContourSet
+fallbacks = [0]                      # fetches that met a mask with more contours than slots: measurements (and shape values) on demand
+def _fetch(self, *a, _orig=ContourSet.fetch, **k):
+    out = _orig(self, *a, **k)
+    fallbacks[0] += self.max_count > min(getattr(self, "_mslots", 4), self.C)
+    return out
+ContourSet.fetch = _fetch
 small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes([("big.tif", image_dev)]), 50)
 pipes[frames[0]].drop_cached("big.tif")
 
 
-def one_image(pipe):
+def one_image(pipe, shape=False):
     """process_image of run_inference for this image: instances, RLE texts, measurement rows."""
     name = "big.tif"
     pipe.begin_image_stats()
@@ -69,7 +86,7 @@ def one_image(pipe):
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, shape=shape)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     pipe.drop_cached(name)
     return n, rows, texts, pipe.end_image_stats((size, size))
@@ -81,18 +98,20 @@ for rep in range(reps):
     for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ... (the order of `frames`)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
-        w0 = pipe.d2h_waits
+        w0, c0, f0 = pipe.d2h_waits, host_copies[0], fallbacks[0]
         t0 = time.perf_counter()
-        n, rows, texts, stats = one_image(pipe)
+        n, rows, texts, stats = one_image(pipe, shape_on[frame])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        h = hashlib.sha256(("\n".join(texts) + repr(rows)).encode()).hexdigest()
+        assert all(len(r) == (27 if shape_on[frame] else 20) for r in rows)
+        h = hashlib.sha256(("\n".join(texts) + repr([r[:20] for r in rows])).encode()).hexdigest()
         digest.setdefault(frame, h)
         assert digest[frame] == h, "a repetition wrote other rows"
-        runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0, instances=n,
+        runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0,
+                                host_copies=host_copies[0] - c0, fetch_fallbacks=fallbacks[0] - f0, instances=n,
                                 rows=len(rows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
         print(f"rep {rep} {frame:11s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
-              f"{pipe.d2h_waits - w0} waits, {stats['full_frame_planes_peak']} planes", flush=True)
+              f"{pipe.d2h_waits - w0} waits, {host_copies[0] - c0} device-to-host copies ({fallbacks[0] - f0} fetch fallbacks), {stats['full_frame_planes_peak']} planes", flush=True)
 
 res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating " + ", ".join(frames),
        "same_rows_and_texts": len(set(digest.values())) == 1, "device": torch.cuda.get_device_name(0), "frames": {}}
@@ -102,7 +121,7 @@ for frame, rr in runs.items():
                                 steady_median_seconds=statistics.median(steady) if steady else None,
                                 steady_min_max_seconds=[min(steady), max(steady)] if steady else None,
                                 peak_bytes_first=rr[0]["peak_bytes"], peak_bytes_steady=max(r["peak_bytes"] for r in rr[1:]) if steady else None,
-                                d2h_waits_per_image=rr[-1]["d2h_waits"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
+                                d2h_waits_per_image=rr[-1]["d2h_waits"], host_copies_per_image=rr[-1]["host_copies"], fetch_fallbacks_per_image=rr[-1]["fetch_fallbacks"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
                                 full_frame_planes_peak=max(r["full_frame_planes_peak"] for r in rr))
 out_path.parent.mkdir(parents=True, exist_ok=True)
 out_path.write_text(json.dumps(res, indent=1))
