@@ -21,6 +21,7 @@ from . import _lib
 _WORKLISTS = os.environ.get("DEEPEMIA_MASK_WORKLISTS", "1") != "0"
 
 SHAPE_COLS = 10          # values per contour of demia_contour_shape
+INSCRIBED_COLS = 8       # values per contour of demia_mask_inscribed / demia_crop_inscribed
 
 
 class PlanePool:
@@ -310,11 +311,14 @@ class MaskOps:
 
     # -- contours + measurements ----------------------------------------------------------------
     def trace(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
-              bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None, scratch: Optional[torch.Tensor] = None) -> "ContourSet":
+              bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None, scratch: Optional[torch.Tensor] = None,
+              keep_words: bool = False) -> "ContourSet":
         """cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) + contourArea + arcLength for every mask, once;
         the returned set can be measured later for any subset of its masks without tracing again.  ``bbox`` (any
         superset of the tight boxes) and ``total_area`` (sizes the point pool) save a reduction when known.  ``scratch``:
-        the caller's own planes of ``packed``'s shape for the regions that do not fit in LDS (default: allocated here)."""
+        the caller's own planes of ``packed``'s shape for the regions that do not fit in LDS (default: allocated here).
+        ``keep_words``: the set remembers the planes, the boxes and the scratch it was traced from (``ContourSet.launch_inscribed``
+        reads the words again); the caller leaves them unchanged for as long as it asks the set for inscribed values."""
         M, H, wpr = packed.shape
         W = self._w(packed)
         if bbox is None or (max_points is None and total_area is None):
@@ -331,19 +335,22 @@ class MaskOps:
         _lib.check(self.lib.demia_mask_contours_wl(_lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bbox), M, H, W, C, max_points,
                                                    _lib.ptr(cs.count), _lib.ptr(cs.info), _lib.ptr(cs.red), _lib.ptr(cs.points),
                                                    _lib.ptr(cs.counters), _lib.ptr(worklist), self._stream()), "demia_mask_contours_wl")
+        if keep_words:
+            cs.set_plane_words(packed, bbox, scratch)
         return cs
 
     def contours(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
                  um_pix: float = 1.0, measure: bool = True, bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None,
-                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False):
+                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False):
         """Per mask: external contours in OpenCV's order, with area, perimeter and the 12 measurement
         values.  Returns a list (per mask) of lists of dicts with keys ``points`` (P, 2) int32,
         ``area``, ``perimeter`` and (if ``measure``) ``values`` (12,) float64.  ``extra``: int32 device tensors that come to the
         host in the SAME copy (e.g. the cropped words the RLE texts are made of); the call then returns (records, host arrays).
-        ``shape``: also ``shape`` (10,) float64, the convex-hull descriptors of ``demia_contour_shape``, in that same copy."""
+        ``shape``: also ``shape`` (10,) float64, the convex-hull descriptors of ``demia_contour_shape``, in that same copy.
+        ``inscribed``: also ``inscribed`` (8,) float64, the inscribed-circle descriptors of ``demia_mask_inscribed``, likewise."""
         if int(packed.shape[0]) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
-        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area)
+        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area, keep_words=inscribed)
         # ONE device-to-host wait: the measurements of every mask's first contours are enqueued right behind the trace and come
         # over with the counts, the contour tables and the points (a mask with more than four contours falls back to the
         # sliced copies of ContourSet.host(): five waits, rare)
@@ -351,8 +358,10 @@ class MaskOps:
             cs.launch_measure(um_pix, slots=4)
         if shape:
             cs.launch_shape(um_pix, slots=4)
+        if inscribed:
+            cs.launch_inscribed(um_pix, slots=4)
         got = cs.fetch(extra=extra, with_points=True)
-        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape)
+        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed)
         return recs if extra is None else (recs, list(got))
 
 
@@ -371,6 +380,9 @@ class ContourSet:
         self._pts_host = None             # contour points brought over by fetch(with_points=True)
         self._shape_dev = None            # [M, slots, 10] shape descriptors enqueued by launch_shape
         self._shape_host = None
+        self._words = None                # where the traced words live (set_plane_words / set_crop_words): what launch_inscribed reads
+        self._insc_dev = None             # [M, slots, 8] inscribed descriptors enqueued by launch_inscribed
+        self._insc_host = None
         self.blocking_point_copies = 0    # times records() had to fetch the points with a device-to-host copy of its own
 
     def host(self):
@@ -414,10 +426,60 @@ class ContourSet:
                                                M, C, mp, _lib.ptr(self._swi), float(um_pix), _lib.ptr(self._shape_dev), self._sslots,
                                                ops._stream()), "demia_contour_shape")
 
+    def set_plane_words(self, packed: torch.Tensor, bbox: torch.Tensor, scratch: torch.Tensor) -> None:
+        """This set was traced from the planes ``packed`` with the boxes ``bbox`` and the scratch planes ``scratch``."""
+        self._words = ("plane", packed, bbox, scratch, self.ops._w(packed))
+
+    def set_crop_words(self, cset, first: int = 0) -> None:
+        """This set is the trace of the masks ``[first, first + M)`` of the crop-framed set ``cset`` -- whether it was traced on the
+        words in place or on planes the masks were unpacked into: the payload lives as long as the set, a plane pool does not."""
+        self._words = ("crop", cset, int(first))
+
+    def _inscribed_into(self, out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray] = None) -> None:
+        """One launch of ``demia_mask_inscribed`` / ``demia_crop_inscribed`` into ``out`` [n, out_c, 8]: every mask, or the
+        positions ``sel`` -- their table rows are gathered, their words are read where they are (the entry's ``select``)."""
+        ops = self.ops
+        if self._words is None:
+            raise RuntimeError("inscribed descriptors: the trace did not keep its words (trace(..., keep_words=True))")
+        n = self.M if sel is None else len(sel)
+        if n == 0:
+            return
+        count, info, sel_d, idx = self.count, self.info, None, None
+        if sel is not None:
+            sel_d = ops.upload(np.ascontiguousarray(sel, dtype=np.int32))
+            idx = sel_d.to(torch.int64)
+            count, info = self.count.index_select(0, idx), self.info.index_select(0, idx)
+        if self._words[0] == "plane":
+            _, packed, bbox, scratch, W = self._words
+            bb = bbox if idx is None else bbox.index_select(0, idx)
+            _lib.check(ops.lib.demia_mask_inscribed(_lib.ptr(sel_d), _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bb), _lib.ptr(count),
+                                                    _lib.ptr(info), n, int(packed.shape[1]), W, self.C, float(um_pix), _lib.ptr(out),
+                                                    int(out_c), ops._stream()), "demia_mask_inscribed")
+        else:
+            _, cset, first = self._words
+            bb = cset.bbox[first:first + self.M]
+            if idx is not None:
+                bb, sel_d = bb.index_select(0, idx), sel_d + first
+            elif first:
+                sel_d = torch.arange(first, first + self.M, dtype=torch.int32, device=ops.device)
+            scratch, off_d = cset.inscribed_scratch()
+            _lib.check(ops.lib.demia_crop_inscribed(_lib.ptr(sel_d), _lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets),
+                                                    _lib.ptr(bb), _lib.ptr(count), _lib.ptr(info), n, cset.hw[0], cset.hw[1], self.C,
+                                                    float(um_pix), _lib.ptr(out), int(out_c), _lib.ptr(scratch), _lib.ptr(off_d),
+                                                    ops._stream()), "demia_crop_inscribed")
+
+    def launch_inscribed(self, um_pix: float = 1.0, slots: int = 4) -> None:
+        """:meth:`launch_measure` for the inscribed-circle descriptors (``demia_mask_inscribed`` / ``demia_crop_inscribed``): the
+        first ``slots`` contours of EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one
+        copy, behind the shape values.  (Masks with more contours than ``slots`` are computed again by :meth:`inscribed` on demand.)"""
+        self._islots, self._i_um = min(int(slots), self.C), float(um_pix)
+        self._insc_dev = torch.zeros((self.M, self._islots, INSCRIBED_COLS), dtype=torch.float64, device=self.ops.device)
+        self._inscribed_into(self._insc_dev, self._islots, um_pix)
+
     def fetch(self, extra: Optional[Sequence[torch.Tensor]] = None, with_points: bool = False):
         """ONE device-to-host wait for everything the host decides on: counters, contour counts, the first ``slots``
         contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran, shape
-        descriptors when :meth:`launch_shape` ran) and the
+        descriptors when :meth:`launch_shape` ran, inscribed descriptors when :meth:`launch_inscribed` ran) and the
         int32 device tensors in ``extra`` (returned as numpy arrays).  Falls back to the sliced copy of :meth:`host` when a
         mask has more contours than the slots fetched.  ``with_points``: the contour POINTS come over in the same copy --
         how many are in use is only known after the wait, so the copy takes as many as the previous trace of this
@@ -432,6 +494,8 @@ class ContourSet:
             f64.append(self._vals_dev.reshape(-1))
         if self._shape_dev is not None:
             f64.append(self._shape_dev.reshape(-1))
+        if self._insc_dev is not None:
+            f64.append(self._insc_dev.reshape(-1))
         extra = list(extra or [])
         parts += [e.reshape(-1) for e in extra]
         n_pts = min(int(getattr(self.ops, "_points_hint", 0)), self.max_points) if with_points else 0
@@ -468,13 +532,19 @@ class ContourSet:
             if getattr(self, "_vals_dev", None) is not None:
                 self._vals_host = d[dpos:dpos + M * k * 12].reshape(M, k, 12)[:, :mc]
                 dpos += M * k * 12
-            if self._shape_dev is not None and mc <= self._sslots:
+            if self._shape_dev is not None:
                 ks = self._sslots
-                self._shape_host = d[dpos:dpos + M * ks * SHAPE_COLS].reshape(M, ks, SHAPE_COLS)[:, :mc]
+                if mc <= ks:
+                    self._shape_host = d[dpos:dpos + M * ks * SHAPE_COLS].reshape(M, ks, SHAPE_COLS)[:, :mc]
+                dpos += M * ks * SHAPE_COLS
+            if self._insc_dev is not None and mc <= self._islots:
+                ki = self._islots
+                self._insc_host = d[dpos:dpos + M * ki * INSCRIBED_COLS].reshape(M, ki, INSCRIBED_COLS)[:, :mc]
         else:                                                     # a mask with many contours: the general (two-wait) path
             self._host = None
             self._vals_host = None
             self._shape_host = None
+            self._insc_host = None
             self.host()
         return outs
 
@@ -534,12 +604,35 @@ class ContourSet:
                                                ops._stream()), "demia_contour_shape")
         return vals.cpu().numpy()
 
+    def inscribed(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
+        """[M, max contours per mask, 8] inscribed descriptors (``demia_mask_inscribed`` / ``demia_crop_inscribed``; only for the
+        selected masks when ``select`` is given: the other rows are zero).  On demand the words are read where the trace's source
+        keeps them (:meth:`set_plane_words` / :meth:`set_crop_words`)."""
+        ops = self.ops
+        self.host()
+        pre = self._insc_host
+        if pre is not None and abs(getattr(self, "_i_um", um_pix) - um_pix) == 0.0:
+            return pre                                    # computed for every mask right behind the trace (launch_inscribed)
+        M, mc = self.M, self.max_count
+        vals = torch.zeros((M, mc, INSCRIBED_COLS), dtype=torch.float64, device=ops.device)
+        if select is None:
+            self._inscribed_into(vals, mc, um_pix)
+        else:
+            sel = np.asarray(list(select), dtype=np.int64)
+            part = torch.zeros((len(sel), mc, INSCRIBED_COLS), dtype=torch.float64, device=ops.device)
+            self._inscribed_into(part, mc, um_pix, sel)
+            if len(sel):
+                vals[torch.from_numpy(sel).to(ops.device)] = part
+        return vals.cpu().numpy()
+
     def records(self, um_pix: float = 1.0, measure: bool = True, select: Optional[Sequence[int]] = None, with_points: bool = True,
-                shape: bool = False):
+                shape: bool = False, inscribed: bool = False):
         """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start).  ``shape``: each
-        dict also holds ``shape``, the contour's 10 values of :meth:`shape`."""
+        dict also holds ``shape``, the contour's 10 values of :meth:`shape`; ``inscribed``: likewise ``inscribed``, the 8 values of
+        :meth:`inscribed`."""
         vals = self.measure(um_pix, select) if measure else None
         shp = self.shape(um_pix, select) if shape else None
+        ins = self.inscribed(um_pix, select) if inscribed else None
         count, info, red, used = self.host()
         pts = None
         if with_points:
@@ -560,6 +653,8 @@ class ContourSet:
                     rec["values"] = vals[m, c]
                 if shp is not None:
                     rec["shape"] = shp[m, c]
+                if ins is not None:
+                    rec["inscribed"] = ins[m, c]
                 recs.append(rec)
             if len(recs) > 1:
                 recs.sort(key=lambda r: (r["start"][1], r["start"][0]), reverse=True)

@@ -543,6 +543,36 @@ int demia_contour_shape(const int32_t* select /* [M] or NULL */, const int32_t* 
                         const int32_t* points, int M, int C, int max_points, int32_t* work_i, double um_pix,
                         double* out /* [M, out_c, 10] */, int out_c, void* stream);
 
+/* demia_mask_inscribed / demia_crop_inscribed = largest inscribed circle and distance-based thickness per external contour (not
+ * in the reference program; opt-in: inference_settings.inscribed_descriptors).  The first measurement on the mask WORDS: for a
+ * mask (frame H x W, bit set = foreground) and its contour c as the trace reports it, info[m, c] = (sx, sy, npts, offset):
+ *   background  every unset pixel of the mask, holes included, and every position outside the frame (a mask that touches the
+ *               frame edge is bounded by it);
+ *   D2(p)  for a foreground pixel p, the smallest squared Euclidean distance between the centres of p and of a background
+ *          pixel: an integer >= 1;
+ *   K(c)   the 8-connected component of the mask that contains (sx, sy).  (A component nested in a hole has no external contour
+ *          and no row; its pixels are in nobody's K but are foreground, not background, for D2.)
+ *   R2 = max D2 over K;  (cx, cy) = the raster-first pixel of K with D2 = R2 (smallest y, then smallest x; frame coordinates);
+ *   N = |K|;  SD2 = sum of D2 over K, summed in int64.  A square filling the frame maximises it at about side^4 / 24: 3.1e15
+ *   for the widest frame this project meets (16500 px), below 2^53 = 9.0e15, so the f64 holds it exactly.
+ *   out [M, out_c, 8] f64 = R2, cx, cy, N, SD2, 2 sqrt(R2) um (inscribed diameter), sqrt(SD2 / N) um (RMS distance to the
+ *       boundary), sqrt(pi R2 / N) (inscribed diameter over the diameter of the circle of area N; no um).  Values 0-4 are integers
+ *       held exactly.  Slots c >= min(count[m], out_c), masks with an empty box, and a start pixel that is not set hold zeros.
+ * The tables (bbox, count, info, out) are indexed by position t < M; the WORDS -- planes and scratch planes, or payload, room,
+ * offsets and scratch_off -- by select[t] (select == NULL: t), so a chunk of a larger set is served from the set's own words.
+ * bbox may be any superset of the tight box that is zero outside it (crops: inside the room).  The kernel reads the words and
+ * count / info and writes nothing but `out` and its scratch, under exactly the tracer's contract: a region (tight box + 1 ring,
+ * clipped to the frame) beyond the tracer's large LDS buffer works in the scratch plane of its mask (demia_mask_contours) or in
+ * scratch[scratch_off[.] ..) (demia_crop_contour_scratch); a region word outside the room is zero and is never fetched.
+ * Integer decisions only, no f32; the result does not depend on alignment, position or launch layout.  H, W <= 65535, W <= ~49000
+ * (the row buffer lives in LDS).  One launch, no allocation, capturable. */
+int demia_mask_inscribed(const int32_t* select /* [M] or NULL */, const uint32_t* masks, uint32_t* scratch, const int32_t* bbox,
+                         const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
+                         double* out /* [M, out_c, 8] */, int out_c, void* stream);
+int demia_crop_inscribed(const int32_t* select /* [M] or NULL */, const uint32_t* payload, const int32_t* room, const int64_t* offsets,
+                         const int32_t* bbox, const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
+                         double* out /* [M, out_c, 8] */, int out_c, uint32_t* scratch, const int64_t* scratch_off, void* stream);
+
 /* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
  * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
  *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at
