@@ -133,12 +133,18 @@ __global__ __launch_bounds__(256, 6) void roi_align_kernel(const RoiP p) {
     const int gh = (int)ceilf(rh / (float)p.P), gw = (int)ceilf(rw / (float)p.P);
     const float cnt = (float)max(gh * gw, 1);
 
-    // Separable form (the common case: at most 8 rows and 8 columns of feature pixels under one bin).  A bin's value is
-    // sum_samples sum_taps w f with w = (hy | ly) (hx | lx) and a sample dropped when its y OR its x is out of range, i.e.
+    // Separable form (the common case: at most 7 samples per bin and axis, so at most TW = 9 rows and 9 columns of feature
+    // pixels under one bin).  g samples span bsz (g - 1) / g <= 6 pixels and so touch at most g + 1 <= 8 pixels in exact
+    // arithmetic -- but not in f32: with bsz = 7 a coordinate can ROUND UP onto an integer (19.999999 -> 20.0: lo = 20,
+    // hi = 21) while the bin's first sample stays below one (13.999999: lo = 13), and the bin touches 9 (its 9th weight is
+    // l = 0, yet the entry must exist: the walks below run over all n).  Ten would need the samples to span 7 pixels, a
+    // pixel more than they do, which rounding steps of 1e-4 pixel at most cannot bring about: n <= g + 2 <= 9.
+    // A bin's value is sum_samples sum_taps w f with w = (hy | ly) (hx | lx) and a sample dropped when its y OR its x is out of range, i.e.
     // sum_y sum_x Wy[y] Wx[x] f[y][x] with Wy / Wx the per-row / per-column sums of the samples' weights: every feature
     // pixel under the bin is loaded ONCE instead of once per sample that touches it ((g + 1)^2 instead of 4 g^2 loads for a
     // g x g sample grid -- the kernel was bound by L1 bandwidth).  The tables are built once per ROI by the first threads.
-    __shared__ float s_w[2][14 * 8];
+    constexpr int TW = 9;                                                            // table entries per bin
+    __shared__ float s_w[2][14 * TW];
     __shared__ int s_lo[2][14], s_n[2][14];
     const bool tables = p.P <= 14 && gh >= 1 && gw >= 1 && gh <= 7 && gw <= 7;        // (block-uniform)
     if (tables) {
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(256, 6) void roi_align_kernel(const RoiP p) {
             const int dim = threadIdx.x / p.P, b = threadIdx.x - dim * p.P;          // dim 0: rows (y), 1: columns (x)
             const int g = dim == 0 ? gh : gw, size = dim == 0 ? H : W;
             const float start = dim == 0 ? rsh : rsw, bsz = dim == 0 ? bin_h : bin_w;
-            float w8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float w9[TW] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             int lo0 = 0, hi_last = -1;
             bool any = false;
             for (int pass = 0; pass < 2; ++pass) {                                   // pass 0: the range; pass 1: the weights
@@ -162,15 +168,15 @@ __global__ __launch_bounds__(256, 6) void roi_align_kernel(const RoiP p) {
                         hi_last = hi;
                     } else {
 #pragma unroll
-                        for (int k = 0; k < 8; ++k) w8[k] += (lo - lo0 == k ? h : 0.f) + (hi - lo0 == k ? l : 0.f);
+                        for (int k = 0; k < TW; ++k) w9[k] += (lo - lo0 == k ? h : 0.f) + (hi - lo0 == k ? l : 0.f);
                     }
                 }
             }
             const int n = any ? hi_last - lo0 + 1 : 0;
             s_lo[dim][b] = lo0;
-            s_n[dim][b] = n;                                                         // n <= g + 1 <= 8
+            s_n[dim][b] = n;                                                         // n <= g + 2 <= TW (see above)
 #pragma unroll
-            for (int k = 0; k < 8; ++k) s_w[dim][b * 8 + k] = w8[k];
+            for (int k = 0; k < TW; ++k) s_w[dim][b * TW + k] = w9[k];
         }
         __syncthreads();
         if (!lane_on) return;
@@ -195,7 +201,7 @@ __global__ __launch_bounds__(256, 6) void roi_align_kernel(const RoiP p) {
                 const int y0 = s_lo[0][ph], ny = s_n[0][ph];
                 float acc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                 for (int yy = 0; yy < ny; ++yy) {
-                    const float wy = s_w[0][ph * 8 + yy];
+                    const float wy = s_w[0][ph * TW + yy];
                     const int y = y0 + yy;
                     if (y == ya) {                         // (wave-uniform branches)
 #pragma unroll
@@ -209,8 +215,8 @@ __global__ __launch_bounds__(256, 6) void roi_align_kernel(const RoiP p) {
                         float t[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
                         for (int xx = 0; xx < nu; ++xx) {
                             const int ia = ux0 + xx - xa0, ib = ux0 + xx - xb0;
-                            const float wa = (unsigned)ia < (unsigned)nxa ? s_w[1][pa * 8 + ia] : 0.f;
-                            const float wb = (unsigned)ib < (unsigned)nxb ? s_w[1][(pa + 1) * 8 + ib] : 0.f;
+                            const float wa = (unsigned)ia < (unsigned)nxa ? s_w[1][pa * TW + ia] : 0.f;
+                            const float wb = (unsigned)ib < (unsigned)nxb ? s_w[1][(pa + 1) * TW + ib] : 0.f;
                             float v[4];
                             A::load(rowp + (long)xx * pixb, inv_s, v);
 #pragma unroll
