@@ -374,13 +374,31 @@ class CropMaskSet:
             self._insc_scratch = got
         return got
 
+    def skeleton_scratch(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(second scratch words, ``scratch2_off`` [M] i64) on the device for ``demia_crop_skeleton`` over masks of this set, sized
+        from the rooms alone (``demia_crop_skeleton_scratch``: one more padded room region per mask whose region exceeds the large LDS
+        buffer) and made on first use: a set nobody asks for a skeleton stays without them."""
+        got = self.__dict__.get("_skel_scratch")
+        if got is None:
+            M = len(self)
+            off = np.zeros(max(M, 1), dtype=np.int64)
+            total = int(self.ops.lib.demia_crop_skeleton_scratch(self.room_h.ctypes.data, M, self.hw[0], self.hw[1], off.ctypes.data))
+            if total:
+                got = (torch.empty((total,), dtype=torch.int32, device=self.ops.device), self.ops.upload(off[:M]))
+            else:
+                t = torch.empty((2,), dtype=torch.int32, device=self.ops.device)      # (never read)
+                got = (t, t)
+            self._skel_scratch = got
+        return got
+
     def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None,
               keep_words: bool = False) -> ContourSet:
         """``MaskOps.trace`` over ALL masks of the set, read where they are (``demia_crop_contours_wl``): no plane, no chunk, no
         wait.  The point pool is sized as ``MaskOps.trace`` sizes it from ``total_area`` (the masks' pixel count, or counts, on the
         host), else from the mask count as ``trace_chunks`` does -- a caller that meets an overflow traces again with the areas.
         ``scratch``: the caller's own i32 words, at least :meth:`contour_scratch`'s total (default: allocated here).
-        ``keep_words``: the contour set remembers this set as the source of its words (``ContourSet.launch_inscribed``)."""
+        ``keep_words``: the contour set remembers this set as the source of its words (``ContourSet.launch_inscribed``,
+        ``ContourSet.launch_skeleton``)."""
         ops, M = self.ops, len(self)
         H, W = self.hw
         if max_points is None:
@@ -409,23 +427,26 @@ class CropMaskSet:
         return cs
 
     def contours(self, max_contours: int = 64, max_points: Optional[int] = None, um_pix: float = 1.0, measure: bool = True, total_area=None,
-                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False):
+                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False, skeleton: bool = False):
         """``MaskOps.contours`` for this set: one trace, the measurements of every mask's first four contours right behind it, ONE
         fetch (``extra`` rides on it); same records, same return value.  Without ``total_area`` the point pool is sized from the
         mask count; if it overflows, the set is traced again with the pool sized from its own (device) areas -- one more wait.
         ``shape``: the records also carry the shape descriptors (``ContourSet.launch_shape``), in that same fetch; ``inscribed``:
-        likewise the inscribed-circle descriptors (``ContourSet.launch_inscribed``, read from the words in place)."""
+        likewise the inscribed-circle descriptors (``ContourSet.launch_inscribed``, read from the words in place); ``skeleton``: and
+        the skeleton descriptors (``ContourSet.launch_skeleton``)."""
         if len(self) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
 
         def run(area):
-            cs = self.trace(max_contours, max_points, total_area=area, keep_words=inscribed)
+            cs = self.trace(max_contours, max_points, total_area=area, keep_words=inscribed or skeleton)
             if measure:
                 cs.launch_measure(um_pix, slots=4)
             if shape:
                 cs.launch_shape(um_pix, slots=4)
             if inscribed:
                 cs.launch_inscribed(um_pix, slots=4)
+            if skeleton:
+                cs.launch_skeleton(um_pix, slots=4)
             return cs, cs.fetch(extra=extra, with_points=True)
         try:
             cs, got = run(total_area)
@@ -433,7 +454,7 @@ class CropMaskSet:
             if "overflow" not in str(e) or total_area is not None or max_points is not None:
                 raise
             cs, got = run(int(self.area.sum().item()))
-        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed)
+        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed, skeleton=skeleton)
         return recs if extra is None else (recs, list(got))
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
@@ -499,7 +520,7 @@ def crop_planes(ops: MaskOps, hw: Tuple[int, int]) -> CropPlanes:
 
 
 def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256, um_pix: Optional[float] = None,
-                 total_area: Optional[np.ndarray] = None, shape: bool = False, inscribed: bool = False):
+                 total_area: Optional[np.ndarray] = None, shape: bool = False, inscribed: bool = False, skeleton: bool = False):
     """The contour trace of every mask of ``cset`` (``MaskOps.trace``, unchanged), ``planes.chunk`` masks at a time through the
     pool: yields (first, n, ContourSet) per chunk, each with its unpack + trace (+ the measurements of its first contours when
     ``um_pix`` is given) enqueued and NOT waited for, and with the NEXT chunk already enqueued behind it -- the pool is reused
@@ -509,7 +530,8 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
     meets an overflow traces that chunk again).  ``shape``: with ``um_pix``, the shape descriptors are enqueued behind the
     measurements (``ContourSet.launch_shape``).  ``inscribed``: every chunk's contour set remembers ``cset`` and the chunk's first mask
     as the source of its words, and with ``um_pix`` the inscribed descriptors are enqueued too (``ContourSet.launch_inscribed``):
-    they read the set's PAYLOAD, never the pool, which the next chunk overwrites -- so does an on-demand ``inscribed()`` later."""
+    they read the set's PAYLOAD, never the pool, which the next chunk overwrites -- so does an on-demand ``inscribed()`` later.
+    ``skeleton``: the same for the skeleton descriptors (``ContourSet.launch_skeleton`` / ``skeleton()``)."""
     ops = cset.ops
     ops.set_frame_width(cset.hw[1])
     pending = None
@@ -521,7 +543,7 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
         else:
             mp = int(min(4096 * n + (1 << 16), 1 << 26))
         cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], max_points=mp, scratch=planes.scratch[:n])
-        if inscribed:
+        if inscribed or skeleton:
             cs.set_crop_words(cset, f)
         if um_pix is not None:
             cs.launch_measure(um_pix, slots=4)
@@ -529,6 +551,8 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
                 cs.launch_shape(um_pix, slots=4)
             if inscribed:
                 cs.launch_inscribed(um_pix, slots=4)
+            if skeleton:
+                cs.launch_skeleton(um_pix, slots=4)
         if pending is not None:
             yield pending
         pending = (f, n, cs)
@@ -537,19 +561,20 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
 
 
 def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, total_area: Optional[np.ndarray] = None,
-                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256, shape: bool = False, inscribed: bool = False):
+                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256, shape: bool = False, inscribed: bool = False,
+                  skeleton: bool = False):
     """``MaskOps.contours`` (trace + the 12 measurements, records in OpenCV's order) for a crop-framed set, chunk by chunk
     through the plane pool.  ``extra``: int32 device tensors that come to the host with the FIRST chunk's tables.
     ``total_area``: the masks' pixel counts on the host (sizes the point pools); without them the pools are sized from the mask
     count, and a chunk whose pool overflows is unpacked and traced again with the pool sized from its own (device) areas.
     ``shape``: the records also carry the shape descriptors, in each chunk's one fetch; ``inscribed``: likewise the inscribed-circle
-    descriptors, read from the set's payload.
+    descriptors, read from the set's payload; ``skeleton``: and the skeleton descriptors.
     Returns (records per mask, host arrays of ``extra`` or None); one device-to-host wait per chunk."""
     ops = cset.ops
     area = None if total_area is None else np.asarray(total_area).reshape(-1)
     recs, got = [], None
     for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area, shape=shape,
-                                                  inscribed=inscribed)):
+                                                  inscribed=inscribed, skeleton=skeleton)):
         ex = extra if k == 0 else None
         try:
             g = cs.fetch(extra=ex, with_points=True)
@@ -562,13 +587,16 @@ def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, to
             cs.launch_measure(um_pix, slots=4)
             if shape:
                 cs.launch_shape(um_pix, slots=4)
-            if inscribed:
+            if inscribed or skeleton:
                 cs.set_crop_words(cset, f)
+            if inscribed:
                 cs.launch_inscribed(um_pix, slots=4)
+            if skeleton:
+                cs.launch_skeleton(um_pix, slots=4)
             g = cs.fetch(extra=ex, with_points=True)
         if k == 0:
             got = list(g)
-        recs.extend(cs.records(um_pix=um_pix, measure=True, shape=shape, inscribed=inscribed))
+        recs.extend(cs.records(um_pix=um_pix, measure=True, shape=shape, inscribed=inscribed, skeleton=skeleton))
     if extra is not None and got is None:
         got = [e.cpu().numpy() for e in extra]
     return recs, (got if extra is not None else None)

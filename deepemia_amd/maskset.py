@@ -22,6 +22,7 @@ _WORKLISTS = os.environ.get("DEEPEMIA_MASK_WORKLISTS", "1") != "0"
 
 SHAPE_COLS = 10          # values per contour of demia_contour_shape
 INSCRIBED_COLS = 8       # values per contour of demia_mask_inscribed / demia_crop_inscribed
+SKELETON_COLS = 8        # values per contour of demia_mask_skeleton / demia_crop_skeleton
 
 
 class PlanePool:
@@ -318,7 +319,8 @@ class MaskOps:
         superset of the tight boxes) and ``total_area`` (sizes the point pool) save a reduction when known.  ``scratch``:
         the caller's own planes of ``packed``'s shape for the regions that do not fit in LDS (default: allocated here).
         ``keep_words``: the set remembers the planes, the boxes and the scratch it was traced from (``ContourSet.launch_inscribed``
-        reads the words again); the caller leaves them unchanged for as long as it asks the set for inscribed values."""
+        and ``ContourSet.launch_skeleton`` read the words again); the caller leaves them unchanged for as long as it asks the set
+        for inscribed or skeleton values."""
         M, H, wpr = packed.shape
         W = self._w(packed)
         if bbox is None or (max_points is None and total_area is None):
@@ -341,16 +343,18 @@ class MaskOps:
 
     def contours(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
                  um_pix: float = 1.0, measure: bool = True, bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None,
-                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False):
+                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False,
+                 skeleton: bool = False):
         """Per mask: external contours in OpenCV's order, with area, perimeter and the 12 measurement
         values.  Returns a list (per mask) of lists of dicts with keys ``points`` (P, 2) int32,
         ``area``, ``perimeter`` and (if ``measure``) ``values`` (12,) float64.  ``extra``: int32 device tensors that come to the
         host in the SAME copy (e.g. the cropped words the RLE texts are made of); the call then returns (records, host arrays).
         ``shape``: also ``shape`` (10,) float64, the convex-hull descriptors of ``demia_contour_shape``, in that same copy.
-        ``inscribed``: also ``inscribed`` (8,) float64, the inscribed-circle descriptors of ``demia_mask_inscribed``, likewise."""
+        ``inscribed``: also ``inscribed`` (8,) float64, the inscribed-circle descriptors of ``demia_mask_inscribed``, likewise;
+        ``skeleton``: also ``skeleton`` (8,) float64, the skeleton descriptors of ``demia_mask_skeleton``, likewise."""
         if int(packed.shape[0]) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
-        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area, keep_words=inscribed)
+        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area, keep_words=inscribed or skeleton)
         # ONE device-to-host wait: the measurements of every mask's first contours are enqueued right behind the trace and come
         # over with the counts, the contour tables and the points (a mask with more than four contours falls back to the
         # sliced copies of ContourSet.host(): five waits, rare)
@@ -360,9 +364,26 @@ class MaskOps:
             cs.launch_shape(um_pix, slots=4)
         if inscribed:
             cs.launch_inscribed(um_pix, slots=4)
+        if skeleton:
+            cs.launch_skeleton(um_pix, slots=4)
         got = cs.fetch(extra=extra, with_points=True)
-        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed)
+        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed, skeleton=skeleton)
         return recs if extra is None else (recs, list(got))
+
+
+    def skeleton(self, packed: torch.Tensor, bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The morphological skeleton (Guo-Hall thinning; ``demia_mask_skeleton`` in its thin-only form) of every mask, as packed
+        planes of ``packed``'s shape; ``packed`` is left as it is.  ``bbox``: any superset of the tight boxes, when known."""
+        M, H, wpr = packed.shape
+        out = torch.zeros_like(packed)
+        if M == 0:
+            return out
+        if bbox is None:
+            _, bbox = self.area_bbox(packed)
+        scratch, scratch2 = torch.empty_like(packed), torch.empty_like(packed)      # only touched by regions that do not fit in LDS
+        _lib.check(self.lib.demia_mask_skeleton(0, _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bbox), 0, 0, M, H, self._w(packed), 1, 1.0,
+                                                0, 0, _lib.ptr(scratch2), _lib.ptr(out), self._stream()), "demia_mask_skeleton")
+        return out
 
 
 class ContourSet:
@@ -383,6 +404,9 @@ class ContourSet:
         self._words = None                # where the traced words live (set_plane_words / set_crop_words): what launch_inscribed reads
         self._insc_dev = None             # [M, slots, 8] inscribed descriptors enqueued by launch_inscribed
         self._insc_host = None
+        self._skel_dev = None             # [M, slots, 8] skeleton descriptors enqueued by launch_skeleton
+        self._skel_host = None
+        self._skel_scratch2 = None        # planes: the second scratch of demia_mask_skeleton, made by the first launch
         self.blocking_point_copies = 0    # times records() had to fetch the points with a device-to-host copy of its own
 
     def host(self):
@@ -476,10 +500,56 @@ class ContourSet:
         self._insc_dev = torch.zeros((self.M, self._islots, INSCRIBED_COLS), dtype=torch.float64, device=self.ops.device)
         self._inscribed_into(self._insc_dev, self._islots, um_pix)
 
+    def _skeleton_into(self, out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray] = None) -> None:
+        """One launch of ``demia_mask_skeleton`` / ``demia_crop_skeleton`` into ``out`` [n, out_c, 8]: every mask, or the
+        positions ``sel`` -- their table rows are gathered, their words are read where they are (the entry's ``select``).  The
+        second scratch (planes: one more plane per mask, here; crops: ``CropMaskSet.skeleton_scratch``) is made on first use."""
+        ops = self.ops
+        if self._words is None:
+            raise RuntimeError("skeleton descriptors: the trace did not keep its words (trace(..., keep_words=True))")
+        n = self.M if sel is None else len(sel)
+        if n == 0:
+            return
+        count, info, sel_d, idx = self.count, self.info, None, None
+        if sel is not None:
+            sel_d = ops.upload(np.ascontiguousarray(sel, dtype=np.int32))
+            idx = sel_d.to(torch.int64)
+            count, info = self.count.index_select(0, idx), self.info.index_select(0, idx)
+        if self._words[0] == "plane":
+            _, packed, bbox, scratch, W = self._words
+            bb = bbox if idx is None else bbox.index_select(0, idx)
+            if self._skel_scratch2 is None:
+                self._skel_scratch2 = torch.empty_like(packed)   # only touched by regions that do not fit in LDS
+            _lib.check(ops.lib.demia_mask_skeleton(_lib.ptr(sel_d), _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bb), _lib.ptr(count),
+                                                   _lib.ptr(info), n, int(packed.shape[1]), W, self.C, float(um_pix), _lib.ptr(out),
+                                                   int(out_c), _lib.ptr(self._skel_scratch2), 0, ops._stream()), "demia_mask_skeleton")
+        else:
+            _, cset, first = self._words
+            bb = cset.bbox[first:first + self.M]
+            if idx is not None:
+                bb, sel_d = bb.index_select(0, idx), sel_d + first
+            elif first:
+                sel_d = torch.arange(first, first + self.M, dtype=torch.int32, device=ops.device)
+            scratch, off_d = cset.inscribed_scratch()
+            scratch2, off2_d = cset.skeleton_scratch()
+            _lib.check(ops.lib.demia_crop_skeleton(_lib.ptr(sel_d), _lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets),
+                                                   _lib.ptr(bb), _lib.ptr(count), _lib.ptr(info), n, cset.hw[0], cset.hw[1], self.C,
+                                                   float(um_pix), _lib.ptr(out), int(out_c), _lib.ptr(scratch), _lib.ptr(off_d),
+                                                   _lib.ptr(scratch2), _lib.ptr(off2_d), 0, ops._stream()), "demia_crop_skeleton")
+
+    def launch_skeleton(self, um_pix: float = 1.0, slots: int = 4) -> None:
+        """:meth:`launch_measure` for the skeleton descriptors (``demia_mask_skeleton`` / ``demia_crop_skeleton``): the first
+        ``slots`` contours of EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one copy,
+        behind the inscribed values.  (Masks with more contours than ``slots`` are computed again by :meth:`skeleton` on demand.)"""
+        self._kslots, self._k_um = min(int(slots), self.C), float(um_pix)
+        self._skel_dev = torch.zeros((self.M, self._kslots, SKELETON_COLS), dtype=torch.float64, device=self.ops.device)
+        self._skeleton_into(self._skel_dev, self._kslots, um_pix)
+
     def fetch(self, extra: Optional[Sequence[torch.Tensor]] = None, with_points: bool = False):
         """ONE device-to-host wait for everything the host decides on: counters, contour counts, the first ``slots``
         contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran, shape
-        descriptors when :meth:`launch_shape` ran, inscribed descriptors when :meth:`launch_inscribed` ran) and the
+        descriptors when :meth:`launch_shape` ran, inscribed descriptors when :meth:`launch_inscribed` ran, skeleton descriptors
+        when :meth:`launch_skeleton` ran) and the
         int32 device tensors in ``extra`` (returned as numpy arrays).  Falls back to the sliced copy of :meth:`host` when a
         mask has more contours than the slots fetched.  ``with_points``: the contour POINTS come over in the same copy --
         how many are in use is only known after the wait, so the copy takes as many as the previous trace of this
@@ -496,6 +566,8 @@ class ContourSet:
             f64.append(self._shape_dev.reshape(-1))
         if self._insc_dev is not None:
             f64.append(self._insc_dev.reshape(-1))
+        if self._skel_dev is not None:
+            f64.append(self._skel_dev.reshape(-1))
         extra = list(extra or [])
         parts += [e.reshape(-1) for e in extra]
         n_pts = min(int(getattr(self.ops, "_points_hint", 0)), self.max_points) if with_points else 0
@@ -537,14 +609,20 @@ class ContourSet:
                 if mc <= ks:
                     self._shape_host = d[dpos:dpos + M * ks * SHAPE_COLS].reshape(M, ks, SHAPE_COLS)[:, :mc]
                 dpos += M * ks * SHAPE_COLS
-            if self._insc_dev is not None and mc <= self._islots:
+            if self._insc_dev is not None:
                 ki = self._islots
-                self._insc_host = d[dpos:dpos + M * ki * INSCRIBED_COLS].reshape(M, ki, INSCRIBED_COLS)[:, :mc]
+                if mc <= ki:
+                    self._insc_host = d[dpos:dpos + M * ki * INSCRIBED_COLS].reshape(M, ki, INSCRIBED_COLS)[:, :mc]
+                dpos += M * ki * INSCRIBED_COLS
+            if self._skel_dev is not None and mc <= self._kslots:
+                kk = self._kslots
+                self._skel_host = d[dpos:dpos + M * kk * SKELETON_COLS].reshape(M, kk, SKELETON_COLS)[:, :mc]
         else:                                                     # a mask with many contours: the general (two-wait) path
             self._host = None
             self._vals_host = None
             self._shape_host = None
             self._insc_host = None
+            self._skel_host = None
             self.host()
         return outs
 
@@ -625,14 +703,36 @@ class ContourSet:
                 vals[torch.from_numpy(sel).to(ops.device)] = part
         return vals.cpu().numpy()
 
+    def skeleton(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
+        """[M, max contours per mask, 8] skeleton descriptors (``demia_mask_skeleton`` / ``demia_crop_skeleton``; only for the
+        selected masks when ``select`` is given: the other rows are zero).  On demand the words are read where the trace's source
+        keeps them (:meth:`set_plane_words` / :meth:`set_crop_words`)."""
+        ops = self.ops
+        self.host()
+        pre = self._skel_host
+        if pre is not None and abs(getattr(self, "_k_um", um_pix) - um_pix) == 0.0:
+            return pre                                    # computed for every mask right behind the trace (launch_skeleton)
+        M, mc = self.M, self.max_count
+        vals = torch.zeros((M, mc, SKELETON_COLS), dtype=torch.float64, device=ops.device)
+        if select is None:
+            self._skeleton_into(vals, mc, um_pix)
+        else:
+            sel = np.asarray(list(select), dtype=np.int64)
+            part = torch.zeros((len(sel), mc, SKELETON_COLS), dtype=torch.float64, device=ops.device)
+            self._skeleton_into(part, mc, um_pix, sel)
+            if len(sel):
+                vals[torch.from_numpy(sel).to(ops.device)] = part
+        return vals.cpu().numpy()
+
     def records(self, um_pix: float = 1.0, measure: bool = True, select: Optional[Sequence[int]] = None, with_points: bool = True,
-                shape: bool = False, inscribed: bool = False):
+                shape: bool = False, inscribed: bool = False, skeleton: bool = False):
         """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start).  ``shape``: each
         dict also holds ``shape``, the contour's 10 values of :meth:`shape`; ``inscribed``: likewise ``inscribed``, the 8 values of
-        :meth:`inscribed`."""
+        :meth:`inscribed`, and ``skeleton``: ``skeleton``, the 8 values of :meth:`skeleton`."""
         vals = self.measure(um_pix, select) if measure else None
         shp = self.shape(um_pix, select) if shape else None
         ins = self.inscribed(um_pix, select) if inscribed else None
+        skl = self.skeleton(um_pix, select) if skeleton else None
         count, info, red, used = self.host()
         pts = None
         if with_points:
@@ -655,6 +755,8 @@ class ContourSet:
                     rec["shape"] = shp[m, c]
                 if ins is not None:
                     rec["inscribed"] = ins[m, c]
+                if skl is not None:
+                    rec["skeleton"] = skl[m, c]
                 recs.append(rec)
             if len(recs) > 1:
                 recs.sort(key=lambda r: (r["start"][1], r["start"][0]), reverse=True)

@@ -573,6 +573,54 @@ int demia_crop_inscribed(const int32_t* select /* [M] or NULL */, const uint32_t
                          const int32_t* bbox, const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
                          double* out /* [M, out_c, 8] */, int out_c, uint32_t* scratch, const int64_t* scratch_off, void* stream);
 
+/* demia_mask_skeleton / demia_crop_skeleton = the morphological skeleton of a mask and, per external contour, its length, end and
+ * branch points (not in the reference program; opt-in: inference_settings.skeleton_descriptors).  The second measurement on the
+ * mask WORDS.  Background is every unset pixel of the mask and every position outside the frame, as for demia_mask_inscribed.
+ * For a pixel P, with y downwards, p2 = N, p3 = NE, p4 = E, p5 = SE, p6 = S, p7 = SW, p8 = W, p9 = NW.
+ *   S   the skeleton of the mask: Guo-Hall thinning (1989, algorithm A1), fully parallel.  With
+ *         C  = (!p2 & (p3|p4)) + (!p4 & (p5|p6)) + (!p6 & (p7|p8)) + (!p8 & (p9|p2)),
+ *         N1 = (p9|p2) + (p3|p4) + (p5|p6) + (p7|p8),  N2 = (p2|p3) + (p4|p5) + (p6|p7) + (p8|p9),  N = min(N1, N2),
+ *       a sub-iteration deletes, simultaneously, every set pixel with C == 1, 2 <= N <= 3 and m == 0, all pixels evaluated on the
+ *       state before it; sub-iteration 0 uses m = (p6 | p7 | !p9) & p8, sub-iteration 1 uses m = (p2 | p3 | !p5) & p4.  The pair
+ *       (0, 1) is repeated until a whole pair deletes nothing.  S is a function of the mask alone.  Distinct 8-connected
+ *       components are never 8-adjacent, so thinning the mask once equals the union of thinning each component.
+ * Per contour c as the trace reports it, info[m, c] = (sx, sy, npts, offset):
+ *   K(c)   the 8-connected component of the mask that contains (sx, sy);  Sk = S & K;  Npix = |K|;
+ *   n      |Sk|;
+ *   n4     pairs of horizontally or vertically adjacent pixels of Sk;
+ *   nd     diagonal links: pairs (x, y), (x+1, y+1) both in Sk with neither (x+1, y) nor (x, y+1) in Sk, and pairs (x, y),
+ *          (x-1, y+1) both in Sk with neither (x-1, y) nor (x, y+1) in Sk;
+ *   ends   pixels of Sk with exactly one 8-neighbour in Sk;
+ *   branches  pixels of Sk whose cyclic sequence p2, p3, ..., p9, p2 (taken in Sk) has three or more 0 -> 1 transitions.
+ *   out [M, out_c, 8] f64 = n, n4, nd, ends, branches, Npix, (n4 + sqrt(2) nd) um (skeleton length), (Npix / n) um (mean width).
+ *       Values 0-5 are integers held exactly.  Slots c >= min(count[m], out_c), masks with an empty box, and a start pixel that is
+ *       not set hold zeros.  A component nested in a hole has no row.
+ * Tables and words are indexed as for demia_mask_inscribed (tables by position t, words and scratches by select[t]); bbox may be
+ * any superset of the tight box that is zero outside it (crops: inside the room).
+ *   skel_out  NULL, or a buffer laid out like the source words ([., H, wpr] planes, or a payload with the same room and offsets):
+ *       the kernel writes S into every word of the mask's region (tight box + 1 ring, clipped to the frame; crops: the words of it
+ *       that lie in the room) and nothing outside it; a mask with an empty box writes nothing.
+ *   count == NULL, info == NULL and out == NULL: the entry only thins into skel_out (C and out_c are ignored).
+ * Scratch: a region up to the tracer's large LDS buffer (8192 words, padded) works in LDS, three buffers.  A larger one reads
+ * the mask in place and works
+ *   planes: in the scratch plane of its mask (`scratch`, as demia_mask_contours) and in the plane of its mask in `scratch2`, both
+ *           [., H, wpr] and indexed like the planes; only the region's words of either are written;
+ *   crops:  in scratch[scratch_off[.] ..) under the tracer's contract (demia_crop_contour_scratch: two padded room regions) and in
+ *           scratch2[scratch2_off[.] ..), which demia_crop_skeleton_scratch sizes from the HOST copy of the rooms alone: it fills
+ *           scratch2_off [M] i64 and returns the total words, ONE padded region of the room for a mask whose room region exceeds
+ *           the large LDS buffer, 0 for every other mask.  With a total of 0 the pointers are not read (any non-NULL will do).
+ * A region word outside the room is zero and is never fetched.  The kernel reads the words and count / info and writes nothing but
+ * out, skel_out and its scratches.  Boolean word operations and popcounts only: no per-pixel loop, no f32; the result does not
+ * depend on alignment, position or launch layout.  H x ceil(W / 32) < 2^26.  One launch, no allocation, capturable. */
+int demia_mask_skeleton(const int32_t* select /* [M] or NULL */, const uint32_t* masks, uint32_t* scratch, const int32_t* bbox,
+                        const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
+                        double* out /* [M, out_c, 8] */, int out_c, uint32_t* scratch2, uint32_t* skel_out, void* stream);
+int64_t demia_crop_skeleton_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch2_off);
+int demia_crop_skeleton(const int32_t* select /* [M] or NULL */, const uint32_t* payload, const int32_t* room, const int64_t* offsets,
+                        const int32_t* bbox, const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
+                        double* out /* [M, out_c, 8] */, int out_c, uint32_t* scratch, const int64_t* scratch_off, uint32_t* scratch2,
+                        const int64_t* scratch2_off, uint32_t* skel_out, void* stream);
+
 /* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
  * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
  *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at

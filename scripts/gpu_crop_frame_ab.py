@@ -4,7 +4,8 @@ tile placement, 0.4 merges, 0.7 cross-class pass, spatial constraints), the RLE 
 process, the frames alternating (full, crop, full, crop, ...; the fourth argument names other frames to alternate, e.g.
 full,crop,crop_direct), same models, same image, same box.  A frame written as ``<frame>+shape`` runs with
 `inference_settings.shape_descriptors: true` (e.g. crop_direct,crop_direct+shape: the setting off and on, alternating), one written
-as ``<frame>+inscribed`` with `inference_settings.inscribed_descriptors: true`; both suffixes may follow one frame.
+as ``<frame>+inscribed`` with `inference_settings.inscribed_descriptors: true`, one written as ``<frame>+skeleton`` with
+`inference_settings.skeleton_descriptors: true`; several suffixes may follow one frame.
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
@@ -57,6 +58,7 @@ metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
 pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f.split("+")[0]), st.global_config) for f in frames}
 shape_on = {f: "shape" in f.split("+")[1:] for f in frames}
 inscribed_on = {f: "inscribed" in f.split("+")[1:] for f in frames}
+skeleton_on = {f: "skeleton" in f.split("+")[1:] for f in frames}
 host_copies = [0]
 for _name in ("cpu", "item"):
     def _counted(self, *a, _orig=getattr(torch.Tensor, _name), **k):
@@ -64,7 +66,7 @@ for _name in ("cpu", "item"):
         return _orig(self, *a, **k)
     setattr(torch.Tensor, _name, _counted)
 from deepemia_amd.maskset import ContourSet
-fallbacks = [0]                      # fetches that met a mask with more contours than slots: measurements (shape, inscribed values) on demand
+fallbacks = [0]                      # fetches that met a mask with more contours than slots: measurements (shape, inscribed, skeleton values) on demand
 def _fetch(self, *a, _orig=ContourSet.fetch, **k):
     out = _orig(self, *a, **k)
     fallbacks[0] += self.max_count > min(getattr(self, "_mslots", 4), self.C)
@@ -74,7 +76,7 @@ small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes(
 pipes[frames[0]].drop_cached("big.tif")
 
 
-def one_image(pipe, shape=False, inscribed=False):
+def one_image(pipe, shape=False, inscribed=False, skeleton=False):
     """process_image of run_inference for this image: instances, RLE texts, measurement rows."""
     name = "big.tif"
     pipe.begin_image_stats()
@@ -88,7 +90,7 @@ def one_image(pipe, shape=False, inscribed=False):
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, shape=shape, inscribed=inscribed)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, shape=shape, inscribed=inscribed, skeleton=skeleton)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     pipe.drop_cached(name)
     return n, rows, texts, pipe.end_image_stats((size, size))
@@ -102,10 +104,10 @@ for rep in range(reps):
         torch.cuda.reset_peak_memory_stats()
         w0, c0, f0 = pipe.d2h_waits, host_copies[0], fallbacks[0]
         t0 = time.perf_counter()
-        n, rows, texts, stats = one_image(pipe, shape_on[frame], inscribed_on[frame])
+        n, rows, texts, stats = one_image(pipe, shape_on[frame], inscribed_on[frame], skeleton_on[frame])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert all(len(r) == 20 + 7 * shape_on[frame] + 6 * inscribed_on[frame] for r in rows)
+        assert all(len(r) == 20 + 7 * shape_on[frame] + 6 * inscribed_on[frame] + 5 * skeleton_on[frame] for r in rows)
         h = hashlib.sha256(("\n".join(texts) + repr([r[:20] for r in rows])).encode()).hexdigest()
         digest.setdefault(frame, h)
         assert digest[frame] == h, "a repetition wrote other rows"
