@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import _WORKLISTS, ContourSet, MaskOps, PlanePool
+from .maskset import _WORKLISTS, ContourSet, MaskOps, PlanePool, reads_words
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
@@ -360,36 +360,34 @@ class CropMaskSet:
         total = int(self.ops.lib.demia_crop_contour_scratch(self.room_h.ctypes.data, M, self.hw[0], self.hw[1], off.ctypes.data))
         return off[:M], total
 
-    def inscribed_scratch(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(scratch words, ``scratch_off`` [M] i64) on the device for ``demia_crop_inscribed`` over masks of this set, sized by
-        :meth:`contour_scratch` -- the tracer's contract -- and made on first use: a set nobody asks stays without them."""
-        got = self.__dict__.get("_insc_scratch")
+    def _lazy_scratch(self, key: str, sizer) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scratch words, ``scratch_off`` [M] i64) on the device, sized by ``sizer() -> (offsets on the host, total words)`` and
+        made on first use: a set nobody asks stays without them."""
+        got = self.__dict__.get(key)
         if got is None:
-            off_h, total = self.contour_scratch()
+            off_h, total = sizer()
             if total:
                 got = (torch.empty((total,), dtype=torch.int32, device=self.ops.device), self.ops.upload(off_h))
             else:
                 t = torch.empty((2,), dtype=torch.int32, device=self.ops.device)      # (never read)
                 got = (t, t)
-            self._insc_scratch = got
+            self.__dict__[key] = got
         return got
 
+    def inscribed_scratch(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The scratch of the word entries (``demia_crop_inscribed``, ``demia_crop_skeleton``) over masks of this set, sized by
+        :meth:`contour_scratch` -- the tracer's contract."""
+        return self._lazy_scratch("_insc_scratch", self.contour_scratch)
+
     def skeleton_scratch(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(second scratch words, ``scratch2_off`` [M] i64) on the device for ``demia_crop_skeleton`` over masks of this set, sized
-        from the rooms alone (``demia_crop_skeleton_scratch``: one more padded room region per mask whose region exceeds the large LDS
-        buffer) and made on first use: a set nobody asks for a skeleton stays without them."""
-        got = self.__dict__.get("_skel_scratch")
-        if got is None:
+        """The second scratch of ``demia_crop_skeleton`` over masks of this set, sized from the rooms alone
+        (``demia_crop_skeleton_scratch``: one more padded room region per mask whose region exceeds the large LDS buffer)."""
+        def sizer():
             M = len(self)
             off = np.zeros(max(M, 1), dtype=np.int64)
             total = int(self.ops.lib.demia_crop_skeleton_scratch(self.room_h.ctypes.data, M, self.hw[0], self.hw[1], off.ctypes.data))
-            if total:
-                got = (torch.empty((total,), dtype=torch.int32, device=self.ops.device), self.ops.upload(off[:M]))
-            else:
-                t = torch.empty((2,), dtype=torch.int32, device=self.ops.device)      # (never read)
-                got = (t, t)
-            self._skel_scratch = got
-        return got
+            return off[:M], total
+        return self._lazy_scratch("_skel_scratch", sizer)
 
     def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None,
               keep_words: bool = False) -> ContourSet:
@@ -397,8 +395,7 @@ class CropMaskSet:
         wait.  The point pool is sized as ``MaskOps.trace`` sizes it from ``total_area`` (the masks' pixel count, or counts, on the
         host), else from the mask count as ``trace_chunks`` does -- a caller that meets an overflow traces again with the areas.
         ``scratch``: the caller's own i32 words, at least :meth:`contour_scratch`'s total (default: allocated here).
-        ``keep_words``: the contour set remembers this set as the source of its words (``ContourSet.launch_inscribed``,
-        ``ContourSet.launch_skeleton``)."""
+        ``keep_words``: the contour set remembers this set as the source of its words (the word families of ``FAMILIES``)."""
         ops, M = self.ops, len(self)
         H, W = self.hw
         if max_points is None:
@@ -427,26 +424,19 @@ class CropMaskSet:
         return cs
 
     def contours(self, max_contours: int = 64, max_points: Optional[int] = None, um_pix: float = 1.0, measure: bool = True, total_area=None,
-                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False, skeleton: bool = False):
+                 extra: Optional[Sequence[torch.Tensor]] = None, descriptors: Sequence[str] = ()):
         """``MaskOps.contours`` for this set: one trace, the measurements of every mask's first four contours right behind it, ONE
         fetch (``extra`` rides on it); same records, same return value.  Without ``total_area`` the point pool is sized from the
         mask count; if it overflows, the set is traced again with the pool sized from its own (device) areas -- one more wait.
-        ``shape``: the records also carry the shape descriptors (``ContourSet.launch_shape``), in that same fetch; ``inscribed``:
-        likewise the inscribed-circle descriptors (``ContourSet.launch_inscribed``, read from the words in place); ``skeleton``: and
-        the skeleton descriptors (``ContourSet.launch_skeleton``)."""
+        ``descriptors``: the records also carry the named families of ``FAMILIES`` (``ContourSet.launch``), in that same fetch; the
+        word families read the words in place."""
+        keep_words = reads_words(descriptors)
         if len(self) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
 
         def run(area):
-            cs = self.trace(max_contours, max_points, total_area=area, keep_words=inscribed or skeleton)
-            if measure:
-                cs.launch_measure(um_pix, slots=4)
-            if shape:
-                cs.launch_shape(um_pix, slots=4)
-            if inscribed:
-                cs.launch_inscribed(um_pix, slots=4)
-            if skeleton:
-                cs.launch_skeleton(um_pix, slots=4)
+            cs = self.trace(max_contours, max_points, total_area=area, keep_words=keep_words)
+            cs.launch_all(um_pix, measure, descriptors, slots=4)
             return cs, cs.fetch(extra=extra, with_points=True)
         try:
             cs, got = run(total_area)
@@ -454,7 +444,7 @@ class CropMaskSet:
             if "overflow" not in str(e) or total_area is not None or max_points is not None:
                 raise
             cs, got = run(int(self.area.sum().item()))
-        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed, skeleton=skeleton)
+        recs = cs.records(um_pix=um_pix, measure=measure, descriptors=descriptors)
         return recs if extra is None else (recs, list(got))
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
@@ -519,40 +509,41 @@ def crop_planes(ops: MaskOps, hw: Tuple[int, int]) -> CropPlanes:
     return cp
 
 
+def _trace_chunk(cset: CropMaskSet, planes: CropPlanes, f: int, n: int, max_contours: int, um_pix: Optional[float], descriptors: Sequence[str],
+                 **pool_size) -> ContourSet:
+    """Masks ``[f, f + n)`` of ``cset`` unpacked into the pool and traced there, with the 12 measurements and the families
+    ``descriptors`` enqueued behind the trace when ``um_pix`` is given; nothing is waited for.  ``pool_size``: ``max_points`` or
+    ``total_area`` of ``MaskOps.trace``.  A word family makes the contour set remember ``cset`` and ``f`` as the source of its
+    words: it reads the set's PAYLOAD -- at the launch here and on demand later -- never the pool, which the next chunk overwrites."""
+    pl = cset.unpack_pooled(planes.pool, f, n)
+    cs = cset.ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], scratch=planes.scratch[:n], **pool_size)
+    if reads_words(descriptors):
+        cs.set_crop_words(cset, f)
+    if um_pix is not None:
+        cs.launch_all(um_pix, True, descriptors, slots=4)
+    return cs
+
+
 def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256, um_pix: Optional[float] = None,
-                 total_area: Optional[np.ndarray] = None, shape: bool = False, inscribed: bool = False, skeleton: bool = False):
+                 total_area: Optional[np.ndarray] = None, descriptors: Sequence[str] = ()):
     """The contour trace of every mask of ``cset`` (``MaskOps.trace``, unchanged), ``planes.chunk`` masks at a time through the
     pool: yields (first, n, ContourSet) per chunk, each with its unpack + trace (+ the measurements of its first contours when
     ``um_pix`` is given) enqueued and NOT waited for, and with the NEXT chunk already enqueued behind it -- the pool is reused
     in stream order, every chunk's contour tables are its own -- so the consumer's fetch of one chunk overlaps the device's
     work on the next, and the contour tables of two chunks at most are alive.  ``total_area``: the masks' pixel counts when
     they are on the host -- sizes every chunk's point pool as ``MaskOps.trace`` does (else from the mask count; a caller that
-    meets an overflow traces that chunk again).  ``shape``: with ``um_pix``, the shape descriptors are enqueued behind the
-    measurements (``ContourSet.launch_shape``).  ``inscribed``: every chunk's contour set remembers ``cset`` and the chunk's first mask
-    as the source of its words, and with ``um_pix`` the inscribed descriptors are enqueued too (``ContourSet.launch_inscribed``):
-    they read the set's PAYLOAD, never the pool, which the next chunk overwrites -- so does an on-demand ``inscribed()`` later.
-    ``skeleton``: the same for the skeleton descriptors (``ContourSet.launch_skeleton`` / ``skeleton()``)."""
-    ops = cset.ops
-    ops.set_frame_width(cset.hw[1])
+    meets an overflow traces that chunk again).  ``descriptors``: with ``um_pix``, the named families of ``FAMILIES`` are enqueued
+    behind the measurements (``ContourSet.launch_all``)."""
+    reads_words(descriptors)                # (an unknown name raises for an empty set too)
+    cset.ops.set_frame_width(cset.hw[1])
     pending = None
     for f in range(0, len(cset), planes.chunk):
         n = min(planes.chunk, len(cset) - f)
-        pl = cset.unpack_pooled(planes.pool, f, n)
         if total_area is not None:
             mp = int(min(max(4 * int(np.sum(total_area[f:f + n])) // 8 + 4096 * n, 1 << 16), 1 << 26))
         else:
             mp = int(min(4096 * n + (1 << 16), 1 << 26))
-        cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], max_points=mp, scratch=planes.scratch[:n])
-        if inscribed or skeleton:
-            cs.set_crop_words(cset, f)
-        if um_pix is not None:
-            cs.launch_measure(um_pix, slots=4)
-            if shape:
-                cs.launch_shape(um_pix, slots=4)
-            if inscribed:
-                cs.launch_inscribed(um_pix, slots=4)
-            if skeleton:
-                cs.launch_skeleton(um_pix, slots=4)
+        cs = _trace_chunk(cset, planes, f, n, max_contours, um_pix, descriptors, max_points=mp)
         if pending is not None:
             yield pending
         pending = (f, n, cs)
@@ -561,42 +552,28 @@ def trace_chunks(cset: CropMaskSet, planes: CropPlanes, max_contours: int = 256,
 
 
 def crop_contours(cset: CropMaskSet, planes: CropPlanes, um_pix: float = 1.0, total_area: Optional[np.ndarray] = None,
-                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256, shape: bool = False, inscribed: bool = False,
-                  skeleton: bool = False):
+                  extra: Optional[Sequence[torch.Tensor]] = None, max_contours: int = 256, descriptors: Sequence[str] = ()):
     """``MaskOps.contours`` (trace + the 12 measurements, records in OpenCV's order) for a crop-framed set, chunk by chunk
     through the plane pool.  ``extra``: int32 device tensors that come to the host with the FIRST chunk's tables.
     ``total_area``: the masks' pixel counts on the host (sizes the point pools); without them the pools are sized from the mask
     count, and a chunk whose pool overflows is unpacked and traced again with the pool sized from its own (device) areas.
-    ``shape``: the records also carry the shape descriptors, in each chunk's one fetch; ``inscribed``: likewise the inscribed-circle
-    descriptors, read from the set's payload; ``skeleton``: and the skeleton descriptors.
+    ``descriptors``: the records also carry the named families of ``FAMILIES``, in each chunk's one fetch.
     Returns (records per mask, host arrays of ``extra`` or None); one device-to-host wait per chunk."""
-    ops = cset.ops
     area = None if total_area is None else np.asarray(total_area).reshape(-1)
     recs, got = [], None
-    for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area, shape=shape,
-                                                  inscribed=inscribed, skeleton=skeleton)):
+    for k, (f, n, cs) in enumerate(trace_chunks(cset, planes, max_contours, um_pix=um_pix, total_area=area, descriptors=descriptors)):
         ex = extra if k == 0 else None
         try:
             g = cs.fetch(extra=ex, with_points=True)
         except _lib.HipKernelError as e:
             if "overflow" not in str(e):
                 raise
-            pl = cset.unpack_pooled(planes.pool, f, n)      # (the chunk behind this one has run: the pool is free again)
-            cs = ops.trace(pl, max_contours=max_contours, bbox=cset.bbox[f:f + n], total_area=int(cset.area[f:f + n].sum().item()),
-                           scratch=planes.scratch[:n])
-            cs.launch_measure(um_pix, slots=4)
-            if shape:
-                cs.launch_shape(um_pix, slots=4)
-            if inscribed or skeleton:
-                cs.set_crop_words(cset, f)
-            if inscribed:
-                cs.launch_inscribed(um_pix, slots=4)
-            if skeleton:
-                cs.launch_skeleton(um_pix, slots=4)
+            # (the chunk behind this one has run: the pool is free again)
+            cs = _trace_chunk(cset, planes, f, n, max_contours, um_pix, descriptors, total_area=int(cset.area[f:f + n].sum().item()))
             g = cs.fetch(extra=ex, with_points=True)
         if k == 0:
             got = list(g)
-        recs.extend(cs.records(um_pix=um_pix, measure=True, shape=shape, inscribed=inscribed, skeleton=skeleton))
+        recs.extend(cs.records(um_pix=um_pix, measure=True, descriptors=descriptors))
     if extra is not None and got is None:
         got = [e.cpu().numpy() for e in extra]
     return recs, (got if extra is not None else None)

@@ -32,7 +32,7 @@ from ..data.models import choose_and_use_model, get_trained_model_paths
 from .. import _lib as _L
 from .. import parallel
 from ..cropset import CropMaskAlgebra, CropMaskSet, CropPlanes, crop_contours, crop_gray_histogram, crop_planes, rooms_of_placed_tiles, trace_chunks
-from ..maskset import MaskOps
+from ..maskset import FAMILIES, MaskOps, families
 from ..utils.config import get_config
 from ..utils.logger_utils import log_memory_usage, system_logger
 from ..utils.mask_algebra import DeviceMaskAlgebra
@@ -45,18 +45,22 @@ from ..utils.spatial_constraints import apply_spatial_constraints_indices, load_
 CSV_HEADER = ["Instance_ID", "Class", "Class_Name", "Major axis length", "Minor axis length", "Eccentricity", "C. Length",
               "C. Width", "Circular eq. diameter", "Aspect ratio", "Circularity", "Chord length", "Ferret diameter",
               "Roundness", "Sphericity", "Contrast d10", "Contrast d50", "Contrast d90", "Detected scale bar", "File name"]
-# the columns `inference_settings.shape_descriptors: true` appends behind "File name": values 3..9 of demia_contour_shape
-SHAPE_CSV_HEADER = ["Convex area", "Convex perimeter", "Solidity", "Convexity", "Max Feret diameter", "Min Feret diameter", "Feret angle"]
+# per family of maskset.FAMILIES, the columns `inference_settings.<name>_descriptors: true` appends behind "File name" (each
+# requested family appends its columns in table order) and, column by column, the index of its value in the family's values:
+#   shape      demia_contour_shape: the convex hull -- area, perimeter, solidity, convexity, true Feret diameters and angle
+#   inscribed  demia_mask_inscribed / demia_crop_inscribed: largest inscribed circle and distance-based thickness of the component
+#   skeleton   demia_mask_skeleton / demia_crop_skeleton: length, mean width, end and branch points of the component's skeleton
+DESCRIPTOR_CSV = {
+    "shape": (["Convex area", "Convex perimeter", "Solidity", "Convexity", "Max Feret diameter", "Min Feret diameter", "Feret angle"],
+              (3, 4, 5, 6, 7, 8, 9)),
+    "inscribed": (["Inscribed diameter", "Inscribed centre x", "Inscribed centre y", "RMS boundary distance", "Inscribed ratio",
+                   "Component pixels"], (5, 1, 2, 6, 7, 3)),
+    "skeleton": (["Skeleton length", "Skeleton mean width", "Skeleton end points", "Skeleton branch points", "Skeleton pixels"],
+                 (6, 7, 3, 4, 0)),
+}
+assert list(DESCRIPTOR_CSV) == list(FAMILIES)
+SHAPE_CSV_HEADER, INSCRIBED_CSV_HEADER, SKELETON_CSV_HEADER = (DESCRIPTOR_CSV[n][0] for n in ("shape", "inscribed", "skeleton"))
 # measurement vector layout of demia_contour_measure -> CSV column order (inference.py:1209-1230)
-# the columns `inference_settings.inscribed_descriptors: true` appends (behind the shape columns when both are on): values
-# 5, 1, 2, 6, 7, 3 of demia_mask_inscribed / demia_crop_inscribed
-INSCRIBED_CSV_HEADER = ["Inscribed diameter", "Inscribed centre x", "Inscribed centre y", "RMS boundary distance", "Inscribed ratio",
-                        "Component pixels"]
-_INSCRIBED_CSV_VALUES = (5, 1, 2, 6, 7, 3)
-# the columns `inference_settings.skeleton_descriptors: true` appends (behind the inscribed columns when those are on): values
-# 6, 7, 3, 4, 0 of demia_mask_skeleton / demia_crop_skeleton
-SKELETON_CSV_HEADER = ["Skeleton length", "Skeleton mean width", "Skeleton end points", "Skeleton branch points", "Skeleton pixels"]
-_SKELETON_CSV_VALUES = (6, 7, 3, 4, 0)
 _VAL = {"major": 0, "minor": 1, "ecc": 2, "Length": 3, "Width": 4, "CircularED": 5, "Aspect": 6, "Circularity": 7,
         "Chords": 8, "Feret": 9, "Roundness": 10, "Sphericity": 11}
 CLASS_COLORS = [(0, 255, 0), (255, 0, 0), (0, 0, 255), (255, 255, 0), (255, 0, 255), (0, 255, 255), (128, 0, 128), (255, 165, 0)]
@@ -319,36 +323,19 @@ def mask_frame_setting(inf_settings: dict) -> str:
     return frame
 
 
-def shape_descriptors_setting(inf_settings: dict) -> bool:
-    """``inference_settings.shape_descriptors`` (per dataset): ``true`` appends the seven convex-hull columns of
-    ``SHAPE_CSV_HEADER`` to every row of ``measurements_results.csv`` (``demia_contour_shape``, in every mask frame); ``false``
-    (the default) writes the reference's 20 columns.  Anything but a bool is a configuration error."""
-    value = (inf_settings or {}).get("shape_descriptors", False)
-    if not isinstance(value, bool):
-        raise ValueError(f"inference_settings.shape_descriptors must be true or false, got {value!r}")
-    return value
-
-
-def inscribed_descriptors_setting(inf_settings: dict) -> bool:
-    """``inference_settings.inscribed_descriptors`` (per dataset): ``true`` appends the six columns of ``INSCRIBED_CSV_HEADER``
-    -- largest inscribed circle and distance-based thickness of every contour's component, from the mask words
-    (``demia_mask_inscribed`` / ``demia_crop_inscribed``, in every mask frame) -- behind the shape columns if those are on;
-    ``false`` (the default) launches, allocates and copies nothing.  Anything but a bool is a configuration error."""
-    value = (inf_settings or {}).get("inscribed_descriptors", False)
-    if not isinstance(value, bool):
-        raise ValueError(f"inference_settings.inscribed_descriptors must be true or false, got {value!r}")
-    return value
-
-
-def skeleton_descriptors_setting(inf_settings: dict) -> bool:
-    """``inference_settings.skeleton_descriptors`` (per dataset): ``true`` appends the five columns of ``SKELETON_CSV_HEADER`` --
-    length, mean width, end and branch points of the morphological skeleton of every contour's component, from the mask words
-    (``demia_mask_skeleton`` / ``demia_crop_skeleton``, in every mask frame) -- behind the shape and inscribed columns if those are
-    on; ``false`` (the default) launches, allocates and copies nothing.  Anything but a bool is a configuration error."""
-    value = (inf_settings or {}).get("skeleton_descriptors", False)
-    if not isinstance(value, bool):
-        raise ValueError(f"inference_settings.skeleton_descriptors must be true or false, got {value!r}")
-    return value
+def descriptors_setting(inf_settings: dict) -> Tuple[str, ...]:
+    """The families of ``maskset.FAMILIES``, in table order, whose ``inference_settings.<name>_descriptors`` (per dataset) is
+    ``true``: each appends its columns of ``DESCRIPTOR_CSV`` to every row of ``measurements_results.csv``, in every mask frame.
+    ``false`` (the default of every key) launches, allocates and copies nothing for that family: without any, the reference's 20
+    columns.  Anything but a bool is a configuration error."""
+    on = []
+    for name in FAMILIES:
+        value = (inf_settings or {}).get(f"{name}_descriptors", False)
+        if not isinstance(value, bool):
+            raise ValueError(f"inference_settings.{name}_descriptors must be true or false, got {value!r}")
+        if value:
+            on.append(name)
+    return tuple(on)
 
 
 DETECTIONS_PER_IMAGE_MAX = 1000
@@ -2164,9 +2151,7 @@ class PipelineSettings:
         self.mask_frame = mask_frame_setting(inf)
         self.rank_exchange = rank_exchange_setting(inf)
         self.detections_per_image = detections_per_image_setting(inf)     # (the model loader reads it too: a bad value ends the run here)
-        self.shape_descriptors = shape_descriptors_setting(inf)
-        self.inscribed_descriptors = inscribed_descriptors_setting(inf)
-        self.skeleton_descriptors = skeleton_descriptors_setting(inf)
+        self.descriptors = descriptors_setting(inf)
         # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
         self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
 
@@ -2517,8 +2502,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                 extra = [crop[0]] if crop is not None else None
                 rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
                                                     visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes,
-                                                    crop_direct=pipe.crop_direct, shape=st.shape_descriptors,
-                                                    inscribed=st.inscribed_descriptors, skeleton=st.skeleton_descriptors)
+                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors)
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final and pipe.crop:
@@ -2614,8 +2598,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     wri.writerow([name.rsplit(".", 1)[0], text])
 
         write_measurements(pipe.ops, dedup_results, inpath, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                           rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, shape=st.shape_descriptors,
-                           inscribed=st.inscribed_descriptors, skeleton=st.skeleton_descriptors)
+                           rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, descriptors=st.descriptors)
         with open(os.path.join(output_dir, "class_color_legend.txt"), "w") as f:
             f.write("Class Color Legend (BGR)\n")
             for i, cname in enumerate(metadata.thing_classes):
@@ -2690,10 +2673,9 @@ def write_predictions_png(path: str, image_bgr: np.ndarray, crops, classes: Sequ
 
 def measurement_rows(image_name: str, classes: Sequence[int], recs, thing_classes, min_area: float, contrast=None, psum: str = "0") -> List[list]:
     """The 20-column rows of ``measurements_results.csv`` for one image / tile (``inference.py:1148-1230``): one row per
-    external contour that passes the area gate, ``<image>_<instance>`` ids counted from 1, ``None`` -> empty field.  A record
-    that holds ``shape`` (``ContourSet.records(shape=True)``) gives 27 columns: the seven of ``SHAPE_CSV_HEADER`` behind them; one
-    that holds ``inscribed`` adds the six of ``INSCRIBED_CSV_HEADER`` behind those (26 / 33 columns), one that holds ``skeleton`` the
-    five of ``SKELETON_CSV_HEADER`` behind all of them (25, 32, 31 or 38 columns)."""
+    external contour that passes the area gate, ``<image>_<instance>`` ids counted from 1, ``None`` -> empty field.  Behind
+    them, each family of ``DESCRIPTOR_CSV`` that the record holds (``ContourSet.records(descriptors=...)``) appends its columns,
+    in table order."""
     rows = []
     for instance_id, (cls, contours) in enumerate(zip(classes, recs), 1):
         cls = int(cls)
@@ -2706,12 +2688,9 @@ def measurement_rows(image_name: str, classes: Sequence[int], recs, thing_classe
             rows.append([f"{image_name}_{instance_id}", cls, cname, float(v[0]), float(v[1]), float(v[2]), float(v[3]),
                          float(v[4]), float(v[5]), float(v[6]), float(v[7]), float(v[8]), float(v[9]), float(v[10]),
                          float(v[11]), d10, d50, d90, psum, image_name])
-            if "shape" in c:
-                rows[-1].extend(float(x) for x in c["shape"][3:10])
-            if "inscribed" in c:
-                rows[-1].extend(float(c["inscribed"][k]) for k in _INSCRIBED_CSV_VALUES)
-            if "skeleton" in c:
-                rows[-1].extend(float(c["skeleton"][k]) for k in _SKELETON_CSV_VALUES)
+            for name, (_, index) in DESCRIPTOR_CSV.items():
+                if name in c:
+                    rows[-1].extend(float(c[name][k]) for k in index)
     return rows
 
 
@@ -2753,16 +2732,15 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
 
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
-                  extra: Optional[list] = None, note_planes=None, crop_direct: bool = False, shape: bool = False,
-                  inscribed: bool = False, skeleton: bool = False) -> List[list]:
+                  extra: Optional[list] = None, note_planes=None, crop_direct: bool = False,
+                  descriptors: Sequence[str] = ()) -> List[list]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
     mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
     the file here, which gives the same bytes).  ``crop_direct``: a crop-framed set is traced, measured and histogrammed on its
-    words in place (``mask_frame: crop_direct``) instead of through the plane pool.  ``shape``: the contour records, and so the
-    rows, also carry the convex-hull shape descriptors (``inference_settings.shape_descriptors``), in every mask frame;
-    ``inscribed``: likewise the inscribed-circle descriptors (``inference_settings.inscribed_descriptors``); ``skeleton``: and the
-    skeleton descriptors (``inference_settings.skeleton_descriptors``)."""
+    words in place (``mask_frame: crop_direct``) instead of through the plane pool.  ``descriptors``: the contour records, and
+    so the rows, also carry these families of ``maskset.FAMILIES`` (``descriptors_setting``), in every mask frame."""
+    families(descriptors)                   # (an unknown name raises for an image without masks too)
     measure_contrast = bool(get_config().get("measure_contrast_distribution", False))     # inference.py:58: GLOBAL config
     host = {}
 
@@ -2798,27 +2776,26 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
         # a crop-framed set traced and measured on its words in place: one trace, one fetch, no plane
         area_h = data.get("area")
         recs = packed.contours(max_contours=256, um_pix=um_pix, total_area=None if area_h is None else int(np.sum(area_h)), extra=extra,
-                               shape=shape, inscribed=inscribed, skeleton=skeleton)
+                               descriptors=descriptors)
         if extra is not None:
             recs, extra_host = recs
             extra[:] = extra_host
     elif crop:
         # a crop-framed set: the same trace + measurements, a chunk of the plane pool at a time
-        recs, extra_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=extra, shape=shape,
-                                         inscribed=inscribed, skeleton=skeleton)
+        recs, extra_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=extra,
+                                         descriptors=descriptors)
         if extra is not None:
             extra[:] = extra_host
     elif data.get("bbox") is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
         # (``extra``: a list of int32 device tensors the image loop wants on the host in the same copy -- the cropped words of the RLE
         # texts --; replaced in place by their host arrays)
         recs = ops.contours(packed, max_contours=256, um_pix=um_pix, bbox=ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32)),
-                            total_area=int(np.sum(data["area"])), extra=extra, shape=shape, inscribed=inscribed,
-                            skeleton=skeleton)
+                            total_area=int(np.sum(data["area"])), extra=extra, descriptors=descriptors)
         if extra is not None:
             recs, extra_host = recs
             extra[:] = extra_host
     else:
-        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, shape=shape, inscribed=inscribed, skeleton=skeleton)
+        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, descriptors=descriptors)
         if extra is not None:
             extra[:] = [e.cpu().numpy() for e in extra]
     contrast = [(None, None, None)] * int(packed.shape[0])
@@ -2839,19 +2816,17 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
 
 def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_path: str, output_dir: str, metadata,
                        dataset_name: str, draw_scalebar: bool = False, visualize: bool = False,
-                       rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False, shape: bool = False,
-                       inscribed: bool = False, skeleton: bool = False) -> str:
+                       rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False,
+                       descriptors: Sequence[str] = ()) -> str:
     """Measurement phase (``inference.py:983-1291``): one CSV row per external contour that passes
     the area gate, 20 columns, ``None`` -> empty field, floats through ``csv.writer``.  ``rows_by_image``: rows the image
     loop (or another rank, when images are sharded over ranks) has already measured; images without an entry are measured here.
-    ``shape``: 27 columns, the seven of ``SHAPE_CSV_HEADER`` behind "File name" (rows measured elsewhere come with them).
-    ``inscribed``: the six of ``INSCRIBED_CSV_HEADER`` behind those: 26 columns, 33 with both.
-    ``skeleton``: the five of ``SKELETON_CSV_HEADER`` behind all of them: 25, 32, 31 or 38 columns."""
+    ``descriptors``: each requested family of ``DESCRIPTOR_CSV`` appends its columns behind "File name", in table order (rows
+    measured elsewhere come with them)."""
     csv_filename = os.path.join(output_dir, "measurements_results.csv")
     with open(csv_filename, "w", newline="") as csvfile:
         w = csv.writer(csvfile)
-        w.writerow(CSV_HEADER + (SHAPE_CSV_HEADER if shape else []) + (INSCRIBED_CSV_HEADER if inscribed else []) +
-                   (SKELETON_CSV_HEADER if skeleton else []))
+        w.writerow(CSV_HEADER + [col for fam in families(descriptors) for col in DESCRIPTOR_CSV[fam.name][0]])
         for test_img in [f for f in os.listdir(test_img_path) if is_image_file(f)]:
             data = dedup_results.get(test_img)
             if data is None:
@@ -2860,7 +2835,7 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
                 rows = rows_by_image[test_img]
             else:
                 rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                                     crop_direct=crop_direct, shape=shape, inscribed=inscribed, skeleton=skeleton)
+                                     crop_direct=crop_direct, descriptors=descriptors)
             for r in rows:
                 w.writerow(r)
             csvfile.flush()

@@ -8,7 +8,9 @@ contour points, measurement rows) ever reach the host.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from functools import partial
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import os
 import numpy as np
@@ -20,9 +22,106 @@ from . import _lib
 # (A/B switch) 0: the large-region variants of the per-mask kernels run over all masks again instead of over a worklist
 _WORKLISTS = os.environ.get("DEEPEMIA_MASK_WORKLISTS", "1") != "0"
 
-SHAPE_COLS = 10          # values per contour of demia_contour_shape
-INSCRIBED_COLS = 8       # values per contour of demia_mask_inscribed / demia_crop_inscribed
-SKELETON_COLS = 8        # values per contour of demia_mask_skeleton / demia_crop_skeleton
+
+def _points_into(cs: "ContourSet", out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray], entry: str, work_ints: str) -> None:
+    """One launch of a POINT-TABLE family's entry (``demia_contour_shape``) into ``out`` [M, out_c, cols]: every mask, or the
+    positions ``sel`` (a flag per mask over the full tables; the other rows are left as they are)."""
+    ops = cs.ops
+    M, C, mp = cs.M, cs.C, cs.max_points
+    wi = torch.empty((int(getattr(ops.lib, work_ints)(M, C, mp)),), dtype=torch.int32, device=ops.device)
+    _lib.check(getattr(ops.lib, entry)(_lib.ptr(cs._flags(sel)), _lib.ptr(cs.count), _lib.ptr(cs.info), _lib.ptr(cs.red), _lib.ptr(cs.points),
+                                       M, C, mp, _lib.ptr(wi), float(um_pix), _lib.ptr(out), int(out_c), ops._stream()), entry)
+
+
+def _words_into(cs: "ContourSet", out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray], what: str, entries: Tuple[str, str],
+                second_scratch: bool = False) -> None:
+    """One launch of a WORD family's entry (``entries``: for planes, for crops) into ``out`` [M, out_c, cols]: every mask, or the
+    positions ``sel`` -- their table rows are gathered, their words are read where they are (the entry's ``select``), their values
+    are scattered to their rows of ``out`` and the other rows are left as they are.  ``second_scratch`` (skeleton): the entries
+    take one more scratch, made on first use (planes: one more plane per mask, here; crops: ``CropMaskSet.skeleton_scratch``), and
+    a thin-only flag, 0."""
+    ops = cs.ops
+    if cs._words is None:
+        raise RuntimeError(f"{what} descriptors: the trace did not keep its words (trace(..., keep_words=True))")
+    n = cs.M if sel is None else len(sel)
+    if n == 0:
+        return
+    count, info, sel_d, idx, dst = cs.count, cs.info, None, None, out
+    if sel is not None:
+        sel_d = ops.upload(np.ascontiguousarray(sel, dtype=np.int32))
+        idx = sel_d.to(torch.int64)
+        count, info = cs.count.index_select(0, idx), cs.info.index_select(0, idx)
+        dst = torch.zeros((n, int(out_c), int(out.shape[2])), dtype=torch.float64, device=ops.device)
+    tail = ()
+    if cs._words[0] == "plane":
+        _, packed, bbox, scratch, W = cs._words
+        bb = bbox if idx is None else bbox.index_select(0, idx)
+        if second_scratch:
+            if cs._scratch2 is None:
+                cs._scratch2 = torch.empty_like(packed)          # only touched by regions that do not fit in LDS
+            tail = (_lib.ptr(cs._scratch2), 0)
+        _lib.check(getattr(ops.lib, entries[0])(_lib.ptr(sel_d), _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bb), _lib.ptr(count),
+                                                _lib.ptr(info), n, int(packed.shape[1]), W, cs.C, float(um_pix), _lib.ptr(dst), int(out_c),
+                                                *tail, ops._stream()), entries[0])
+    else:
+        _, cset, first = cs._words
+        bb = cset.bbox[first:first + cs.M]
+        if idx is not None:
+            bb, sel_d = bb.index_select(0, idx), sel_d + first
+        elif first:
+            sel_d = torch.arange(first, first + cs.M, dtype=torch.int32, device=ops.device)
+        scratch, off_d = cset.inscribed_scratch()
+        if second_scratch:
+            scratch2, off2_d = cset.skeleton_scratch()
+            tail = (_lib.ptr(scratch2), _lib.ptr(off2_d), 0)
+        _lib.check(getattr(ops.lib, entries[1])(_lib.ptr(sel_d), _lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets),
+                                                _lib.ptr(bb), _lib.ptr(count), _lib.ptr(info), n, cset.hw[0], cset.hw[1], cs.C,
+                                                float(um_pix), _lib.ptr(dst), int(out_c), _lib.ptr(scratch), _lib.ptr(off_d), *tail,
+                                                ops._stream()), entries[1])
+    if idx is not None:
+        out[idx] = dst
+
+
+@dataclass(frozen=True)
+class Family:
+    """One opt-in descriptor family per contour: all that ``ContourSet``, the callers' ``descriptors`` arguments and the CSV
+    writer know of it."""
+    name: str                # record key, ``inference_settings.<name>_descriptors``
+    cols: int                # float64 values per contour
+    words: bool              # reads the mask words (the trace must keep them) instead of the point tables
+    enqueue: Callable        # (cs, out [M, out_c, cols], out_c, um_pix, sel: positions or None) -> None, without a wait
+
+
+# in the order of the float64 block of ContourSet.fetch and of the CSV columns
+FAMILIES = {f.name: f for f in (
+    Family("shape", 10, False, partial(_points_into, entry="demia_contour_shape", work_ints="demia_contour_shape_work_ints")),
+    Family("inscribed", 8, True, partial(_words_into, what="inscribed", entries=("demia_mask_inscribed", "demia_crop_inscribed"))),
+    Family("skeleton", 8, True, partial(_words_into, what="skeleton", entries=("demia_mask_skeleton", "demia_crop_skeleton"),
+                                        second_scratch=True)),
+)}
+
+
+def families(descriptors: Sequence[str]) -> Tuple[Family, ...]:
+    """The families named in ``descriptors``, in table order; ``ValueError`` for a name the table does not hold."""
+    names = tuple(descriptors)
+    unknown = [n for n in names if n not in FAMILIES]
+    if unknown:
+        raise ValueError(f"unknown descriptor family {unknown[0]!r}: one of {', '.join(FAMILIES)}")
+    return tuple(f for f in FAMILIES.values() if f.name in names)
+
+
+def reads_words(descriptors: Sequence[str]) -> bool:
+    """Whether any of the families ``descriptors`` reads the mask words: the trace then has to keep them."""
+    return any(f.words for f in families(descriptors))
+
+
+@dataclass
+class Launched:
+    """What ``ContourSet.launch`` enqueued for one family."""
+    dev: torch.Tensor                        # [M, slots, cols] float64 on the device
+    slots: int
+    um_pix: float
+    host: Optional[np.ndarray] = None        # [M, max contours per mask, cols] view of fetch()'s copy; None when it fell back
 
 
 class PlanePool:
@@ -318,9 +417,8 @@ class MaskOps:
         the returned set can be measured later for any subset of its masks without tracing again.  ``bbox`` (any
         superset of the tight boxes) and ``total_area`` (sizes the point pool) save a reduction when known.  ``scratch``:
         the caller's own planes of ``packed``'s shape for the regions that do not fit in LDS (default: allocated here).
-        ``keep_words``: the set remembers the planes, the boxes and the scratch it was traced from (``ContourSet.launch_inscribed``
-        and ``ContourSet.launch_skeleton`` read the words again); the caller leaves them unchanged for as long as it asks the set
-        for inscribed or skeleton values."""
+        ``keep_words``: the set remembers the planes, the boxes and the scratch it was traced from (the word families of
+        ``FAMILIES`` read the words again); the caller leaves them unchanged for as long as it asks the set for their values."""
         M, H, wpr = packed.shape
         W = self._w(packed)
         if bbox is None or (max_points is None and total_area is None):
@@ -343,33 +441,24 @@ class MaskOps:
 
     def contours(self, packed: torch.Tensor, max_contours: int = 64, max_points: Optional[int] = None,
                  um_pix: float = 1.0, measure: bool = True, bbox: Optional[torch.Tensor] = None, total_area: Optional[int] = None,
-                 extra: Optional[Sequence[torch.Tensor]] = None, shape: bool = False, inscribed: bool = False,
-                 skeleton: bool = False):
+                 extra: Optional[Sequence[torch.Tensor]] = None, descriptors: Sequence[str] = ()):
         """Per mask: external contours in OpenCV's order, with area, perimeter and the 12 measurement
         values.  Returns a list (per mask) of lists of dicts with keys ``points`` (P, 2) int32,
         ``area``, ``perimeter`` and (if ``measure``) ``values`` (12,) float64.  ``extra``: int32 device tensors that come to the
         host in the SAME copy (e.g. the cropped words the RLE texts are made of); the call then returns (records, host arrays).
-        ``shape``: also ``shape`` (10,) float64, the convex-hull descriptors of ``demia_contour_shape``, in that same copy.
-        ``inscribed``: also ``inscribed`` (8,) float64, the inscribed-circle descriptors of ``demia_mask_inscribed``, likewise;
-        ``skeleton``: also ``skeleton`` (8,) float64, the skeleton descriptors of ``demia_mask_skeleton``, likewise."""
+        ``descriptors``: names of ``FAMILIES``; every record also holds each named family's values under its name, (cols,)
+        float64, brought over in that same copy."""
+        keep_words = reads_words(descriptors)
         if int(packed.shape[0]) == 0:
             return [] if extra is None else ([], [e.cpu().numpy() for e in extra])
-        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area, keep_words=inscribed or skeleton)
+        cs = self.trace(packed, max_contours, max_points, bbox=bbox, total_area=total_area, keep_words=keep_words)
         # ONE device-to-host wait: the measurements of every mask's first contours are enqueued right behind the trace and come
         # over with the counts, the contour tables and the points (a mask with more than four contours falls back to the
         # sliced copies of ContourSet.host(): five waits, rare)
-        if measure:
-            cs.launch_measure(um_pix, slots=4)
-        if shape:
-            cs.launch_shape(um_pix, slots=4)
-        if inscribed:
-            cs.launch_inscribed(um_pix, slots=4)
-        if skeleton:
-            cs.launch_skeleton(um_pix, slots=4)
+        cs.launch_all(um_pix, measure, descriptors, slots=4)
         got = cs.fetch(extra=extra, with_points=True)
-        recs = cs.records(um_pix=um_pix, measure=measure, shape=shape, inscribed=inscribed, skeleton=skeleton)
+        recs = cs.records(um_pix=um_pix, measure=measure, descriptors=descriptors)
         return recs if extra is None else (recs, list(got))
-
 
     def skeleton(self, packed: torch.Tensor, bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The morphological skeleton (Guo-Hall thinning; ``demia_mask_skeleton`` in its thin-only form) of every mask, as packed
@@ -399,14 +488,12 @@ class ContourSet:
         self.counters = torch.zeros((4,), dtype=torch.int32, device=dev)
         self._host = None
         self._pts_host = None             # contour points brought over by fetch(with_points=True)
-        self._shape_dev = None            # [M, slots, 10] shape descriptors enqueued by launch_shape
-        self._shape_host = None
-        self._words = None                # where the traced words live (set_plane_words / set_crop_words): what launch_inscribed reads
-        self._insc_dev = None             # [M, slots, 8] inscribed descriptors enqueued by launch_inscribed
-        self._insc_host = None
-        self._skel_dev = None             # [M, slots, 8] skeleton descriptors enqueued by launch_skeleton
-        self._skel_host = None
-        self._skel_scratch2 = None        # planes: the second scratch of demia_mask_skeleton, made by the first launch
+        self._mslots, self._m_um = 4, None    # launch_measure: contour slots per mask and scale of ...
+        self._vals_dev = None             # ... the [M, slots, 12] measurement values it enqueued
+        self._vals_host = None
+        self.launched = {}                # family name -> Launched: what launch() enqueued
+        self._words = None                # where the traced words live (set_plane_words / set_crop_words): what the word families read
+        self._scratch2 = None             # planes: the second scratch of a word family that wants one, made by its first launch
         self.blocking_point_copies = 0    # times records() had to fetch the points with a device-to-host copy of its own
 
     def host(self):
@@ -437,18 +524,23 @@ class ContourSet:
                                                  _lib.ptr(self.points), M, C, mp, _lib.ptr(self._wi), _lib.ptr(self._wf), _lib.ptr(self._wd),
                                                  float(um_pix), _lib.ptr(self._vals_dev), self._mslots, ops._stream()), "demia_contour_measure")
 
-    def launch_shape(self, um_pix: float = 1.0, slots: int = 4) -> None:
-        """:meth:`launch_measure` for the convex-hull shape descriptors (``demia_contour_shape``): the first ``slots`` contours of
-        EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one copy.  (Masks with more
-        contours than ``slots`` are computed again by :meth:`shape` on demand.)"""
-        ops = self.ops
-        M, C, mp = self.M, self.C, self.max_points
-        self._sslots, self._s_um = min(int(slots), C), float(um_pix)
-        self._swi = torch.empty((int(ops.lib.demia_contour_shape_work_ints(M, C, mp)),), dtype=torch.int32, device=ops.device)
-        self._shape_dev = torch.zeros((M, self._sslots, SHAPE_COLS), dtype=torch.float64, device=ops.device)
-        _lib.check(ops.lib.demia_contour_shape(0, _lib.ptr(self.count), _lib.ptr(self.info), _lib.ptr(self.red), _lib.ptr(self.points),
-                                               M, C, mp, _lib.ptr(self._swi), float(um_pix), _lib.ptr(self._shape_dev), self._sslots,
-                                               ops._stream()), "demia_contour_shape")
+    def launch(self, name: str, um_pix: float = 1.0, slots: int = 4) -> None:
+        """:meth:`launch_measure` for the descriptor family ``name`` of ``FAMILIES``: the first ``slots`` contours of EVERY mask,
+        enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one copy, in table order.  (Masks with more
+        contours than ``slots`` are computed again by :meth:`descriptor` on demand.)"""
+        fam, = families((name,))
+        k = min(int(slots), self.C)
+        dev = torch.zeros((self.M, k, fam.cols), dtype=torch.float64, device=self.ops.device)
+        fam.enqueue(self, dev, k, um_pix, None)
+        self.launched[name] = Launched(dev, k, float(um_pix))
+
+    def launch_all(self, um_pix: float, measure: bool, descriptors: Sequence[str], slots: int = 4) -> None:
+        """:meth:`launch_measure` if ``measure``, then :meth:`launch` for every family named in ``descriptors``, in table order."""
+        fams = families(descriptors)
+        if measure:
+            self.launch_measure(um_pix, slots=slots)
+        for fam in fams:
+            self.launch(fam.name, um_pix, slots=slots)
 
     def set_plane_words(self, packed: torch.Tensor, bbox: torch.Tensor, scratch: torch.Tensor) -> None:
         """This set was traced from the planes ``packed`` with the boxes ``bbox`` and the scratch planes ``scratch``."""
@@ -459,115 +551,23 @@ class ContourSet:
         words in place or on planes the masks were unpacked into: the payload lives as long as the set, a plane pool does not."""
         self._words = ("crop", cset, int(first))
 
-    def _inscribed_into(self, out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray] = None) -> None:
-        """One launch of ``demia_mask_inscribed`` / ``demia_crop_inscribed`` into ``out`` [n, out_c, 8]: every mask, or the
-        positions ``sel`` -- their table rows are gathered, their words are read where they are (the entry's ``select``)."""
-        ops = self.ops
-        if self._words is None:
-            raise RuntimeError("inscribed descriptors: the trace did not keep its words (trace(..., keep_words=True))")
-        n = self.M if sel is None else len(sel)
-        if n == 0:
-            return
-        count, info, sel_d, idx = self.count, self.info, None, None
-        if sel is not None:
-            sel_d = ops.upload(np.ascontiguousarray(sel, dtype=np.int32))
-            idx = sel_d.to(torch.int64)
-            count, info = self.count.index_select(0, idx), self.info.index_select(0, idx)
-        if self._words[0] == "plane":
-            _, packed, bbox, scratch, W = self._words
-            bb = bbox if idx is None else bbox.index_select(0, idx)
-            _lib.check(ops.lib.demia_mask_inscribed(_lib.ptr(sel_d), _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bb), _lib.ptr(count),
-                                                    _lib.ptr(info), n, int(packed.shape[1]), W, self.C, float(um_pix), _lib.ptr(out),
-                                                    int(out_c), ops._stream()), "demia_mask_inscribed")
-        else:
-            _, cset, first = self._words
-            bb = cset.bbox[first:first + self.M]
-            if idx is not None:
-                bb, sel_d = bb.index_select(0, idx), sel_d + first
-            elif first:
-                sel_d = torch.arange(first, first + self.M, dtype=torch.int32, device=ops.device)
-            scratch, off_d = cset.inscribed_scratch()
-            _lib.check(ops.lib.demia_crop_inscribed(_lib.ptr(sel_d), _lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets),
-                                                    _lib.ptr(bb), _lib.ptr(count), _lib.ptr(info), n, cset.hw[0], cset.hw[1], self.C,
-                                                    float(um_pix), _lib.ptr(out), int(out_c), _lib.ptr(scratch), _lib.ptr(off_d),
-                                                    ops._stream()), "demia_crop_inscribed")
-
-    def launch_inscribed(self, um_pix: float = 1.0, slots: int = 4) -> None:
-        """:meth:`launch_measure` for the inscribed-circle descriptors (``demia_mask_inscribed`` / ``demia_crop_inscribed``): the
-        first ``slots`` contours of EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one
-        copy, behind the shape values.  (Masks with more contours than ``slots`` are computed again by :meth:`inscribed` on demand.)"""
-        self._islots, self._i_um = min(int(slots), self.C), float(um_pix)
-        self._insc_dev = torch.zeros((self.M, self._islots, INSCRIBED_COLS), dtype=torch.float64, device=self.ops.device)
-        self._inscribed_into(self._insc_dev, self._islots, um_pix)
-
-    def _skeleton_into(self, out: torch.Tensor, out_c: int, um_pix: float, sel: Optional[np.ndarray] = None) -> None:
-        """One launch of ``demia_mask_skeleton`` / ``demia_crop_skeleton`` into ``out`` [n, out_c, 8]: every mask, or the
-        positions ``sel`` -- their table rows are gathered, their words are read where they are (the entry's ``select``).  The
-        second scratch (planes: one more plane per mask, here; crops: ``CropMaskSet.skeleton_scratch``) is made on first use."""
-        ops = self.ops
-        if self._words is None:
-            raise RuntimeError("skeleton descriptors: the trace did not keep its words (trace(..., keep_words=True))")
-        n = self.M if sel is None else len(sel)
-        if n == 0:
-            return
-        count, info, sel_d, idx = self.count, self.info, None, None
-        if sel is not None:
-            sel_d = ops.upload(np.ascontiguousarray(sel, dtype=np.int32))
-            idx = sel_d.to(torch.int64)
-            count, info = self.count.index_select(0, idx), self.info.index_select(0, idx)
-        if self._words[0] == "plane":
-            _, packed, bbox, scratch, W = self._words
-            bb = bbox if idx is None else bbox.index_select(0, idx)
-            if self._skel_scratch2 is None:
-                self._skel_scratch2 = torch.empty_like(packed)   # only touched by regions that do not fit in LDS
-            _lib.check(ops.lib.demia_mask_skeleton(_lib.ptr(sel_d), _lib.ptr(packed), _lib.ptr(scratch), _lib.ptr(bb), _lib.ptr(count),
-                                                   _lib.ptr(info), n, int(packed.shape[1]), W, self.C, float(um_pix), _lib.ptr(out),
-                                                   int(out_c), _lib.ptr(self._skel_scratch2), 0, ops._stream()), "demia_mask_skeleton")
-        else:
-            _, cset, first = self._words
-            bb = cset.bbox[first:first + self.M]
-            if idx is not None:
-                bb, sel_d = bb.index_select(0, idx), sel_d + first
-            elif first:
-                sel_d = torch.arange(first, first + self.M, dtype=torch.int32, device=ops.device)
-            scratch, off_d = cset.inscribed_scratch()
-            scratch2, off2_d = cset.skeleton_scratch()
-            _lib.check(ops.lib.demia_crop_skeleton(_lib.ptr(sel_d), _lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets),
-                                                   _lib.ptr(bb), _lib.ptr(count), _lib.ptr(info), n, cset.hw[0], cset.hw[1], self.C,
-                                                   float(um_pix), _lib.ptr(out), int(out_c), _lib.ptr(scratch), _lib.ptr(off_d),
-                                                   _lib.ptr(scratch2), _lib.ptr(off2_d), 0, ops._stream()), "demia_crop_skeleton")
-
-    def launch_skeleton(self, um_pix: float = 1.0, slots: int = 4) -> None:
-        """:meth:`launch_measure` for the skeleton descriptors (``demia_mask_skeleton`` / ``demia_crop_skeleton``): the first
-        ``slots`` contours of EVERY mask, enqueued behind the trace without a wait; :meth:`fetch` carries the values in its one copy,
-        behind the inscribed values.  (Masks with more contours than ``slots`` are computed again by :meth:`skeleton` on demand.)"""
-        self._kslots, self._k_um = min(int(slots), self.C), float(um_pix)
-        self._skel_dev = torch.zeros((self.M, self._kslots, SKELETON_COLS), dtype=torch.float64, device=self.ops.device)
-        self._skeleton_into(self._skel_dev, self._kslots, um_pix)
-
     def fetch(self, extra: Optional[Sequence[torch.Tensor]] = None, with_points: bool = False):
         """ONE device-to-host wait for everything the host decides on: counters, contour counts, the first ``slots``
-        contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran, shape
-        descriptors when :meth:`launch_shape` ran, inscribed descriptors when :meth:`launch_inscribed` ran, skeleton descriptors
-        when :meth:`launch_skeleton` ran) and the
+        contour slots of every mask (info, area / perimeter, measurement values when :meth:`launch_measure` ran, then the values of
+        every family :meth:`launch` ran for, in table order whatever the launch order was) and the
         int32 device tensors in ``extra`` (returned as numpy arrays).  Falls back to the sliced copy of :meth:`host` when a
         mask has more contours than the slots fetched.  ``with_points``: the contour POINTS come over in the same copy --
         how many are in use is only known after the wait, so the copy takes as many as the previous trace of this
         ``MaskOps`` used (+ 25 %); when that was too few (the first call of a job) :meth:`records` copies them itself and
         counts it in ``blocking_point_copies``."""
         M = self.M
-        k = getattr(self, "_mslots", 4)
-        k = min(k, self.C)
+        k = min(self._mslots, self.C)
         parts = [self.counters, self.count, self.info[:, :k].reshape(-1)]
         f64 = [self.red[:, :k].reshape(-1)]
-        if getattr(self, "_vals_dev", None) is not None:
+        if self._vals_dev is not None:
             f64.append(self._vals_dev.reshape(-1))
-        if self._shape_dev is not None:
-            f64.append(self._shape_dev.reshape(-1))
-        if self._insc_dev is not None:
-            f64.append(self._insc_dev.reshape(-1))
-        if self._skel_dev is not None:
-            f64.append(self._skel_dev.reshape(-1))
+        live = [(self.launched[name], fam.cols) for name, fam in FAMILIES.items() if name in self.launched]
+        f64 += [st.dev.reshape(-1) for st, _ in live]
         extra = list(extra or [])
         parts += [e.reshape(-1) for e in extra]
         n_pts = min(int(getattr(self.ops, "_points_hint", 0)), self.max_points) if with_points else 0
@@ -601,28 +601,18 @@ class ContourSet:
             self.max_count = mc
             self._host = (count, info[:, :mc], red[:, :mc], int(cnt[0]))
             dpos = M * k * 2
-            if getattr(self, "_vals_dev", None) is not None:
+            if self._vals_dev is not None:
                 self._vals_host = d[dpos:dpos + M * k * 12].reshape(M, k, 12)[:, :mc]
                 dpos += M * k * 12
-            if self._shape_dev is not None:
-                ks = self._sslots
-                if mc <= ks:
-                    self._shape_host = d[dpos:dpos + M * ks * SHAPE_COLS].reshape(M, ks, SHAPE_COLS)[:, :mc]
-                dpos += M * ks * SHAPE_COLS
-            if self._insc_dev is not None:
-                ki = self._islots
-                if mc <= ki:
-                    self._insc_host = d[dpos:dpos + M * ki * INSCRIBED_COLS].reshape(M, ki, INSCRIBED_COLS)[:, :mc]
-                dpos += M * ki * INSCRIBED_COLS
-            if self._skel_dev is not None and mc <= self._kslots:
-                kk = self._kslots
-                self._skel_host = d[dpos:dpos + M * kk * SKELETON_COLS].reshape(M, kk, SKELETON_COLS)[:, :mc]
+            for st, cols in live:                                 # (a family launched with fewer slots than mc falls back alone)
+                size = M * st.slots * cols
+                st.host = d[dpos:dpos + size].reshape(M, st.slots, cols)[:, :mc] if mc <= st.slots else None
+                dpos += size
         else:                                                     # a mask with many contours: the general (two-wait) path
             self._host = None
             self._vals_host = None
-            self._shape_host = None
-            self._insc_host = None
-            self._skel_host = None
+            for st, _ in live:
+                st.host = None
             self.host()
         return outs
 
@@ -639,19 +629,22 @@ class ContourSet:
             out[m] = red[m, k, 1]
         return out
 
+    def _flags(self, select: Optional[Sequence[int]]) -> Optional[torch.Tensor]:
+        """[M] int32 on the device, 1 at the positions ``select``: the select of the point-table entries (None: every mask)."""
+        if select is None:
+            return None
+        flags = np.zeros(self.M, dtype=np.int32)
+        flags[np.asarray(list(select), dtype=np.int64)] = 1
+        return torch.from_numpy(flags).to(self.ops.device)
+
     def measure(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
         """[M, max contours per mask, 12] measurement values (only for the selected masks when ``select`` is given)."""
         ops = self.ops
         self.host()
-        pre = getattr(self, "_vals_host", None)
-        if pre is not None and abs(getattr(self, "_m_um", um_pix) - um_pix) == 0.0:
-            return pre                                    # measured for every mask right behind the trace (launch_measure)
+        if self._vals_host is not None and self._m_um == um_pix:
+            return self._vals_host                        # measured for every mask right behind the trace (launch_measure)
         M, C, mp, mc = self.M, self.C, self.max_points, self.max_count
-        sel_t = None
-        if select is not None:
-            flags = np.zeros(M, dtype=np.int32)
-            flags[np.asarray(list(select), dtype=np.int64)] = 1
-            sel_t = torch.from_numpy(flags).to(ops.device)
+        sel_t = self._flags(select)
         wi = torch.empty((int(ops.lib.demia_contour_work_ints(M, C, mp)),), dtype=torch.int32, device=ops.device)
         wf = torch.empty((int(ops.lib.demia_contour_work_floats(M, C, mp)),), dtype=torch.float32, device=ops.device)
         wd = torch.empty((int(ops.lib.demia_contour_work_doubles(M, C, mp)),), dtype=torch.float64, device=ops.device)
@@ -661,78 +654,27 @@ class ContourSet:
                                                  float(um_pix), _lib.ptr(vals), mc, ops._stream()), "demia_contour_measure")
         return vals.cpu().numpy()
 
-    def shape(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
-        """[M, max contours per mask, 10] shape descriptors (``demia_contour_shape``; only for the selected masks when ``select``
-        is given)."""
-        ops = self.ops
+    def descriptor(self, name: str, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
+        """[M, max contours per mask, cols] values of the family ``name`` of ``FAMILIES`` (only for the selected masks when ``select``
+        is given: the other rows are zero).  What :meth:`launch` + :meth:`fetch` brought over, else one launch on demand over the
+        contour slots in use (one more copy, as :meth:`measure`) -- a word family then reads the words where the trace's source keeps
+        them (:meth:`set_plane_words` / :meth:`set_crop_words`)."""
+        fam, = families((name,))
         self.host()
-        pre = self._shape_host
-        if pre is not None and abs(getattr(self, "_s_um", um_pix) - um_pix) == 0.0:
-            return pre                                    # computed for every mask right behind the trace (launch_shape)
-        M, C, mp, mc = self.M, self.C, self.max_points, self.max_count
-        sel_t = None
-        if select is not None:
-            flags = np.zeros(M, dtype=np.int32)
-            flags[np.asarray(list(select), dtype=np.int64)] = 1
-            sel_t = torch.from_numpy(flags).to(ops.device)
-        wi = torch.empty((int(ops.lib.demia_contour_shape_work_ints(M, C, mp)),), dtype=torch.int32, device=ops.device)
-        vals = torch.zeros((M, mc, SHAPE_COLS), dtype=torch.float64, device=ops.device)
-        _lib.check(ops.lib.demia_contour_shape(_lib.ptr(sel_t), _lib.ptr(self.count), _lib.ptr(self.info), _lib.ptr(self.red),
-                                               _lib.ptr(self.points), M, C, mp, _lib.ptr(wi), float(um_pix), _lib.ptr(vals), mc,
-                                               ops._stream()), "demia_contour_shape")
-        return vals.cpu().numpy()
-
-    def inscribed(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
-        """[M, max contours per mask, 8] inscribed descriptors (``demia_mask_inscribed`` / ``demia_crop_inscribed``; only for the
-        selected masks when ``select`` is given: the other rows are zero).  On demand the words are read where the trace's source
-        keeps them (:meth:`set_plane_words` / :meth:`set_crop_words`)."""
-        ops = self.ops
-        self.host()
-        pre = self._insc_host
-        if pre is not None and abs(getattr(self, "_i_um", um_pix) - um_pix) == 0.0:
-            return pre                                    # computed for every mask right behind the trace (launch_inscribed)
-        M, mc = self.M, self.max_count
-        vals = torch.zeros((M, mc, INSCRIBED_COLS), dtype=torch.float64, device=ops.device)
-        if select is None:
-            self._inscribed_into(vals, mc, um_pix)
-        else:
-            sel = np.asarray(list(select), dtype=np.int64)
-            part = torch.zeros((len(sel), mc, INSCRIBED_COLS), dtype=torch.float64, device=ops.device)
-            self._inscribed_into(part, mc, um_pix, sel)
-            if len(sel):
-                vals[torch.from_numpy(sel).to(ops.device)] = part
-        return vals.cpu().numpy()
-
-    def skeleton(self, um_pix: float = 1.0, select: Optional[Sequence[int]] = None) -> np.ndarray:
-        """[M, max contours per mask, 8] skeleton descriptors (``demia_mask_skeleton`` / ``demia_crop_skeleton``; only for the
-        selected masks when ``select`` is given: the other rows are zero).  On demand the words are read where the trace's source
-        keeps them (:meth:`set_plane_words` / :meth:`set_crop_words`)."""
-        ops = self.ops
-        self.host()
-        pre = self._skel_host
-        if pre is not None and abs(getattr(self, "_k_um", um_pix) - um_pix) == 0.0:
-            return pre                                    # computed for every mask right behind the trace (launch_skeleton)
-        M, mc = self.M, self.max_count
-        vals = torch.zeros((M, mc, SKELETON_COLS), dtype=torch.float64, device=ops.device)
-        if select is None:
-            self._skeleton_into(vals, mc, um_pix)
-        else:
-            sel = np.asarray(list(select), dtype=np.int64)
-            part = torch.zeros((len(sel), mc, SKELETON_COLS), dtype=torch.float64, device=ops.device)
-            self._skeleton_into(part, mc, um_pix, sel)
-            if len(sel):
-                vals[torch.from_numpy(sel).to(ops.device)] = part
+        st = self.launched.get(name)
+        if st is not None and st.host is not None and st.um_pix == um_pix:
+            return st.host                                # computed for every mask right behind the trace (launch)
+        vals = torch.zeros((self.M, self.max_count, fam.cols), dtype=torch.float64, device=self.ops.device)
+        fam.enqueue(self, vals, self.max_count, um_pix, None if select is None else np.asarray(list(select), dtype=np.int64))
         return vals.cpu().numpy()
 
     def records(self, um_pix: float = 1.0, measure: bool = True, select: Optional[Sequence[int]] = None, with_points: bool = True,
-                shape: bool = False, inscribed: bool = False, skeleton: bool = False):
-        """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start).  ``shape``: each
-        dict also holds ``shape``, the contour's 10 values of :meth:`shape`; ``inscribed``: likewise ``inscribed``, the 8 values of
-        :meth:`inscribed`, and ``skeleton``: ``skeleton``, the 8 values of :meth:`skeleton`."""
+                descriptors: Sequence[str] = ()):
+        """Per (selected) mask the list of contour dicts in OpenCV's order (reverse raster order of the start).  ``descriptors``: each
+        dict also holds, under the name of every family named, the contour's values of :meth:`descriptor`."""
+        fams = families(descriptors)
         vals = self.measure(um_pix, select) if measure else None
-        shp = self.shape(um_pix, select) if shape else None
-        ins = self.inscribed(um_pix, select) if inscribed else None
-        skl = self.skeleton(um_pix, select) if skeleton else None
+        desc = {fam.name: self.descriptor(fam.name, um_pix, select) for fam in fams}
         count, info, red, used = self.host()
         pts = None
         if with_points:
@@ -751,12 +693,8 @@ class ContourSet:
                     rec["points"] = pts[off: off + n]             # views of this call's own host copies
                 if vals is not None:
                     rec["values"] = vals[m, c]
-                if shp is not None:
-                    rec["shape"] = shp[m, c]
-                if ins is not None:
-                    rec["inscribed"] = ins[m, c]
-                if skl is not None:
-                    rec["skeleton"] = skl[m, c]
+                for name, v in desc.items():
+                    rec[name] = v[m, c]
                 recs.append(rec)
             if len(recs) > 1:
                 recs.sort(key=lambda r: (r["start"][1], r["start"][0]), reverse=True)

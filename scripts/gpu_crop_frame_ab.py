@@ -5,14 +5,15 @@ process, the frames alternating (full, crop, full, crop, ...; the fourth argumen
 full,crop,crop_direct), same models, same image, same box.  A frame written as ``<frame>+shape`` runs with
 `inference_settings.shape_descriptors: true` (e.g. crop_direct,crop_direct+shape: the setting off and on, alternating), one written
 as ``<frame>+inscribed`` with `inference_settings.inscribed_descriptors: true`, one written as ``<frame>+skeleton`` with
-`inference_settings.skeleton_descriptors: true`; several suffixes may follow one frame.
+`inference_settings.skeleton_descriptors: true` -- any family of `maskset.FAMILIES`; several suffixes may follow one frame.
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
 (`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`), the device-to-host waits of the post-processing (the pipeline's
 own counter) and every `Tensor.cpu()` / `Tensor.item()` call of the image (counted here: `measure_image`'s waits are among them; a
 fetch that meets a mask with more contours than slots falls back to on-demand launches with copies of their own, counted apart), the
-most full-frame planes alive after the tile mapping, and whether all frames wrote the same rows (their 20 reference columns) and texts.
+most full-frame planes alive after the tile mapping, whether all frames wrote the same rows (their 20 reference columns) and texts, and
+a digest of ALL columns of the rows (`rows_sha256`: what pins the descriptor columns from one commit to the next).
 
     python scripts/gpu_crop_frame_ab.py [size=8192] [reps=4] [out.json] [frames=full,crop]
 """
@@ -43,6 +44,7 @@ os.chdir(root)
 
 from deepemia_amd.engine import MaskRCNNEngine
 from deepemia_amd.functions import inference as I
+from deepemia_amd.maskset import ContourSet, families
 from deepemia_amd.predictor import Predictor
 from deepemia_amd.utils.mask_utils import rle_crop_launch, rle_text_from_payload
 from deepemia_amd.utils.spatial_constraints import load_spatial_constraints
@@ -56,27 +58,24 @@ pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"
 spatial_cfg = load_spatial_constraints(T.DATASET)
 metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
 pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f.split("+")[0]), st.global_config) for f in frames}
-shape_on = {f: "shape" in f.split("+")[1:] for f in frames}
-inscribed_on = {f: "inscribed" in f.split("+")[1:] for f in frames}
-skeleton_on = {f: "skeleton" in f.split("+")[1:] for f in frames}
+descriptors = {f: tuple(fam.name for fam in families(f.split("+")[1:])) for f in frames}      # (an unknown suffix: ValueError)
 host_copies = [0]
 for _name in ("cpu", "item"):
     def _counted(self, *a, _orig=getattr(torch.Tensor, _name), **k):
         host_copies[0] += bool(self.is_cuda)
         return _orig(self, *a, **k)
     setattr(torch.Tensor, _name, _counted)
-from deepemia_amd.maskset import ContourSet
 fallbacks = [0]                      # fetches that met a mask with more contours than slots: measurements (shape, inscribed, skeleton values) on demand
 def _fetch(self, *a, _orig=ContourSet.fetch, **k):
     out = _orig(self, *a, **k)
-    fallbacks[0] += self.max_count > min(getattr(self, "_mslots", 4), self.C)
+    fallbacks[0] += self.max_count > min(self._mslots, self.C)
     return out
 ContourSet.fetch = _fetch
 small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes([("big.tif", image_dev)]), 50)
 pipes[frames[0]].drop_cached("big.tif")
 
 
-def one_image(pipe, shape=False, inscribed=False, skeleton=False):
+def one_image(pipe, descriptors=()):
     """process_image of run_inference for this image: instances, RLE texts, measurement rows."""
     name = "big.tif"
     pipe.begin_image_stats()
@@ -90,27 +89,29 @@ def one_image(pipe, shape=False, inscribed=False, skeleton=False):
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, shape=shape, inscribed=inscribed, skeleton=skeleton)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     pipe.drop_cached(name)
     return n, rows, texts, pipe.end_image_stats((size, size))
 
 
 runs = {f: [] for f in pipes}
-digest = {}
+digest, digest_all = {}, {}          # per frame: texts + the 20 reference columns; ALL columns of the rows
 for rep in range(reps):
     for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ... (the order of `frames`)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         w0, c0, f0 = pipe.d2h_waits, host_copies[0], fallbacks[0]
         t0 = time.perf_counter()
-        n, rows, texts, stats = one_image(pipe, shape_on[frame], inscribed_on[frame], skeleton_on[frame])
+        n, rows, texts, stats = one_image(pipe, descriptors[frame])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert all(len(r) == 20 + 7 * shape_on[frame] + 6 * inscribed_on[frame] + 5 * skeleton_on[frame] for r in rows)
+        assert all(len(r) == 20 + sum(len(I.DESCRIPTOR_CSV[name][0]) for name in descriptors[frame]) for r in rows)
         h = hashlib.sha256(("\n".join(texts) + repr([r[:20] for r in rows])).encode()).hexdigest()
+        h_all = hashlib.sha256(repr(rows).encode()).hexdigest()
         digest.setdefault(frame, h)
-        assert digest[frame] == h, "a repetition wrote other rows"
+        digest_all.setdefault(frame, h_all)
+        assert digest[frame] == h and digest_all[frame] == h_all, "a repetition wrote other rows"
         runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0,
                                 host_copies=host_copies[0] - c0, fetch_fallbacks=fallbacks[0] - f0, instances=n,
                                 rows=len(rows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
@@ -126,6 +127,7 @@ for frame, rr in runs.items():
                                 steady_min_max_seconds=[min(steady), max(steady)] if steady else None,
                                 peak_bytes_first=rr[0]["peak_bytes"], peak_bytes_steady=max(r["peak_bytes"] for r in rr[1:]) if steady else None,
                                 d2h_waits_per_image=rr[-1]["d2h_waits"], host_copies_per_image=rr[-1]["host_copies"], fetch_fallbacks_per_image=rr[-1]["fetch_fallbacks"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
+                                rows20_texts_sha256=digest[frame], rows_sha256=digest_all[frame],
                                 full_frame_planes_peak=max(r["full_frame_planes_peak"] for r in rr))
 out_path.parent.mkdir(parents=True, exist_ok=True)
 out_path.write_text(json.dumps(res, indent=1))

@@ -53,12 +53,12 @@ def test_contour_counts_and_nested_component(cases):
 
 def test_setting_default_off_per_dataset_bool_only():
     from deepemia_amd.functions import inference as inf
-    assert inf.inscribed_descriptors_setting({}) is False and inf.inscribed_descriptors_setting(None) is False
-    assert inf.inscribed_descriptors_setting({"inscribed_descriptors": True}) is True
-    assert inf.inscribed_descriptors_setting({"inscribed_descriptors": False, "shape_descriptors": True}) is False
+    assert inf.descriptors_setting({}) == () and inf.descriptors_setting(None) == ()
+    assert inf.descriptors_setting({"inscribed_descriptors": True}) == ("inscribed",)
+    assert inf.descriptors_setting({"inscribed_descriptors": False, "shape_descriptors": True}) == ("shape",)
     for bad in (1, 0, "true", "yes", None, [True], 1.0):
         with pytest.raises(ValueError, match="inscribed_descriptors"):
-            inf.inscribed_descriptors_setting({"inscribed_descriptors": bad})
+            inf.descriptors_setting({"inscribed_descriptors": bad})
     assert len(inf.INSCRIBED_CSV_HEADER) == 6 and not set(inf.INSCRIBED_CSV_HEADER) & set(inf.CSV_HEADER + inf.SHAPE_CSV_HEADER)
 
 

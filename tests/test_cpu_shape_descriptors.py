@@ -113,18 +113,18 @@ def _settings(tmp_path, monkeypatch, overrides):
 
 
 def test_setting_defaults_to_off_and_is_read_per_dataset(tmp_path, monkeypatch):
-    from deepemia_amd.functions.inference import shape_descriptors_setting
-    assert shape_descriptors_setting({}) is False and shape_descriptors_setting(None) is False
-    assert shape_descriptors_setting({"shape_descriptors": True}) is True
-    assert _settings(tmp_path, monkeypatch, {"tile_settings": {"tile_size": 256}}).shape_descriptors is False
-    assert _settings(tmp_path, monkeypatch, {"shape_descriptors": True, "mask_frame": "crop_direct"}).shape_descriptors is True
+    from deepemia_amd.functions.inference import descriptors_setting
+    assert descriptors_setting({}) == () and descriptors_setting(None) == ()
+    assert descriptors_setting({"shape_descriptors": True}) == ("shape",)
+    assert _settings(tmp_path, monkeypatch, {"tile_settings": {"tile_size": 256}}).descriptors == ()
+    assert _settings(tmp_path, monkeypatch, {"shape_descriptors": True, "mask_frame": "crop_direct"}).descriptors == ("shape",)
 
 
 @pytest.mark.parametrize("value", ["true", "on", 1, 0, None, [True], 1.0])
 def test_setting_accepts_a_bool_only(tmp_path, monkeypatch, value):
-    from deepemia_amd.functions.inference import shape_descriptors_setting
+    from deepemia_amd.functions.inference import descriptors_setting
     with pytest.raises(ValueError, match="shape_descriptors"):
-        shape_descriptors_setting({"shape_descriptors": value})
+        descriptors_setting({"shape_descriptors": value})
     with pytest.raises(ValueError, match="shape_descriptors"):
         _settings(tmp_path, monkeypatch, {"shape_descriptors": value})       # raised while the settings are read: no model yet
 

@@ -70,12 +70,14 @@ def test_invariants_on_random_masks():
 
 def test_setting_default_off_per_dataset_bool_only():
     from deepemia_amd.functions import inference as inf
-    assert inf.skeleton_descriptors_setting({}) is False and inf.skeleton_descriptors_setting(None) is False
-    assert inf.skeleton_descriptors_setting({"skeleton_descriptors": True}) is True
-    assert inf.skeleton_descriptors_setting({"skeleton_descriptors": False, "inscribed_descriptors": True}) is False
+    assert inf.descriptors_setting({}) == () and inf.descriptors_setting(None) == ()
+    assert inf.descriptors_setting({"skeleton_descriptors": True}) == ("skeleton",)
+    assert inf.descriptors_setting({"skeleton_descriptors": False, "inscribed_descriptors": True}) == ("inscribed",)
+    # table order, whatever the order of the keys
+    assert inf.descriptors_setting({"skeleton_descriptors": True, "inscribed_descriptors": True, "shape_descriptors": True}) == ("shape", "inscribed", "skeleton")
     for bad in (1, 0, "true", "yes", None, [True], 1.0):
         with pytest.raises(ValueError, match="skeleton_descriptors"):
-            inf.skeleton_descriptors_setting({"skeleton_descriptors": bad})
+            inf.descriptors_setting({"skeleton_descriptors": bad})
     assert inf.SKELETON_CSV_HEADER == ["Skeleton length", "Skeleton mean width", "Skeleton end points", "Skeleton branch points",
                                        "Skeleton pixels"]
     assert not set(inf.SKELETON_CSV_HEADER) & set(inf.CSV_HEADER + inf.SHAPE_CSV_HEADER + inf.INSCRIBED_CSV_HEADER)
@@ -99,8 +101,7 @@ def test_row_widths_of_all_eight_combinations():
                 rec["skeleton"] = skel
             rows = inf.measurement_rows("img.tif", [1], [[rec, dict(rec, area=1.0)]], ["a", "b"], 5.0)      # the second: below the area gate
             assert len(rows) == 1
-            header = (inf.CSV_HEADER + (inf.SHAPE_CSV_HEADER if with_shape else []) + (inf.INSCRIBED_CSV_HEADER if with_insc else []) +
-                      (inf.SKELETON_CSV_HEADER if with_skel else []))
+            header = inf.CSV_HEADER + [col for name, (cols, _) in inf.DESCRIPTOR_CSV.items() if name in rec for col in cols]
             assert len(header) == len(rows[0])
             widths.append(len(rows[0]))
             assert rows[0][:20] == plain
@@ -113,6 +114,34 @@ def test_row_widths_of_all_eight_combinations():
                 # Skeleton length, mean width, end points, branch points, pixels
                 assert rows[0][-5:] == [44.04, 5.108, 2.0, 1.0, 74.0] and all(type(x) is float for x in rows[0][-5:])
     assert sorted(widths) == [20, 25, 26, 27, 31, 32, 33, 38]
+
+
+def test_rows_of_every_subset_follow_the_table():
+    """Each family a record holds appends its columns of ``DESCRIPTOR_CSV`` behind the 20, at the offset the table order gives it,
+    whatever the order of the record's keys; the table is the one of ``maskset.FAMILIES``."""
+    import itertools
+
+    from deepemia_amd.functions import inference as inf
+    from deepemia_amd.maskset import FAMILIES
+    assert list(inf.DESCRIPTOR_CSV) == list(FAMILIES) == ["shape", "inscribed", "skeleton"]
+    assert [FAMILIES[n].cols for n in FAMILIES] == [10, 8, 8] and [FAMILIES[n].words for n in FAMILIES] == [False, True, True]
+    assert [inf.DESCRIPTOR_CSV[n][1] for n in FAMILIES] == [(3, 4, 5, 6, 7, 8, 9), (5, 1, 2, 6, 7, 3), (6, 7, 3, 4, 0)]
+    assert (inf.SHAPE_CSV_HEADER, inf.INSCRIBED_CSV_HEADER, inf.SKELETON_CSV_HEADER) == tuple(inf.DESCRIPTOR_CSV[n][0] for n in FAMILIES)
+    values = {n: 1000.0 * (i + 1) + np.arange(float(FAMILIES[n].cols)) for i, n in enumerate(FAMILIES)}
+    subsets = [s for k in range(4) for s in itertools.combinations(FAMILIES, k)]
+    assert len(subsets) == 8
+    for subset in subsets:
+        rec = dict(area=50.0, perimeter=30.0, values=np.arange(12.0))
+        for name in reversed(subset):                                    # keys in reverse table order
+            rec[name] = values[name]
+        row, = inf.measurement_rows("img.tif", [1], [[rec]], ["a", "b"], 5.0)
+        assert len(row) == 20 + sum(len(inf.DESCRIPTOR_CSV[n][0]) for n in subset)
+        at = 20
+        for name in subset:                                              # (combinations keeps the table order)
+            header, index = inf.DESCRIPTOR_CSV[name]
+            assert len(header) == len(index) and row[at:at + len(header)] == [float(values[name][k]) for k in index]
+            at += len(header)
+        assert at == len(row)
 
 
 # ------------------------------------------------------------------------------------------------------ the second scratch

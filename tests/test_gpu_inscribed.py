@@ -271,7 +271,7 @@ def test_crop_words_equal_planes(ops, cases):
     cset = CropMaskSet.from_planes(ops, planes, W)
     ccs = cset.trace(max_contours=16, keep_words=True)
     assert torch.equal(ccs.count, cs.count)
-    got = ccs.inscribed(UM)
+    got = ccs.descriptor("inscribed", UM)
     for m in range(len(masks)):                                          # (a second trace may leave a mask's contours in other slots)
         n = int(cs.host()[0][m])
         a = got[m, :n][np.lexsort((ccs.host()[1][m, :n, 0], ccs.host()[1][m, :n, 1]))]
@@ -343,24 +343,25 @@ def test_launch_slots_equals_on_demand(ops, cases, monkeypatch):
         planes = ops.from_dense(masks)
         cs = ops.trace(planes, max_contours=16, keep_words=True)
         cs.launch_measure(UM, slots=4)
-        cs.launch_inscribed(UM, slots=4)
+        cs.launch("inscribed", UM, slots=4)
         copies = _spy_copies(monkeypatch)
         cs.fetch(with_points=True)
-        full = cs.inscribed(UM)
+        full = cs.descriptor("inscribed", UM)
         if not fallback:
             assert copies[0] == 1                                        # counts, tables, measurements and inscribed values: ONE copy
         monkeypatch.undo()
-        first = cs._insc_dev.cpu().numpy()
-        assert (cs._insc_host is None) == fallback
-        carried, cs._insc_host = cs._insc_host, None                     # on demand, on the SAME tables, as if nothing had ridden along
-        demand = cs.inscribed(UM)
-        picked = cs.inscribed(UM, select=[2])
-        cs._insc_host = carried
+        st = cs.launched["inscribed"]
+        first = st.dev.cpu().numpy()
+        assert (st.host is None) == fallback
+        carried, st.host = st.host, None                                 # on demand, on the SAME tables, as if nothing had ridden along
+        demand = cs.descriptor("inscribed", UM)
+        picked = cs.descriptor("inscribed", UM, select=[2])
+        st.host = carried
         n = int(cs.host()[0].max())
         assert (n > 4) == fallback and full.shape == demand.shape == (len(masks), n, COLS)
         assert (_bits(full) == _bits(demand)).all() and (_bits(first[:, :min(n, 4)]) == _bits(full[:, :4])).all()
         assert (_bits(picked[2]) == _bits(full[2])).all() and not picked[:2].any()
-        recs = cs.records(um_pix=UM, inscribed=True)
+        recs = cs.records(um_pix=UM, descriptors=("inscribed",))
         assert all("inscribed" not in r for rs in cs.records(um_pix=UM) for r in rs)
         for mask, rs in zip(masks, recs):
             ref = IR.Reference(mask) if mask.any() else None
@@ -371,14 +372,14 @@ def test_launch_slots_equals_on_demand(ops, cases, monkeypatch):
     masks = np.stack([six, few, ringm, six[::-1, ::-1].copy(), ringm[:, ::-1].copy()])
     cset = CropMaskSet.from_planes(ops, ops.from_dense(masks), W)
     cp = CropPlanes(ops, (H, W), chunk=2)
-    chunks = list(trace_chunks(cset, cp, max_contours=16, um_pix=UM, inscribed=True))
+    chunks = list(trace_chunks(cset, cp, max_contours=16, um_pix=UM, descriptors=("inscribed",)))
     assert [(f, n) for f, n, _ in chunks] == [(0, 2), (2, 2), (4, 1)]
     torch.cuda.synchronize()
     for f, n, cs in chunks:
         cs.fetch(with_points=True)
-    assert chunks[0][2]._insc_host is None and chunks[1][2]._insc_host is None and chunks[2][2]._insc_host is not None
+    assert [c[2].launched["inscribed"].host is None for c in chunks] == [True, True, False]
     for f, n, cs in chunks:
-        recs = cs.records(um_pix=UM, inscribed=True)
+        recs = cs.records(um_pix=UM, descriptors=("inscribed",))
         for mask, rs in zip(masks[f:f + n], recs):
             ref = IR.Reference(mask)
             assert len(rs) == len(ref.starts())
@@ -397,12 +398,12 @@ def test_measure_and_shape_values_are_untouched(ops, cases):
     for insc in (False, True):
         cs = ops.trace(planes, max_contours=16, keep_words=insc)
         cs.launch_measure(UM, slots=8)
-        cs.launch_shape(UM, slots=8)
+        cs.launch("shape", UM, slots=8)
         if insc:
-            cs.launch_inscribed(UM, slots=8)
+            cs.launch("inscribed", UM, slots=8)
         cs.fetch(with_points=True)
         order = [np.lexsort((cs.host()[1][m, :int(cs.host()[0][m]), 0], cs.host()[1][m, :int(cs.host()[0][m]), 1])) for m in range(len(masks))]
-        out.append([(torch.from_numpy(cs.measure(UM)[m][o].copy()), torch.from_numpy(cs.shape(UM)[m][o].copy())) for m, o in enumerate(order)])
+        out.append([(torch.from_numpy(cs.measure(UM)[m][o].copy()), torch.from_numpy(cs.descriptor("shape", UM)[m][o].copy())) for m, o in enumerate(order)])
     for (v0, s0), (v1, s1) in zip(*out):
         assert v0.shape[1] == 12 and s0.shape[1] == 10 and torch.equal(v0, v1) and torch.equal(s0, s1)
 

@@ -189,7 +189,7 @@ def _many_contours_mask():
 
 
 def test_launch_shape_slots_equals_shape(gpu_device):
-    """``launch_shape(slots=4)`` + ``fetch`` against ``shape()``: a set whose masks fit the slots (the values ride on the fetch) and a
+    """``launch("shape", slots=4)`` + ``fetch`` against ``descriptor("shape")``: a set whose masks fit the slots (the values ride on the fetch) and a
     mask with more contours than slots (the fallback computes them on demand)."""
     from deepemia_amd.maskset import MaskOps
 
@@ -203,15 +203,16 @@ def test_launch_shape_slots_equals_shape(gpu_device):
         planes = ops.from_dense(masks)
         cs = ops.trace(planes, max_contours=16)
         cs.launch_measure(UM, slots=4)
-        cs.launch_shape(UM, slots=4)
+        cs.launch("shape", UM, slots=4)
         cs.fetch(with_points=True)
-        first = cs._shape_dev.cpu().numpy()                             # [M, 4, 10]
-        assert (cs._shape_host is None) == fallback
-        full = cs.shape(UM)
+        st = cs.launched["shape"]
+        first = st.dev.cpu().numpy()                                    # [M, 4, 10]
+        assert (st.host is None) == fallback
+        full = cs.descriptor("shape", UM)
         # on demand, on the SAME tables (a second trace may leave a mask's contours in other slots): as if nothing had ridden along
-        carried, cs._shape_host = cs._shape_host, None
-        demand = cs.shape(UM)
-        cs._shape_host = carried
+        carried, st.host = st.host, None
+        demand = cs.descriptor("shape", UM)
+        st.host = carried
         n = int(cs.host()[0].max())
         assert (n > 4) == fallback and full.shape == demand.shape == (len(masks), n, COLS)
         assert (_bits(full) == _bits(demand)).all()
@@ -219,7 +220,7 @@ def test_launch_shape_slots_equals_shape(gpu_device):
         count = cs.host()[0]
         for m in range(len(masks)):
             assert not full[m, int(count[m]):].any()                   # rows as allocated
-        recs = cs.records(um_pix=UM, shape=True)
+        recs = cs.records(um_pix=UM, descriptors=("shape",))
         plain = cs.records(um_pix=UM)
         assert all("shape" not in r for rs in plain for r in rs)
         for rs, ps in zip(recs, plain):

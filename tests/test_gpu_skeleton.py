@@ -331,7 +331,7 @@ def test_crop_words_equal_planes(ops, cases):
     cset = CropMaskSet.from_planes(ops, planes, W)
     ccs = cset.trace(max_contours=16, keep_words=True)
     assert torch.equal(ccs.count, cs.count)
-    got = ccs.skeleton(UM)
+    got = ccs.descriptor("skeleton", UM)
     for m in range(len(masks)):                                          # (a second trace may leave a mask's contours in other slots)
         n = int(cs.host()[0][m])
         a = got[m, :n][np.lexsort((ccs.host()[1][m, :n, 0], ccs.host()[1][m, :n, 1]))]
@@ -412,25 +412,26 @@ def test_launch_slots_equals_on_demand(ops, cases, monkeypatch):
         planes = ops.from_dense(masks)
         cs = ops.trace(planes, max_contours=16, keep_words=True)
         cs.launch_measure(UM, slots=4)
-        cs.launch_inscribed(UM, slots=4)
-        cs.launch_skeleton(UM, slots=4)
+        cs.launch("inscribed", UM, slots=4)
+        cs.launch("skeleton", UM, slots=4)
         copies = _spy_copies(monkeypatch)
         cs.fetch(with_points=True)
-        full = cs.skeleton(UM)
+        full = cs.descriptor("skeleton", UM)
         if not fallback:
             assert copies[0] == 1                                        # counts, tables, measurements, inscribed and skeleton values: ONE copy
         monkeypatch.undo()
-        first = cs._skel_dev.cpu().numpy()
-        assert (cs._skel_host is None) == fallback
-        carried, cs._skel_host = cs._skel_host, None                     # on demand, on the SAME tables, as if nothing had ridden along
-        demand = cs.skeleton(UM)
-        picked = cs.skeleton(UM, select=[2])
-        cs._skel_host = carried
+        st = cs.launched["skeleton"]
+        first = st.dev.cpu().numpy()
+        assert (st.host is None) == fallback
+        carried, st.host = st.host, None                                 # on demand, on the SAME tables, as if nothing had ridden along
+        demand = cs.descriptor("skeleton", UM)
+        picked = cs.descriptor("skeleton", UM, select=[2])
+        st.host = carried
         n = int(cs.host()[0].max())
         assert (n > 4) == fallback and full.shape == demand.shape == (len(masks), n, COLS)
         assert (_bits(full) == _bits(demand)).all() and (_bits(first[:, :min(n, 4)]) == _bits(full[:, :4])).all()
         assert (_bits(picked[2]) == _bits(full[2])).all() and not picked[:2].any()
-        recs = cs.records(um_pix=UM, skeleton=True)
+        recs = cs.records(um_pix=UM, descriptors=("skeleton",))
         assert all("skeleton" not in r for rs in cs.records(um_pix=UM) for r in rs)
         for mask, rs in zip(masks, recs):
             ref = SR.Reference(mask) if mask.any() else None
@@ -441,14 +442,14 @@ def test_launch_slots_equals_on_demand(ops, cases, monkeypatch):
     masks = np.stack([six, few, ringm, six[::-1, ::-1].copy(), ringm[:, ::-1].copy()])
     cset = CropMaskSet.from_planes(ops, ops.from_dense(masks), W)
     cp = CropPlanes(ops, (H, W), chunk=2)
-    chunks = list(trace_chunks(cset, cp, max_contours=16, um_pix=UM, skeleton=True))
+    chunks = list(trace_chunks(cset, cp, max_contours=16, um_pix=UM, descriptors=("skeleton",)))
     assert [(f, n) for f, n, _ in chunks] == [(0, 2), (2, 2), (4, 1)]
     torch.cuda.synchronize()
     for f, n, cs in chunks:
         cs.fetch(with_points=True)
-    assert chunks[0][2]._skel_host is None and chunks[1][2]._skel_host is None and chunks[2][2]._skel_host is not None
+    assert [c[2].launched["skeleton"].host is None for c in chunks] == [True, True, False]
     for f, n, cs in chunks:
-        recs = cs.records(um_pix=UM, skeleton=True)
+        recs = cs.records(um_pix=UM, descriptors=("skeleton",))
         for mask, rs in zip(masks[f:f + n], recs):
             ref = SR.Reference(mask)
             assert len(rs) == len(ref.starts())
@@ -458,6 +459,8 @@ def test_launch_slots_equals_on_demand(ops, cases, monkeypatch):
 
 # ------------------------------------------------------------------------------------- 6. the 12 + 10 + 8 other values untouched
 def test_measure_shape_and_inscribed_values_are_untouched(ops, cases):
+    from functools import partial
+
     import torch
     H, W = 150, 230
     masks = _frame_of_cases(cases, ["six_components", "ring", "dumbbell"], H, W, [(20, 33), (5, 160), (60, 10)])
@@ -467,14 +470,14 @@ def test_measure_shape_and_inscribed_values_are_untouched(ops, cases):
     for skel in (False, True):
         cs = ops.trace(planes, max_contours=16, keep_words=True)
         cs.launch_measure(UM, slots=8)
-        cs.launch_shape(UM, slots=8)
-        cs.launch_inscribed(UM, slots=8)
+        cs.launch("shape", UM, slots=8)
+        cs.launch("inscribed", UM, slots=8)
         if skel:
-            cs.launch_skeleton(UM, slots=8)
+            cs.launch("skeleton", UM, slots=8)
         cs.fetch(with_points=True)
-        assert (cs._skel_host is not None) == skel
+        assert ("skeleton" in cs.launched and cs.launched["skeleton"].host is not None) == skel
         order = [np.lexsort((cs.host()[1][m, :int(cs.host()[0][m]), 0], cs.host()[1][m, :int(cs.host()[0][m]), 1])) for m in range(len(masks))]
-        out.append([tuple(torch.from_numpy(f(UM)[m][o].copy()) for f in (cs.measure, cs.shape, cs.inscribed)) for m, o in enumerate(order)])
+        out.append([tuple(torch.from_numpy(f(UM)[m][o].copy()) for f in (cs.measure, partial(cs.descriptor, "shape"), partial(cs.descriptor, "inscribed"))) for m, o in enumerate(order)])
     for a, b in zip(*out):
         assert [v.shape[1] for v in a] == [12, 10, 8] and all(torch.equal(x, y) for x, y in zip(a, b))
 
