@@ -42,6 +42,10 @@ __device__ void bitonic_desc(unsigned long long* a, int n) {
     }
 }
 
+// torch.clamp(x, max=c) as Detectron2's apply_deltas applies it to the size deltas: a NaN stays a NaN (fminf would return c, and
+// the row of a NaN delta would come out finite and be kept; upstream drops it as not finite).  The same value as fminf otherwise.
+__device__ __forceinline__ float clamp_max(float x, float c) { return x > c ? c : x; }
+
 __device__ __forceinline__ bool iou_gt(const float4 a, const float4 b, float thr) {
     // torchvision nms_kernel: area = (x2-x1)*(y2-y1); suppress when inter / (a + b - inter) > thr
     const float aa = (a.z - a.x) * (a.w - a.y);
@@ -288,7 +292,7 @@ __global__ __launch_bounds__(1024) void rpn_level_kernel(const RpnP p) {
         const float widths = ax2 - ax1, heights = ay2 - ay1;
         const float cx = ax1 + 0.5f * widths, cy = ay1 + 0.5f * heights;
         const float dx = d[0], dy = d[1];
-        const float dw = fminf(d[2], SCALE_CLAMP), dh = fminf(d[3], SCALE_CLAMP);
+        const float dw = clamp_max(d[2], SCALE_CLAMP), dh = clamp_max(d[3], SCALE_CLAMP);
         const float pcx = dx * widths + cx, pcy = dy * heights + cy;
         const float pw = expf(dw) * widths, ph = expf(dh) * heights;
         float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
@@ -393,7 +397,7 @@ __device__ __forceinline__ float4 det_class_box(const float* d, const float4& pb
     const float widths = pb.z - pb.x, heights = pb.w - pb.y;
     const float cx = pb.x + 0.5f * widths, cy = pb.y + 0.5f * heights;
     const float dx = d[0] / 10.0f, dy = d[1] / 10.0f;
-    const float dw = fminf(d[2] / 5.0f, SCALE_CLAMP), dh = fminf(d[3] / 5.0f, SCALE_CLAMP);
+    const float dw = clamp_max(d[2] / 5.0f, SCALE_CLAMP), dh = clamp_max(d[3] / 5.0f, SCALE_CLAMP);
     const float pcx = dx * widths + cx, pcy = dy * heights + cy;
     const float pw = expf(dw) * widths, ph = expf(dh) * heights;
     const float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;

@@ -235,7 +235,7 @@ typedef struct demia_rpn_desc {
     int32_t head_ld;
     int32_t N;
     int32_t img_h, img_w;        /* unpadded network-input size boxes are clipped to */
-    int32_t pre_topk, post_topk; /* <= 1024 each */
+    int32_t pre_topk, post_topk; /* 1 <= pre_topk <= 1000, 1 <= post_topk <= 1024; head_ld >= 15 (else DEMIA_EINVAL) */
     float nms_thresh;
     float* out_boxes;
     float* out_scores;

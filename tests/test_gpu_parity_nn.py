@@ -525,9 +525,9 @@ def test_box_detections_follow_torchvisions_batched_nms_branch_on_threshold_pair
 def test_box_detections_many_classes_and_a_non_finite_row(env, k):
     """demia_box_detections with K = 1, 3 and 12 classes and 1000 proposals (up to 12 000 (proposal, class) pairs; only
     those above the score threshold take a sort slot; class and delta columns sit at K-dependent offsets of the engine's
-    (5 K + 1 + 3) // 4 * 4-wide rows) and one proposal whose box is not finite: same survivors, order and classes as the
-    oracle's fast_rcnn_inference.  The non-finite row is the one with the highest class score, so keeping it would change
-    the first detection.  K = 12 fills all 100 slots; a one-class softmax need not."""
+    (5 K + 1 + 3) // 4 * 4-wide rows) and two proposals whose boxes are not finite (an overflowing centre delta, a NaN size
+    delta): same survivors, order and classes as the oracle's fast_rcnn_inference.  The non-finite rows are the two with the
+    highest class scores, so keeping either would change the first detection.  K = 12 fills all 100 slots; a one-class softmax need not."""
     import torch.nn.functional as F2
 
     eng, R, dev = env["eng"], env["R"], env["dev"]
@@ -543,11 +543,18 @@ def test_box_detections_many_classes_and_a_non_finite_row(env, k):
     # inf coordinates, and Detectron2 drops the whole row
     bw[top] = 100.0
     deltas[top, 4 * (k // 2)] = 3.0e38
+    # ... and the row with the second highest class score has a NaN height delta: torch.clamp(max=) keeps the NaN, the box is
+    # NaN and the row is dropped as well (a clamp that returns its bound for a NaN would keep a finite box)
+    best = probs[:, :k].max(dim=1).values.clone()
+    best[top] = -1.0
+    second = int(best.argmax())
+    deltas[second, 4 * ((k - 1) // 2) + 3] = float("nan")
     props = torch.stack([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], dim=1)
     pred = R.apply_deltas(deltas, props, (10.0, 10.0, 5.0, 5.0))
-    assert not bool(torch.isfinite(pred[top]).all()) and int(torch.isfinite(pred).all(dim=1).sum()) == r - 1
+    assert not bool(torch.isfinite(pred[top]).all()) and not bool(torch.isfinite(pred[second]).all())
+    assert int(torch.isfinite(pred).all(dim=1).sum()) == r - 2
     rb, rs, rc, _ = R.fast_rcnn_inference(pred, probs, (newh, neww), 0.3)
-    assert float(rs[0]) < float(probs[top, :k].max())
+    assert float(rs[0]) < float(probs[second, :k].max()) < float(probs[top, :k].max())
     ld = (5 * k + 1 + 3) // 4 * 4                 # the engine's box_pred row (64 at K = 12)
     logits = torch.zeros((1, r, ld))
     logits[0, :, :k + 1] = cls_logits
