@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import _WORKLISTS, ContourSet, MaskOps, PlanePool, reads_words
+from .maskset import _WORKLISTS, ContourSet, MaskOps, Neighbours, PlanePool, _neighbour_buffers, reads_words
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
@@ -446,6 +446,20 @@ class CropMaskSet:
             cs, got = run(int(self.area.sum().item()))
         recs = cs.records(um_pix=um_pix, measure=measure, descriptors=descriptors)
         return recs if extra is None else (recs, list(got))
+
+    def neighbours(self, area=None, group=None, r2: int = -1) -> Neighbours:
+        """``MaskOps.neighbours`` on the words in place (``demia_crop_neighbours``): the same tables, no plane, no wait.  ``area``:
+        the pixel counts on the host; None: the set's own are read with a wait of their own (callers outside the pipeline)."""
+        M, ops = len(self), self.ops
+        H, W = self.hw
+        if area is None:
+            area = self.area.cpu().numpy() if M else np.zeros(0)
+        res, group_d, off_d = _neighbour_buffers(ops, M, area, group)
+        _lib.check(ops.lib.demia_crop_neighbours(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                 _lib.ptr(group_d), M, H, W, int(r2), _lib.ptr(off_d), _lib.ptr(res.points),
+                                                 _lib.ptr(res.nborder), _lib.ptr(res.sums), _lib.ptr(res.table), ops._stream()),
+                   "demia_crop_neighbours")
+        return res
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
         """``MaskOps.gray_histogram`` on the words in place (``demia_crop_gray_histogram``): [M, 256] gray-level counts."""

@@ -1,0 +1,313 @@
+// Neighbour statistics per instance (demia_mask_neighbours / demia_crop_neighbours; definition: include/deepemia_hip.h): the first
+// RELATION between masks -- nearest edge-to-edge gaps and contact counts -- on the mask WORDS, two kernels over a word source
+// (maskwords.h), one workgroup per mask each.
+//
+// mask_border_kernel    the border pixels of every mask as points (y << 16 | x), compacted into points[point_off[m] ..), with the
+//                       border count, the pixel count and the coordinate sums.  A border word is A & ~(up & down & left & right), 32
+//                       pixels per lane-operation; the neighbour words of a word outside the view read 0 and are never fetched.
+// mask_neighbour_kernel for mask a, d2(a, b) over the masks b that can still matter.  gap(a, b), the squared distance of the two
+//                       boxes, never exceeds d2(a, b), so b is evaluated only while gap <= max(best so far, r2, 2) -- in ascending
+//                       (gap, b), which makes `best` shrink after the first few.  A pair whose boxes meet is first asked for a shared
+//                       pixel (mwords::pair_count over the box intersection: d2 = 0); otherwise d2 is the minimum over a's border
+//                       points x b's border points: for disjoint masks the closest pair of pixels is a pair of border pixels.
+//
+// Every decision is an integer comparison and every minimum and sum is order-free, so the result does not depend on which thread
+// saw which word or point.  No f32 / f64, no global atomics, plain vector stores.
+#include "common.h"
+#include "maskwords.h"
+
+namespace {
+
+using mwords::CropWords;
+using mwords::PlaneWords;
+using mwords::View;
+
+// a's border points staged in LDS; the points beyond are read from global memory where the border kernel left them
+constexpr int NB_LDS_POINTS = 8192;
+// candidates (gap, b) kept in LDS once a scan of all masks finds no more than this many that can still matter; while it finds
+// more, every step scans all masks again
+constexpr int NB_CAND_LIST = 256;
+
+constexpr int NB_THREADS = 256;
+constexpr int NB_WAVES = NB_THREADS / 64;
+constexpr long long NB_INF = 0x7fffffffffffffffLL;
+constexpr int NB_IDX_BITS = 24;                      // a candidate's key is gap << 24 | b: gap < 2^34, M <= 2^24
+
+template <class S>
+struct NeighP {
+    S src;
+    const int* bbox;             // [M, 4]
+    const int* group;            // [M] or NULL
+    long M;
+    int H, W;
+    long long r2;
+    const long* point_off;       // [M + 1]
+    uint32_t* points;
+    int* nborder;                // [M]
+    long long* sums;             // [M, 3] N, Sx, Sy
+    long long* table;            // [M, 6]
+};
+
+// Word column wx of row y of the frame as view v stores it: 0 outside the view, never fetched there.
+__device__ __forceinline__ uint32_t word_at(const View v, int y, int wx) {
+    const int ly = y - v.y0, lx = wx - v.c0;
+    if ((unsigned)ly >= (unsigned)v.rows || (unsigned)lx >= (unsigned)v.cols) return 0u;
+    return v.p[(long)ly * v.cols + lx];
+}
+
+// The box of mask m clipped to the frame and to its view: rows y0 .. y1, word columns c0 .. c1 (empty: returns false).
+__device__ __forceinline__ bool clipped_box(const View v, const int4 b, int H, int W, int& y0, int& y1, int& c0, int& c1) {
+    if (b.x < 0 || v.rows == 0) return false;
+    y0 = max(max(b.x, 0), v.y0);
+    y1 = min(min(b.z, H - 1), v.y0 + v.rows - 1);
+    c0 = max(max(b.y, 0) >> 5, v.c0);
+    c1 = min(min(b.w, W - 1) >> 5, v.c0 + v.cols - 1);
+    return y0 <= y1 && c0 <= c1;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
+
+__device__ __forceinline__ long long wave_min(long long v) {
+    for (int s = 32; s > 0; s >>= 1) v = min(v, (long long)__shfl_xor(v, s, 64));
+    return v;
+}
+
+// The minimum of v over the block, in every thread.  s_red: NB_WAVES slots that the previous use's readers have left.
+__device__ __forceinline__ long long block_min(long long v, long long* s_red) {
+    v = wave_min(v);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long r = s_red[0];
+#pragma unroll
+    for (int w = 1; w < NB_WAVES; ++w) r = min(r, s_red[w]);
+    __syncthreads();
+    return r;
+}
+
+template <class S>
+__global__ __launch_bounds__(NB_THREADS) void mask_border_kernel(const NeighP<S> p) {
+    __shared__ int s_count;
+    __shared__ long long s_acc[NB_WAVES][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long m = blockIdx.x;
+    const View v = p.src.view(m);
+    const int4 b = reinterpret_cast<const int4*>(p.bbox)[m];
+    const long off = p.point_off[m];
+    const long cap = p.point_off[m + 1] - off;               // border <= pixels: the host sized it from the pixel counts
+    uint32_t* out = p.points + off;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    long long acc[3] = {0, 0, 0};
+    int y0, y1, c0, c1;
+    if (clipped_box(v, b, p.H, p.W, y0, y1, c0, c1)) {
+        const int rw = c1 - c0 + 1, n = (y1 - y0 + 1) * rw;
+        const int wlast = (p.W - 1) >> 5;
+        const uint32_t tail = (p.W & 31) ? (1u << (p.W & 31)) - 1u : 0xffffffffu;      // columns beyond W - 1 are nobody's pixels
+        for (int i = tid; i < n; i += NB_THREADS) {
+            const int ly = i / rw, y = y0 + ly, wx = c0 + (i - ly * rw);
+            uint32_t a = word_at(v, y, wx);
+            if (wx == wlast) a &= tail;
+            if (!a) continue;
+            const uint32_t up = y > 0 ? word_at(v, y - 1, wx) : 0u, dn = y < p.H - 1 ? word_at(v, y + 1, wx) : 0u;
+            const uint32_t wl = word_at(v, y, wx - 1);
+            uint32_t wr = wx < wlast ? word_at(v, y, wx + 1) : 0u;
+            if (wx + 1 == wlast) wr &= tail;
+            const uint32_t lf = (a << 1) | (wl >> 31), rt = (a >> 1) | (wr << 31);
+            uint32_t bd = a & ~(up & dn & lf & rt);
+            const int na = __popc(a);
+            // sum of the bit positions of a word, by bit of the position
+            const int sx = __popc(a & 0xaaaaaaaau) + 2 * __popc(a & 0xccccccccu) + 4 * __popc(a & 0xf0f0f0f0u) + 8 * __popc(a & 0xff00ff00u) +
+                           16 * __popc(a & 0xffff0000u);
+            acc[0] += na;
+            acc[1] += (long long)na * (32 * wx) + sx;
+            acc[2] += (long long)na * y;
+            if (bd) {
+                int k = atomicAdd(&s_count, __popc(bd));      // LDS; the order inside a mask is unspecified
+                while (bd) {
+                    const int bit = __ffs(bd) - 1;
+                    bd &= bd - 1;
+                    if (k < cap) out[k] = ((uint32_t)y << 16) | (uint32_t)(32 * wx + bit);
+                    ++k;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[j] = wave_sum(acc[j]);
+    if (lane == 0)
+        for (int j = 0; j < 3; ++j) s_acc[wave][j] = acc[j];
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < NB_WAVES; ++w)
+            for (int j = 0; j < 3; ++j) acc[j] += s_acc[w][j];
+        for (int j = 0; j < 3; ++j) p.sums[m * 3 + j] = acc[j];
+        p.nborder[m] = s_count;
+    }
+}
+
+__device__ __forceinline__ long long box_gap(const int4 a, const int4 b) {
+    const long long gy = max(0, max(b.x - a.z, a.x - b.z)), gx = max(0, max(b.y - a.w, a.y - b.w));
+    return gx * gx + gy * gy;
+}
+
+// (d, i) < (best, idx): a candidate that can still take the place of the nearest so far (idx < 0: none yet)
+__device__ __forceinline__ bool beats(long long d, long i, long long best, long idx) { return idx < 0 || d < best || (d == best && i < idx); }
+
+template <class S>
+__global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP<S> p) {
+    __shared__ uint32_t s_pts[NB_LDS_POINTS];
+    __shared__ long long s_list[NB_CAND_LIST];
+    __shared__ long long s_red[NB_WAVES];
+    __shared__ int s_n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long a = blockIdx.x;
+    long long* row = p.table + a * 6;
+    const long long within0 = p.r2 < 0 ? -1 : 0;
+    const long long na_pix = p.sums[a * 3];
+    if (na_pix <= 0) {
+        if (tid == 0) { row[0] = -1; row[1] = -1; row[2] = -1; row[3] = -1; row[4] = 0; row[5] = within0; }
+        return;
+    }
+    const int4 ba = reinterpret_cast<const int4*>(p.bbox)[a];
+    const View va = p.src.view(a);
+    const int ga = p.group ? p.group[a] : 0;
+    const long offa = p.point_off[a];
+    const int na = (int)min((long)p.nborder[a], p.point_off[a + 1] - offa);
+    const uint32_t* pa = p.points + offa;
+    for (int i = tid; i < min(na, NB_LDS_POINTS); i += NB_THREADS) s_pts[i] = pa[i];
+
+    const long long fixed = max(p.r2, 2LL);                 // a pair at most this far apart is counted, whatever the nearest is
+    long long best_any = NB_INF, best_grp = NB_INF;
+    long idx_any = -1, idx_grp = -1;
+    long long touching = 0, within = within0;
+    long long last = -1;                                     // key of the candidate evaluated last: keys ascend strictly
+    bool listed = false;
+    int nlist = 0;
+    const long long idx_mask = (1LL << NB_IDX_BITS) - 1;
+
+    for (;;) {
+        // the smallest key above `last` among the masks that can still matter
+        long long kmin = NB_INF;
+        if (!listed) {
+            if (tid == 0) s_n = 0;
+            __syncthreads();                                 // (first trip: s_pts is written too)
+            for (long b = tid; b < p.M; b += NB_THREADS) {
+                if (b == a || p.sums[b * 3] <= 0) continue;
+                const int4 bb = reinterpret_cast<const int4*>(p.bbox)[b];
+                if (bb.x < 0) continue;
+                const long long gap = box_gap(ba, bb), key = (gap << NB_IDX_BITS) | b;
+                if (key <= last) continue;
+                const bool same = !p.group || p.group[b] == ga;
+                if (!(gap <= fixed || beats(gap, b, best_any, idx_any) || (same && beats(gap, b, best_grp, idx_grp)))) continue;
+                kmin = min(kmin, key);
+                const int slot = atomicAdd(&s_n, 1);         // LDS
+                if (slot < NB_CAND_LIST) s_list[slot] = key;
+            }
+            __syncthreads();
+            nlist = s_n;
+            listed = nlist <= NB_CAND_LIST;                  // the list holds every mask that can matter from here on
+        } else {
+            for (int i = tid; i < nlist; i += NB_THREADS) {
+                const long long key = s_list[i];
+                if (key <= last) continue;
+                const long b = key & idx_mask;
+                const long long gap = key >> NB_IDX_BITS;
+                const bool same = !p.group || p.group[b] == ga;
+                if (gap <= fixed || beats(gap, b, best_any, idx_any) || (same && beats(gap, b, best_grp, idx_grp))) kmin = min(kmin, key);
+            }
+        }
+        kmin = block_min(kmin, s_red);
+        if (kmin == NB_INF) break;
+        last = kmin;
+        const long b = kmin & idx_mask;
+        const bool same = !p.group || p.group[b] == ga;
+        const int4 bb = reinterpret_cast<const int4*>(p.bbox)[b];
+
+        // d2(a, b), exact where it is at most `lim`; a value above `lim` changes nothing below
+        const long long lim = max(fixed, max(idx_any < 0 ? NB_INF : best_any, same ? (idx_grp < 0 ? NB_INF : best_grp) : 0LL));
+        long long d2 = NB_INF;
+        bool shared = false;
+        if ((kmin >> NB_IDX_BITS) == 0) {                    // the boxes meet: a shared pixel?
+            const View vb = p.src.view(b);
+            const long long c = mwords::pair_count<1>(va, ba, vb, bb, tid, NB_THREADS);
+            shared = -block_min(-c, s_red) > 0;
+        }
+        if (shared) d2 = 0;
+        else {
+            const long offb = p.point_off[b];
+            const int nb = (int)min((long)p.nborder[b], p.point_off[b + 1] - offb);
+            const uint32_t* pb = p.points + offb;
+            unsigned long long dmin = ~0ULL;
+            // a wave takes 64 of b's points at a time, one per lane, and hands them round; its lanes share a's points
+            for (int q0 = wave * 64; q0 < nb; q0 += NB_THREADS) {
+                const int cnt = min(64, nb - q0);
+                const uint32_t qv = lane < cnt ? pb[q0 + lane] : 0u;
+                for (int j = 0; j < cnt; ++j) {
+                    const uint32_t q = __shfl(qv, j, 64);
+                    const int qy = q >> 16, qx = q & 0xffff;
+                    // q is at least this far from every pixel of a
+                    const long long ey = max(0, max(ba.x - qy, qy - ba.z)), ex = max(0, max(ba.y - qx, qx - ba.w));
+                    if (ex * ex + ey * ey > lim) continue;
+                    for (int i = lane; i < na; i += 64) {
+                        const uint32_t t = i < NB_LDS_POINTS ? s_pts[i] : pa[i];
+                        // |dx|, |dy| <= 65535: each square fits 32 unsigned bits, their sum does not
+                        const unsigned dy = (unsigned)abs((int)(t >> 16) - qy), dx = (unsigned)abs((int)(t & 0xffff) - qx);
+                        const unsigned long long d = (unsigned long long)(dx * dx) + (unsigned long long)(dy * dy);
+                        dmin = min(dmin, d);
+                    }
+                }
+            }
+            d2 = block_min(dmin > (unsigned long long)NB_INF ? NB_INF : (long long)dmin, s_red);
+        }
+        if (d2 <= 2) ++touching;
+        if (p.r2 >= 0 && d2 <= p.r2) ++within;
+        if (d2 != NB_INF && beats(d2, b, best_any, idx_any)) { best_any = d2; idx_any = b; }
+        if (same && d2 != NB_INF && beats(d2, b, best_grp, idx_grp)) { best_grp = d2; idx_grp = b; }
+    }
+    if (tid == 0) {
+        row[0] = idx_any < 0 ? -1 : best_any; row[1] = idx_any;
+        row[2] = idx_grp < 0 ? -1 : best_grp; row[3] = idx_grp;
+        row[4] = touching; row[5] = within;
+    }
+}
+
+template <class S>
+int launch_neighbours(const NeighP<S>& p, hipStream_t st, const char* name) {
+    hipLaunchKernelGGL(mask_border_kernel<S>, dim3((unsigned)p.M), dim3(NB_THREADS), 0, st, p);
+    DEMIA_CHECK_LAUNCH(name);
+    hipLaunchKernelGGL(mask_neighbour_kernel<S>, dim3((unsigned)p.M), dim3(NB_THREADS), 0, st, p);
+    DEMIA_CHECK_LAUNCH(name);
+    return DEMIA_OK;
+}
+
+}  // namespace
+
+#define NB_REQUIRE_COMMON()                                                                                                   \
+    DEMIA_REQUIRE(M >= 0 && M < (1LL << NB_IDX_BITS) && H > 0 && W > 0 && H <= 65535 && W <= 65535, "shapes");            \
+    if (M == 0) return DEMIA_OK;                                                                                              \
+    DEMIA_REQUIRE(bbox && point_off && points && nborder && sums && table, "args")
+
+extern "C" int demia_mask_neighbours(const uint32_t* masks, const int32_t* bbox, const int32_t* group, int64_t M, int H, int W, int64_t r2,
+                                     const int64_t* point_off, uint32_t* points, int32_t* nborder, int64_t* sums, int64_t* table,
+                                     void* stream) {
+    NB_REQUIRE_COMMON();
+    DEMIA_REQUIRE(masks != nullptr, "args");
+    NeighP<PlaneWords> p{PlaneWords{masks, H, (W + 31) >> 5, nullptr}, bbox, group, (long)M, H, W, (long long)r2,
+                         reinterpret_cast<const long*>(point_off), points, nborder, reinterpret_cast<long long*>(sums),
+                         reinterpret_cast<long long*>(table)};
+    return launch_neighbours(p, (hipStream_t)stream, "mask_neighbour_kernel");
+}
+
+extern "C" int demia_crop_neighbours(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                                     const int32_t* group, int64_t M, int H, int W, int64_t r2, const int64_t* point_off, uint32_t* points,
+                                     int32_t* nborder, int64_t* sums, int64_t* table, void* stream) {
+    NB_REQUIRE_COMMON();
+    DEMIA_REQUIRE(payload && room && offsets, "args");
+    NeighP<CropWords> p{CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, bbox, group, (long)M, H, W, (long long)r2,
+                        reinterpret_cast<const long*>(point_off), points, nborder, reinterpret_cast<long long*>(sums),
+                        reinterpret_cast<long long*>(table)};
+    return launch_neighbours(p, (hipStream_t)stream, "mask_neighbour_kernel<crop>");
+}

@@ -22,7 +22,7 @@ import os
 import threading
 import time
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -32,7 +32,7 @@ from ..data.models import choose_and_use_model, get_trained_model_paths
 from .. import _lib as _L
 from .. import parallel
 from ..cropset import CropMaskAlgebra, CropMaskSet, CropPlanes, crop_contours, crop_gray_histogram, crop_planes, rooms_of_placed_tiles, trace_chunks
-from ..maskset import FAMILIES, MaskOps, families
+from ..maskset import FAMILIES, MaskOps, Neighbours, families
 from ..utils.config import get_config
 from ..utils.logger_utils import log_memory_usage, system_logger
 from ..utils.mask_algebra import DeviceMaskAlgebra
@@ -336,6 +336,81 @@ def descriptors_setting(inf_settings: dict) -> Tuple[str, ...]:
         if value:
             on.append(name)
     return tuple(on)
+
+
+NEIGHBOUR_CSV_HEADER = ["Instance_ID", "Class", "Class_Name", "Pixels", "Centroid x", "Centroid y", "Nearest neighbour", "Nearest distance",
+                        "Nearest same-class neighbour", "Nearest same-class distance", "Touching neighbours", "Neighbours within radius",
+                        "Detected scale bar", "File name"]
+
+
+class NeighbourSetting(NamedTuple):
+    enabled: bool
+    radius: Optional[float]          # in the CSV's length unit (um with a scale bar, else pixels); None: no within count
+
+
+def neighbours_setting(inf_settings: dict) -> NeighbourSetting:
+    """``inference_settings.neighbour_statistics`` (per dataset, default false): ``true`` runs the neighbour stage
+    (``demia_mask_neighbours``) on every image's final instances and writes ``neighbours_results.csv`` -- one row per instance, its
+    nearest neighbours edge to edge and its contacts -- in every mask frame; ``false`` launches, allocates, copies and writes nothing.
+    ``inference_settings.neighbour_radius`` (optional): the radius of the "Neighbours within radius" count, in the CSV's length
+    unit; unset leaves the column empty.  Anything but a bool, and a radius that is not a finite number >= 0, is a configuration
+    error."""
+    value = (inf_settings or {}).get("neighbour_statistics", False)
+    if not isinstance(value, bool):
+        raise ValueError(f"inference_settings.neighbour_statistics must be true or false, got {value!r}")
+    radius = (inf_settings or {}).get("neighbour_radius", None)
+    if radius is not None:
+        if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius < 0:
+            raise ValueError(f"inference_settings.neighbour_radius must be a finite number >= 0, got {radius!r}")
+        radius = float(radius)
+    return NeighbourSetting(value, radius)
+
+
+def neighbour_r2(radius: Optional[float], um_pix: float) -> int:
+    """The squared pixel radius of one image's within count: ``floor((radius / um_pix)^2)``, -1 (not asked for) without a radius."""
+    if radius is None:
+        return -1
+    return int(math.floor((radius / um_pix) ** 2))
+
+
+class NeighbourStage:
+    """The neighbour stage of one image as ``measure_image`` runs it: the caller states the radius, ``rows`` comes back."""
+
+    def __init__(self, radius: Optional[float] = None):
+        self.radius = radius
+        self.rows: List[list] = []
+
+
+def neighbour_rows(image_name: str, classes: Sequence[int], thing_classes, table: np.ndarray, sums: np.ndarray, um_pix: float,
+                   psum: str = "0") -> List[list]:
+    """The rows of ``neighbours_results.csv`` (``NEIGHBOUR_CSV_HEADER``) for one image from the stage's two int64 tables (``table``
+    [M, 6], ``sums`` [M, 3]): one row per instance with a pixel, ``<image>_<k>`` ids as in ``measurements_results.csv`` (k from 1;
+    neighbours are written as their id), centroids ``(Sx / N) * um_pix``, distances ``math.sqrt(d2) * um_pix``, -1 -> empty field."""
+    rows = []
+    for k, cls in enumerate(classes):
+        n, sx, sy = (int(v) for v in sums[k])
+        if n <= 0:
+            continue
+        d_any, i_any, d_grp, i_grp, touching, within = (int(v) for v in table[k])
+        cls = int(cls)
+        cname = thing_classes[cls] if cls < len(thing_classes) else f"class_{cls}"
+        rows.append([f"{image_name}_{k + 1}", cls, cname, n, (sx / n) * um_pix, (sy / n) * um_pix,
+                     None if i_any < 0 else f"{image_name}_{i_any + 1}", None if i_any < 0 else math.sqrt(d_any) * um_pix,
+                     None if i_grp < 0 else f"{image_name}_{i_grp + 1}", None if i_grp < 0 else math.sqrt(d_grp) * um_pix,
+                     touching, None if within < 0 else within, psum, image_name])
+    return rows
+
+
+def write_neighbours(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
+    """``neighbours_results.csv``: the header and every image's rows of ``neighbour_rows``, in the images' order."""
+    path = os.path.join(output_dir, "neighbours_results.csv")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(NEIGHBOUR_CSV_HEADER)
+        for name in image_names:
+            for r in rows_by_image.get(name, []):
+                w.writerow(r)
+    return path
 
 
 DETECTIONS_PER_IMAGE_MAX = 1000
@@ -2152,6 +2227,7 @@ class PipelineSettings:
         self.rank_exchange = rank_exchange_setting(inf)
         self.detections_per_image = detections_per_image_setting(inf)     # (the model loader reads it too: a bad value ends the run here)
         self.descriptors = descriptors_setting(inf)
+        self.neighbours = neighbours_setting(inf)
         # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
         self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
 
@@ -2370,6 +2446,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
 
     rle_by_image: Dict[str, List[str]] = {}       # per image the EncodedPixels texts of its final instances (a16)
     rows_by_image: Dict[str, List[list]] = {}     # per image its measurement rows (a17-a19), measured while the image is still resident
+    neighbour_rows_by_image: Dict[str, List[list]] = {}      # ... and, with neighbour_statistics, its rows of neighbours_results.csv
     keep_masks = os.environ.get("DEEPEMIA_KEEP_MASKS", "0") == "1"
     dedup_results: Dict[str, dict] = {}
     processed = set()
@@ -2500,9 +2577,12 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                 else:
                     crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
                 extra = [crop[0]] if crop is not None else None
+                stage = NeighbourStage(st.neighbours.radius) if st.neighbours.enabled else None
                 rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
                                                     visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes,
-                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors)
+                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors, neighbours=stage)
+                if stage is not None:
+                    neighbour_rows_by_image[name] = stage.rows
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final and pipe.crop:
@@ -2574,13 +2654,15 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                        f"{total / max(len(my_images), 1):.4f}s/image, {pipe.forward_calls} batched forwards")
     if shard_images:
         # the ONE exchange of the image-sharded job: every rank's rows and texts go to rank 0, which writes the files
-        mine = (rle_by_image, rows_by_image, {k: {kk: vv for kk, vv in v.items() if kk != "masks"} for k, v in dedup_results.items()}, sorted(processed))
+        mine = (rle_by_image, (rows_by_image, neighbour_rows_by_image),
+                {k: {kk: vv for kk, vv in v.items() if kk != "masks"} for k, v in dedup_results.items()}, sorted(processed))
         gathered = [None] * job_world
         dist.all_gather_object(gathered, mine)         # (an all-gather: the object collective every backend, RCCL included, supports)
         if job_rank == 0:
-            for r_rle, r_rows, r_res, r_done in gathered[1:]:
+            for r_rle, (r_rows, r_nrows), r_res, r_done in gathered[1:]:
                 rle_by_image.update(r_rle)
                 rows_by_image.update(r_rows)
+                neighbour_rows_by_image.update(r_nrows)
                 for k, v in r_res.items():
                     dedup_results.setdefault(k, dict(v, masks=None))
                 processed.update(r_done)
@@ -2598,7 +2680,10 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     wri.writerow([name.rsplit(".", 1)[0], text])
 
         write_measurements(pipe.ops, dedup_results, inpath, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                           rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, descriptors=st.descriptors)
+                           rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, descriptors=st.descriptors,
+                           neighbours=st.neighbours, neighbour_rows_by_image=neighbour_rows_by_image)
+        if st.neighbours.enabled:
+            write_neighbours(output_dir, images_name, neighbour_rows_by_image)
         with open(os.path.join(output_dir, "class_color_legend.txt"), "w") as f:
             f.write("Class Color Legend (BGR)\n")
             for i, cname in enumerate(metadata.thing_classes):
@@ -2733,9 +2818,12 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
                   extra: Optional[list] = None, note_planes=None, crop_direct: bool = False,
-                  descriptors: Sequence[str] = ()) -> List[list]:
+                  descriptors: Sequence[str] = (), neighbours: Optional[NeighbourStage] = None) -> List[list]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
     mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
+    ``neighbours``: the neighbour stage (``neighbours_setting``) runs on the same final set with the scale detected here; it is
+    enqueued before the trace's fetch and its two tables ride in that fetch's copy, so it adds no wait; its rows of
+    ``neighbours_results.csv`` come back in ``neighbours.rows``.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
     the file here, which gives the same bytes).  ``crop_direct``: a crop-framed set is traced, measured and histogrammed on its
     words in place (``mask_frame: crop_direct``) instead of through the plane pool.  ``descriptors``: the contour records, and
@@ -2763,6 +2851,8 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     else:
         psum, um_pix = detect_scale_bar(im, roi_config=None, dataset_name=dataset_name)
     packed, classes = data["masks"], data["classes"]
+    if neighbours is not None:
+        neighbours.rows = []
     if packed is None or packed.shape[0] == 0:
         return []
     h, wd = data["hw"]
@@ -2772,32 +2862,45 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     direct = crop and crop_direct
     if note_planes is not None and not direct:
         note_planes(crop_planes(ops, (h, wd)).cap if crop else 2 * int(packed.shape[0]))      # (the masks + the trace's scratch planes)
+    bbox_dev = None
+    if not crop and data.get("bbox") is not None:
+        bbox_dev = ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32))
+    # ``ride``: the int32 device tensors that come to the host in the trace's own copy -- the caller's ``extra`` (the cropped words of
+    # the RLE texts; replaced in place by their host arrays) and, behind them, the two tables of the neighbour stage
+    ride = extra
+    if neighbours is not None:
+        group = np.asarray(classes, dtype=np.int32)
+        r2 = neighbour_r2(neighbours.radius, um_pix)
+        if crop:
+            nb = packed.neighbours(area=data.get("area"), group=group, r2=r2)
+        else:
+            nb = ops.neighbours(packed, bbox_dev, data.get("area") if bbox_dev is not None else None, group=group, r2=r2)
+        ride = list(extra or []) + [nb.table_i32, nb.sums_i32]
     if direct:
         # a crop-framed set traced and measured on its words in place: one trace, one fetch, no plane
         area_h = data.get("area")
-        recs = packed.contours(max_contours=256, um_pix=um_pix, total_area=None if area_h is None else int(np.sum(area_h)), extra=extra,
+        recs = packed.contours(max_contours=256, um_pix=um_pix, total_area=None if area_h is None else int(np.sum(area_h)), extra=ride,
                                descriptors=descriptors)
-        if extra is not None:
-            recs, extra_host = recs
-            extra[:] = extra_host
+        if ride is not None:
+            recs, ride_host = recs
     elif crop:
         # a crop-framed set: the same trace + measurements, a chunk of the plane pool at a time
-        recs, extra_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=extra,
-                                         descriptors=descriptors)
-        if extra is not None:
-            extra[:] = extra_host
-    elif data.get("bbox") is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
-        # (``extra``: a list of int32 device tensors the image loop wants on the host in the same copy -- the cropped words of the RLE
-        # texts --; replaced in place by their host arrays)
-        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, bbox=ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32)),
-                            total_area=int(np.sum(data["area"])), extra=extra, descriptors=descriptors)
-        if extra is not None:
-            recs, extra_host = recs
-            extra[:] = extra_host
+        recs, ride_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=ride,
+                                        descriptors=descriptors)
+    elif bbox_dev is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
+        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, bbox=bbox_dev, total_area=int(np.sum(data["area"])), extra=ride,
+                            descriptors=descriptors)
+        if ride is not None:
+            recs, ride_host = recs
     else:
         recs = ops.contours(packed, max_contours=256, um_pix=um_pix, descriptors=descriptors)
-        if extra is not None:
-            extra[:] = [e.cpu().numpy() for e in extra]
+        if ride is not None:
+            ride_host = [e.cpu().numpy() for e in ride]
+    if extra is not None:
+        extra[:] = ride_host[:len(extra)]
+    if neighbours is not None:
+        table, sums = Neighbours.from_i32(ride_host[-2], ride_host[-1])
+        neighbours.rows = neighbour_rows(test_img, classes, metadata.thing_classes, table, sums, um_pix, psum)
     contrast = [(None, None, None)] * int(packed.shape[0])
     if measure_contrast:
         # measurements.py:195-215: gray levels under the whole instance mask; the histogram is a device reduction
@@ -2817,12 +2920,14 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
 def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_path: str, output_dir: str, metadata,
                        dataset_name: str, draw_scalebar: bool = False, visualize: bool = False,
                        rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False,
-                       descriptors: Sequence[str] = ()) -> str:
+                       descriptors: Sequence[str] = (), neighbours: Optional[NeighbourSetting] = None,
+                       neighbour_rows_by_image: Optional[Dict[str, List[list]]] = None) -> str:
     """Measurement phase (``inference.py:983-1291``): one CSV row per external contour that passes
     the area gate, 20 columns, ``None`` -> empty field, floats through ``csv.writer``.  ``rows_by_image``: rows the image
     loop (or another rank, when images are sharded over ranks) has already measured; images without an entry are measured here.
     ``descriptors``: each requested family of ``DESCRIPTOR_CSV`` appends its columns behind "File name", in table order (rows
-    measured elsewhere come with them)."""
+    measured elsewhere come with them).  ``neighbours`` enabled: an image measured here also runs the neighbour stage, as the image
+    loop does, and files its rows of ``neighbours_results.csv`` in ``neighbour_rows_by_image``."""
     csv_filename = os.path.join(output_dir, "measurements_results.csv")
     with open(csv_filename, "w", newline="") as csvfile:
         w = csv.writer(csvfile)
@@ -2834,8 +2939,11 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
             if rows_by_image is not None and test_img in rows_by_image:
                 rows = rows_by_image[test_img]
             else:
+                stage = NeighbourStage(neighbours.radius) if (neighbours is not None and neighbours.enabled) else None
                 rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                                     crop_direct=crop_direct, descriptors=descriptors)
+                                     crop_direct=crop_direct, descriptors=descriptors, neighbours=stage)
+                if stage is not None and neighbour_rows_by_image is not None:
+                    neighbour_rows_by_image[test_img] = stage.rows
             for r in rows:
                 w.writerow(r)
             csvfile.flush()

@@ -124,6 +124,57 @@ class Launched:
     host: Optional[np.ndarray] = None        # [M, max contours per mask, cols] view of fetch()'s copy; None when it fell back
 
 
+def neighbour_offsets(area) -> np.ndarray:
+    """``point_off`` [M + 1] i64 of ``demia_mask_neighbours``: the exclusive prefix sum of the masks' pixel counts on the host (a
+    mask has no more border pixels than pixels), so the border points need no count-then-allocate wait."""
+    a = np.maximum(np.asarray(area, dtype=np.int64).reshape(-1), 0)
+    off = np.zeros(len(a) + 1, dtype=np.int64)
+    np.cumsum(a, out=off[1:])
+    return off
+
+
+@dataclass
+class Neighbours:
+    """What ``MaskOps.neighbours`` / ``CropMaskSet.neighbours`` enqueued (``demia_mask_neighbours``), all on the device."""
+    table: torch.Tensor          # [M, 6] int64: d2_any, idx_any, d2_group, idx_group, touching, within
+    sums: torch.Tensor           # [M, 3] int64: N, Sx, Sy
+    nborder: torch.Tensor        # [M] int32
+    points: torch.Tensor         # int32 words: mask m's border pixels (y << 16 | x) from point_off[m]
+    point_off: np.ndarray        # [M + 1] int64, on the host
+
+    # int32 views of the two tables: what rides in ContourSet.fetch(extra=...)
+    @property
+    def table_i32(self) -> torch.Tensor:
+        return self.table.view(torch.int32)
+
+    @property
+    def sums_i32(self) -> torch.Tensor:
+        return self.sums.view(torch.int32)
+
+    @staticmethod
+    def from_i32(table_i32: np.ndarray, sums_i32: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """The host copies of :attr:`table_i32` / :attr:`sums_i32` as the int64 tables ``[M, 6]`` / ``[M, 3]``."""
+        t = np.ascontiguousarray(table_i32, dtype=np.int32).reshape(-1).view(np.int64).reshape(-1, 6)
+        s = np.ascontiguousarray(sums_i32, dtype=np.int32).reshape(-1).view(np.int64).reshape(-1, 3)
+        return t, s
+
+
+def _neighbour_buffers(ops: "MaskOps", M: int, area, group) -> Tuple[Neighbours, Optional[torch.Tensor], torch.Tensor]:
+    """The outputs of one neighbour stage and its two host tables on the device, in ONE upload: (result, group or None, point_off)."""
+    off = neighbour_offsets(area)
+    assert len(off) == M + 1
+    dev = ops.device
+    res = Neighbours(torch.empty((M, 6), dtype=torch.int64, device=dev), torch.empty((M, 3), dtype=torch.int64, device=dev),
+                     torch.empty((M,), dtype=torch.int32, device=dev), torch.empty((max(int(off[-1]), 1),), dtype=torch.int32, device=dev), off)
+    parts = [off.view(np.int32)]
+    if group is not None:
+        g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        assert len(g) == M
+        parts.append(g)
+    tab = ops.upload(np.concatenate(parts))
+    return res, (tab[2 * (M + 1):] if group is not None else None), tab[:2 * (M + 1)].view(torch.int64)
+
+
 class PlanePool:
     """Mask planes that stay ZERO outside per-slot boxes (``demia_mask_gather_regions_pooled``): a gather into the pool
     writes the union of a slot's previous box and its new one instead of whole 512-KiB planes.  The planes handed out are
@@ -459,6 +510,23 @@ class MaskOps:
         got = cs.fetch(extra=extra, with_points=True)
         recs = cs.records(um_pix=um_pix, measure=measure, descriptors=descriptors)
         return recs if extra is None else (recs, list(got))
+
+    def neighbours(self, packed: torch.Tensor, bbox: Optional[torch.Tensor], area, group=None, r2: int = -1) -> Neighbours:
+        """Nearest edge-to-edge gaps and contact counts between the masks of ``packed`` (``demia_mask_neighbours``; the definition
+        is in ``include/deepemia_hip.h``): both kernels are enqueued without a wait and the device tensors returned.  ``bbox``: any
+        superset of the tight boxes; ``area``: the pixel counts on the HOST (they size the border points); ``group``: a host array
+        of a label per mask, the nearest neighbour is also reported among the masks of the same label (None: one group);
+        ``r2``: squared radius of the within count, < 0: not asked for.  With ``area`` (or ``bbox``) None, ``area_bbox`` is read
+        with a wait of its own -- for callers outside the pipeline."""
+        M, H, wpr = packed.shape
+        if M and (area is None or bbox is None):
+            a, bbox = self.area_bbox(packed, bbox)
+            area = a.cpu().numpy()
+        res, group_d, off_d = _neighbour_buffers(self, M, area if M else np.zeros(0), group)
+        _lib.check(self.lib.demia_mask_neighbours(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(group_d), M, H, self._w(packed), int(r2),
+                                                  _lib.ptr(off_d), _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums),
+                                                  _lib.ptr(res.table), self._stream()), "demia_mask_neighbours")
+        return res
 
     def skeleton(self, packed: torch.Tensor, bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The morphological skeleton (Guo-Hall thinning; ``demia_mask_skeleton`` in its thin-only form) of every mask, as packed

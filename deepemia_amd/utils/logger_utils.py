@@ -17,7 +17,9 @@ def get_log_dir() -> Path:
     base = Path(os.environ.get("DEEPEMIA_LOG_DIR", str(Path.home() / "logs")))
     try:
         base.mkdir(parents=True, exist_ok=True)
-        probe = base / ".w"
+        # (a name of this process's own: two ranks that start together would otherwise unlink each other's probe, and the loser
+        # of that race logged into the fallback directory)
+        probe = base / f".w{os.getpid()}"
         probe.touch()
         probe.unlink()
     except OSError:

@@ -621,6 +621,41 @@ int demia_crop_skeleton(const int32_t* select /* [M] or NULL */, const uint32_t*
                         double* out /* [M, out_c, 8] */, int out_c, uint32_t* scratch, const int64_t* scratch_off, uint32_t* scratch2,
                         const int64_t* scratch2_off, uint32_t* skel_out, void* stream);
 
+/* demia_mask_neighbours / demia_crop_neighbours = nearest edge-to-edge gaps and contact counts BETWEEN the masks of one frame (not
+ * in the reference program; opt-in: inference_settings.neighbour_statistics).  Not a value per contour of one mask but a relation
+ * between masks, one row per mask.  Frame H x W, H, W <= 65535; M < 2^24 masks.
+ *   P(m)   the set pixels of mask m;  N(m) = |P(m)|;  Sx, Sy = the sums of x and of y over P(m), int64.
+ *   d2(a, b) = min over p in P(a), q in P(b) of (px - qx)^2 + (py - qy)^2, int64, between pixel centres: 0 when the masks share a
+ *          pixel (a mask contained in another shares), 1 for 4-adjacent pixels, 2 for diagonal ones; a mask nested in another's
+ *          HOLE is disjoint from it and has a positive distance.
+ *   nearest neighbour of a   the b != a with N(b) > 0 that minimises (d2(a, b), b) lexicographically: the lower index wins a tie;
+ *   nearest in the same group   the same over the b with group[b] == group[a] (group == NULL: every mask is in one group);
+ *   touching   the number of b != a, N(b) > 0, with d2(a, b) <= 2 (overlapping or 8-adjacent);
+ *   within     the number of b != a, N(b) > 0, with d2(a, b) <= r2;  r2 < 0: not asked for, the value is -1.
+ *   table [M, 6] i64 = d2_any, idx_any, d2_group, idx_group, touching, within; d2 and idx are -1 where no such b exists.  A mask with
+ *       N = 0 has no distances and is nobody's neighbour: -1, -1, -1, -1, 0, within (0, or -1 for r2 < 0).
+ *   sums [M, 3] i64 = N, Sx, Sy;  nborder [M] i32 = the number of border pixels of m.
+ *   points   the border pixels of mask m as (y << 16) | x in points[point_off[m] .. point_off[m] + nborder[m]), in no stated order.  A
+ *       border pixel is a set pixel with an unset 4-neighbour, positions outside the frame counting as unset (a harmless
+ *       superset of the pixels that face another mask): for disjoint masks the minimum over border pixels is the minimum over all.
+ *   point_off [M + 1] i64, made by the host: the exclusive prefix sum of upper bounds of the border counts (the pixel counts
+ *       serve: border <= pixels), so nothing is counted first and nothing overflows; a mask whose border exceeds its share is cut
+ *       to it.  Nothing outside points[0 .. point_off[M]), nborder, sums and table is written.
+ * bbox may be any superset of the tight box that is zero outside it (crops: inside the room); a word outside a mask's view is zero
+ * and is never fetched; bits beyond column W - 1 are masked off.  Two kernels, one workgroup per mask each: the borders, then per
+ * mask a the masks b in ascending (box gap, b) while the gap -- a lower bound of d2 -- is at most max(nearest so far, r2, 2); a pair
+ * whose boxes meet is first asked for a shared pixel over the box intersection.  a's border points are staged in LDS up to 8192
+ * and read from `points` beyond; the candidates are listed in LDS once at most 256 remain.  Integer comparisons only, no f32 or
+ * f64 on the device, plain vector stores; the result does not depend on alignment, position, launch layout or the frame form.
+ * M == 0: DEMIA_OK without a launch.  No allocation, one stream, capturable. */
+int demia_mask_neighbours(const uint32_t* masks, const int32_t* bbox, const int32_t* group /* [M] or NULL */, int64_t M, int H, int W,
+                          int64_t r2, const int64_t* point_off /* [M + 1] */, uint32_t* points, int32_t* nborder /* [M] */,
+                          int64_t* sums /* [M, 3] */, int64_t* table /* [M, 6] */, void* stream);
+int demia_crop_neighbours(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                          const int32_t* group /* [M] or NULL */, int64_t M, int H, int W, int64_t r2,
+                          const int64_t* point_off /* [M + 1] */, uint32_t* points, int32_t* nborder /* [M] */,
+                          int64_t* sums /* [M, 3] */, int64_t* table /* [M, 6] */, void* stream);
+
 /* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
  * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
  *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at

@@ -5,7 +5,9 @@ process, the frames alternating (full, crop, full, crop, ...; the fourth argumen
 full,crop,crop_direct), same models, same image, same box.  A frame written as ``<frame>+shape`` runs with
 `inference_settings.shape_descriptors: true` (e.g. crop_direct,crop_direct+shape: the setting off and on, alternating), one written
 as ``<frame>+inscribed`` with `inference_settings.inscribed_descriptors: true`, one written as ``<frame>+skeleton`` with
-`inference_settings.skeleton_descriptors: true` -- any family of `maskset.FAMILIES`; several suffixes may follow one frame.
+`inference_settings.skeleton_descriptors: true` -- any family of `maskset.FAMILIES`; several suffixes may follow one frame.  The suffix
+``+neighbours`` runs with `inference_settings.neighbour_statistics: true` (the neighbour stage of `measure_image`; a radius of 50
+pixels): its rows are counted and digested apart (`neighbour_rows`, `neighbour_rows_sha256`).
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
@@ -58,7 +60,9 @@ pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"
 spatial_cfg = load_spatial_constraints(T.DATASET)
 metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
 pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f.split("+")[0]), st.global_config) for f in frames}
-descriptors = {f: tuple(fam.name for fam in families(f.split("+")[1:])) for f in frames}      # (an unknown suffix: ValueError)
+descriptors = {f: tuple(fam.name for fam in families([x for x in f.split("+")[1:] if x != "neighbours"])) for f in frames}      # (an unknown suffix: ValueError)
+neighbours = {f: "neighbours" in f.split("+")[1:] for f in frames}
+NEIGHBOUR_RADIUS = 50.0
 host_copies = [0]
 for _name in ("cpu", "item"):
     def _counted(self, *a, _orig=getattr(torch.Tensor, _name), **k):
@@ -75,8 +79,8 @@ small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes(
 pipes[frames[0]].drop_cached("big.tif")
 
 
-def one_image(pipe, descriptors=()):
-    """process_image of run_inference for this image: instances, RLE texts, measurement rows."""
+def one_image(pipe, descriptors=(), with_neighbours=False):
+    """process_image of run_inference for this image: instances, RLE texts, measurement rows (and the neighbour rows)."""
     name = "big.tif"
     pipe.begin_image_stats()
     packed, scores, classes, tabs = I.final_instances(pipe, st, name, image_dev, small, len(T.CLASSES), spatial_cfg, I.image_phases_enabled(pipe))
@@ -88,22 +92,26 @@ def one_image(pipe, descriptors=()):
     else:
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
+    stage = I.NeighbourStage(NEIGHBOUR_RADIUS) if with_neighbours else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors, neighbours=stage)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
+    if with_neighbours and pipe.crop:      # (a crop-framed set is a few MiB: keeping it does not move the next repetition's peak)
+        last_set[pipe.mask_frame] = (pipe, packed, classes, tabs)
     pipe.drop_cached(name)
-    return n, rows, texts, pipe.end_image_stats((size, size))
+    return n, rows, texts, pipe.end_image_stats((size, size)), (stage.rows if stage is not None else None)
 
 
+last_set = {}                        # crop frame -> the final set of the last image measured with +neighbours
 runs = {f: [] for f in pipes}
-digest, digest_all = {}, {}          # per frame: texts + the 20 reference columns; ALL columns of the rows
+digest, digest_all, digest_nb = {}, {}, {}          # per frame: texts + the 20 reference columns; ALL columns of the rows; the neighbour rows
 for rep in range(reps):
     for frame, pipe in pipes.items():                    # alternating: full, crop, full, crop, ... (the order of `frames`)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         w0, c0, f0 = pipe.d2h_waits, host_copies[0], fallbacks[0]
         t0 = time.perf_counter()
-        n, rows, texts, stats = one_image(pipe, descriptors[frame])
+        n, rows, texts, stats, nrows = one_image(pipe, descriptors[frame], neighbours[frame])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert all(len(r) == 20 + sum(len(I.DESCRIPTOR_CSV[name][0]) for name in descriptors[frame]) for r in rows)
@@ -111,15 +119,17 @@ for rep in range(reps):
         h_all = hashlib.sha256(repr(rows).encode()).hexdigest()
         digest.setdefault(frame, h)
         digest_all.setdefault(frame, h_all)
-        assert digest[frame] == h and digest_all[frame] == h_all, "a repetition wrote other rows"
+        h_nb = None if nrows is None else hashlib.sha256(repr(nrows).encode()).hexdigest()
+        digest_nb.setdefault(frame, h_nb)
+        assert digest[frame] == h and digest_all[frame] == h_all and digest_nb[frame] == h_nb, "a repetition wrote other rows"
         runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0,
                                 host_copies=host_copies[0] - c0, fetch_fallbacks=fallbacks[0] - f0, instances=n,
-                                rows=len(rows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
+                                rows=len(rows), neighbour_rows=None if nrows is None else len(nrows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
         print(f"rep {rep} {frame:11s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
               f"{pipe.d2h_waits - w0} waits, {host_copies[0] - c0} device-to-host copies ({fallbacks[0] - f0} fetch fallbacks), {stats['full_frame_planes_peak']} planes", flush=True)
 
 res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating " + ", ".join(frames),
-       "same_rows_and_texts": len(set(digest.values())) == 1, "device": torch.cuda.get_device_name(0), "frames": {}}
+       "same_rows_and_texts": len(set(digest.values())) == 1, "same_neighbour_rows": len({v for v in digest_nb.values() if v is not None}) <= 1, "device": torch.cuda.get_device_name(0), "frames": {}}
 for frame, rr in runs.items():
     steady = [r["seconds"] for r in rr[1:]]
     res["frames"][frame] = dict(first_image_seconds=rr[0]["seconds"], steady_seconds=steady,
@@ -128,7 +138,43 @@ for frame, rr in runs.items():
                                 peak_bytes_first=rr[0]["peak_bytes"], peak_bytes_steady=max(r["peak_bytes"] for r in rr[1:]) if steady else None,
                                 d2h_waits_per_image=rr[-1]["d2h_waits"], host_copies_per_image=rr[-1]["host_copies"], fetch_fallbacks_per_image=rr[-1]["fetch_fallbacks"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
                                 rows20_texts_sha256=digest[frame], rows_sha256=digest_all[frame],
+                                neighbour_rows=rr[-1]["neighbour_rows"], neighbour_rows_sha256=digest_nb[frame],
                                 full_frame_planes_peak=max(r["full_frame_planes_peak"] for r in rr))
+
+
+def stage_alone(frame):
+    """The neighbour stage by itself on the last final set of ``frame``: device time of its two launches (events, 5 runs, the
+    median), for all masks and with the masks of the longest borders left out -- a launch that ends on one slow mask gets much
+    shorter without it."""
+    pipe, packed, classes, tabs = last_set[frame]
+    area, group = np.asarray(tabs[0]), np.asarray(classes, dtype=np.int32)
+    r2 = I.neighbour_r2(NEIGHBOUR_RADIUS, 1.0)
+
+    def timed(keep):
+        sub = packed if keep is None else packed.select(keep)
+        call = lambda: sub.neighbours(area=area if keep is None else area[keep], group=group if keep is None else group[keep], r2=r2)
+        ms = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            nb = call()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), nb
+    t_all, nb = timed(None)
+    nborder = nb.nborder.cpu().numpy().astype(np.int64)
+    order = np.argsort(-nborder, kind="stable")
+    out = dict(masks=int(len(nborder)), device_ms_all=t_all, border_points=int(nborder.sum()), border_points_max=int(nborder.max()),
+               border_points_median=float(np.median(nborder)), border_points_above_lds_limit=int((nborder > 8192).sum()))
+    for drop in (1, 8):
+        out[f"device_ms_without_{drop}_longest"] = timed(np.sort(order[drop:]))[0]
+    return out
+
+
+if last_set:
+    res["neighbour_stage_alone"] = {f: stage_alone(f) for f in last_set}
 out_path.parent.mkdir(parents=True, exist_ok=True)
 out_path.write_text(json.dumps(res, indent=1))
 print(json.dumps(res))
