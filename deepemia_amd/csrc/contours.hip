@@ -17,8 +17,7 @@
 // which is where OpenCV's raster scan starts the same border; valid traces are walked again to emit their points.
 // Measurements: one wave per contour (rank sort + Jacobi least squares over the lanes).
 // Compiled with -ffp-contract=off: the f32 calipers follow OpenCV's operation order.
-#include "common.h"
-#include "maskregion.h"
+#include "wordregion.h"
 
 namespace {
 
@@ -188,7 +187,7 @@ __device__ void walk_segment(const BitImg& im, const uint32_t* startmap, Walkers
 // convolution's workgroups on the other stream) and a large one; a small-region mask with too many candidates is
 // handed on through count[m] = -1.
 constexpr int TRACE_WORDS_SMALL = 1024, CAND_SMALL = 512;
-constexpr int TRACE_WORDS = 8192, CAND_MAX = 3072;
+constexpr int TRACE_WORDS = wreg::LARGE_WORDS, CAND_MAX = 3072;      // the word-region kernels stage by the same buffer
 
 struct ContourP {
     static constexpr bool ROOM = false;
@@ -1238,20 +1237,9 @@ extern "C" int demia_mask_contours_wl(const uint32_t* masks, uint32_t* scratch, 
     return launch_contour_trace(p, worklist, (hipStream_t)stream);
 }
 
-// Words of scratch a crop-framed trace needs, from the host's room table alone: a mask whose ROOM's region (+ 1 ring, clipped
-// to the frame: an upper bound of the region of its tight box) exceeds the large LDS buffer gets two padded region buffers.
+// Words of scratch a crop-framed trace needs: two padded region buffers per large room.
 extern "C" int64_t demia_crop_contour_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch_off) {
-    int64_t total = 0;
-    for (int64_t m = 0; m < M; ++m) {
-        const int32_t* r = room_host + 4 * m;
-        scratch_off[m] = total;
-        if (r[0] < 0) continue;
-        int ry0, wx0, rh, rw;
-        mreg::region_of(r[0], r[1], r[2], r[3], 1, H, W, ry0, wx0, rh, rw);
-        const int64_t pn = (int64_t)(rh + 2) * (rw + 2);
-        if (pn > TRACE_WORDS) total += 2 * pn;
-    }
-    return total;
+    return wreg::room_scratch_words(room_host, M, H, W, 2, scratch_off);
 }
 
 extern "C" int demia_crop_contours_wl(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox, int M, int H,

@@ -1,4 +1,5 @@
-// Per-mask REGION machinery shared by the packed-mask kernels (maskops.hip, contours.hip).
+// Per-mask REGION machinery shared by the packed-mask kernels (maskops.hip, contours.hip; wordregion.h builds the stage of the
+// kernels that measure on the mask words -- inscribed.hip, skeleton.hip -- on region_of and flood).
 //
 // An instance mask of a 2048 x 2048 tile is a 512 KiB bit plane, but its set pixels live in a bounding box that is
 // typically ~70 rows x 3 words.  Every per-mask stage therefore works on the bbox region only (+ a margin for

@@ -1,6 +1,6 @@
 // Where the packed words of a mask live, as a type: the kernels that only READ masks (maskops.hip: pair counts, gray
-// histogram, pooled gather; evaluate.hip: cross matrix, run lengths) are written once over a word SOURCE and instantiated for
-// both layouts,
+// histogram, pooled gather; evaluate.hip: cross matrix, run lengths; wordregion.h and its kernels; neighbours.hip) are written
+// once over a word SOURCE and instantiated for both layouts,
 //
 //   PlaneWords   full-frame planes [M, H, wpr]
 //   CropWords    crop-framed sets (cropops.hip: room, offsets, payload)
@@ -42,6 +42,25 @@ __device__ __forceinline__ uint32_t pixel(const View v, int y, int x) {
     const int ly = y - v.y0, lx = (x >> 5) - v.c0;
     if (ly < 0 || ly >= v.rows || lx < 0 || lx >= v.cols) return 0u;
     return (v.p[(long)ly * v.cols + lx] >> (x & 31)) & 1u;
+}
+
+// The word-granular sibling of pixel(): word column wx of row y of the frame as view v stores it, 0 outside the view and never
+// fetched there.
+__device__ __forceinline__ uint32_t word_at(const View v, int y, int wx) {
+    const int ly = y - v.y0, lx = wx - v.c0;
+    if ((unsigned)ly >= (unsigned)v.rows || (unsigned)lx >= (unsigned)v.cols) return 0u;
+    return v.p[(long)ly * v.cols + lx];
+}
+
+// The box b of a mask clipped to the frame and to its view v: rows y0 .. y1, word columns c0 .. c1 (empty: returns false) -- for
+// one mask what pair_count's window is for two.
+__device__ __forceinline__ bool clipped_box(const View v, const int4 b, int H, int W, int& y0, int& y1, int& c0, int& c1) {
+    if (b.x < 0 || v.rows == 0) return false;
+    y0 = max(max(b.x, 0), v.y0);
+    y1 = min(min(b.z, H - 1), v.y0 + v.rows - 1);
+    c0 = max(max(b.y, 0) >> 5, v.c0);
+    c1 = min(min(b.w, W - 1) >> 5, v.c0 + v.cols - 1);
+    return y0 <= y1 && c0 <= c1;
 }
 
 // popcount(a & b) over the intersection of two tight boxes (y0, x0, y1, x1), each operand addressed with its own view's

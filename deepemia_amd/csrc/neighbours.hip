@@ -1,6 +1,7 @@
 // Neighbour statistics per instance (demia_mask_neighbours / demia_crop_neighbours; definition: include/deepemia_hip.h): the first
 // RELATION between masks -- nearest edge-to-edge gaps and contact counts -- on the mask WORDS, two kernels over a word source
-// (maskwords.h), one workgroup per mask each.
+// (maskwords.h: views, word_at, clipped_box, pair_count), one workgroup per mask each; the block reductions and the launch are
+// those of wordregion.h.
 //
 // mask_border_kernel    the border pixels of every mask as points (y << 16 | x), compacted into points[point_off[m] ..), with the
 //                       border count, the pixel count and the coordinate sums.  A border word is A & ~(up & down & left & right), 32
@@ -13,8 +14,7 @@
 //
 // Every decision is an integer comparison and every minimum and sum is order-free, so the result does not depend on which thread
 // saw which word or point.  No f32 / f64, no global atomics, plain vector stores.
-#include "common.h"
-#include "maskwords.h"
+#include "wordregion.h"
 
 namespace {
 
@@ -28,8 +28,7 @@ constexpr int NB_LDS_POINTS = 8192;
 // more, every step scans all masks again
 constexpr int NB_CAND_LIST = 256;
 
-constexpr int NB_THREADS = 256;
-constexpr int NB_WAVES = NB_THREADS / 64;
+constexpr int NB_THREADS = wreg::THREADS, NB_WAVES = wreg::WAVES;
 constexpr long long NB_INF = 0x7fffffffffffffffLL;
 constexpr int NB_IDX_BITS = 24;                      // a candidate's key is gap << 24 | b: gap < 2^34, M <= 2^24
 
@@ -48,50 +47,11 @@ struct NeighP {
     long long* table;            // [M, 6]
 };
 
-// Word column wx of row y of the frame as view v stores it: 0 outside the view, never fetched there.
-__device__ __forceinline__ uint32_t word_at(const View v, int y, int wx) {
-    const int ly = y - v.y0, lx = wx - v.c0;
-    if ((unsigned)ly >= (unsigned)v.rows || (unsigned)lx >= (unsigned)v.cols) return 0u;
-    return v.p[(long)ly * v.cols + lx];
-}
-
-// The box of mask m clipped to the frame and to its view: rows y0 .. y1, word columns c0 .. c1 (empty: returns false).
-__device__ __forceinline__ bool clipped_box(const View v, const int4 b, int H, int W, int& y0, int& y1, int& c0, int& c1) {
-    if (b.x < 0 || v.rows == 0) return false;
-    y0 = max(max(b.x, 0), v.y0);
-    y1 = min(min(b.z, H - 1), v.y0 + v.rows - 1);
-    c0 = max(max(b.y, 0) >> 5, v.c0);
-    c1 = min(min(b.w, W - 1) >> 5, v.c0 + v.cols - 1);
-    return y0 <= y1 && c0 <= c1;
-}
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
-__device__ __forceinline__ long long wave_min(long long v) {
-    for (int s = 32; s > 0; s >>= 1) v = min(v, (long long)__shfl_xor(v, s, 64));
-    return v;
-}
-
-// The minimum of v over the block, in every thread.  s_red: NB_WAVES slots that the previous use's readers have left.
-__device__ __forceinline__ long long block_min(long long v, long long* s_red) {
-    v = wave_min(v);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = s_red[0];
-#pragma unroll
-    for (int w = 1; w < NB_WAVES; ++w) r = min(r, s_red[w]);
-    __syncthreads();
-    return r;
-}
-
 template <class S>
 __global__ __launch_bounds__(NB_THREADS) void mask_border_kernel(const NeighP<S> p) {
     __shared__ int s_count;
-    __shared__ long long s_acc[NB_WAVES][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ long long s_red[NB_WAVES * 3];
+    const int tid = threadIdx.x;
     const long m = blockIdx.x;
     const View v = p.src.view(m);
     const int4 b = reinterpret_cast<const int4*>(p.bbox)[m];
@@ -102,18 +62,18 @@ __global__ __launch_bounds__(NB_THREADS) void mask_border_kernel(const NeighP<S>
     __syncthreads();
     long long acc[3] = {0, 0, 0};
     int y0, y1, c0, c1;
-    if (clipped_box(v, b, p.H, p.W, y0, y1, c0, c1)) {
+    if (mwords::clipped_box(v, b, p.H, p.W, y0, y1, c0, c1)) {
         const int rw = c1 - c0 + 1, n = (y1 - y0 + 1) * rw;
         const int wlast = (p.W - 1) >> 5;
         const uint32_t tail = (p.W & 31) ? (1u << (p.W & 31)) - 1u : 0xffffffffu;      // columns beyond W - 1 are nobody's pixels
         for (int i = tid; i < n; i += NB_THREADS) {
             const int ly = i / rw, y = y0 + ly, wx = c0 + (i - ly * rw);
-            uint32_t a = word_at(v, y, wx);
+            uint32_t a = mwords::word_at(v, y, wx);
             if (wx == wlast) a &= tail;
             if (!a) continue;
-            const uint32_t up = y > 0 ? word_at(v, y - 1, wx) : 0u, dn = y < p.H - 1 ? word_at(v, y + 1, wx) : 0u;
-            const uint32_t wl = word_at(v, y, wx - 1);
-            uint32_t wr = wx < wlast ? word_at(v, y, wx + 1) : 0u;
+            const uint32_t up = y > 0 ? mwords::word_at(v, y - 1, wx) : 0u, dn = y < p.H - 1 ? mwords::word_at(v, y + 1, wx) : 0u;
+            const uint32_t wl = mwords::word_at(v, y, wx - 1);
+            uint32_t wr = wx < wlast ? mwords::word_at(v, y, wx + 1) : 0u;
             if (wx + 1 == wlast) wr &= tail;
             const uint32_t lf = (a << 1) | (wl >> 31), rt = (a >> 1) | (wr << 31);
             uint32_t bd = a & ~(up & dn & lf & rt);
@@ -135,14 +95,8 @@ __global__ __launch_bounds__(NB_THREADS) void mask_border_kernel(const NeighP<S>
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) acc[j] = wave_sum(acc[j]);
-    if (lane == 0)
-        for (int j = 0; j < 3; ++j) s_acc[wave][j] = acc[j];
-    __syncthreads();
+    wreg::block_sum(acc, s_red);                             // (its barrier: s_count is final)
     if (tid == 0) {
-        for (int w = 1; w < NB_WAVES; ++w)
-            for (int j = 0; j < 3; ++j) acc[j] += s_acc[w][j];
         for (int j = 0; j < 3; ++j) p.sums[m * 3 + j] = acc[j];
         p.nborder[m] = s_count;
     }
@@ -219,7 +173,7 @@ __global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP
                 if (gap <= fixed || beats(gap, b, best_any, idx_any) || (same && beats(gap, b, best_grp, idx_grp))) kmin = min(kmin, key);
             }
         }
-        kmin = block_min(kmin, s_red);
+        kmin = wreg::block_min(kmin, s_red);
         if (kmin == NB_INF) break;
         last = kmin;
         const long b = kmin & idx_mask;
@@ -233,7 +187,7 @@ __global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP
         if ((kmin >> NB_IDX_BITS) == 0) {                    // the boxes meet: a shared pixel?
             const View vb = p.src.view(b);
             const long long c = mwords::pair_count<1>(va, ba, vb, bb, tid, NB_THREADS);
-            shared = -block_min(-c, s_red) > 0;
+            shared = -wreg::block_min(-c, s_red) > 0;
         }
         if (shared) d2 = 0;
         else {
@@ -260,7 +214,7 @@ __global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP
                     }
                 }
             }
-            d2 = block_min(dmin > (unsigned long long)NB_INF ? NB_INF : (long long)dmin, s_red);
+            d2 = wreg::block_min(dmin > (unsigned long long)NB_INF ? NB_INF : (long long)dmin, s_red);
         }
         if (d2 <= 2) ++touching;
         if (p.r2 >= 0 && d2 <= p.r2) ++within;
@@ -276,11 +230,8 @@ __global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP
 
 template <class S>
 int launch_neighbours(const NeighP<S>& p, hipStream_t st, const char* name) {
-    hipLaunchKernelGGL(mask_border_kernel<S>, dim3((unsigned)p.M), dim3(NB_THREADS), 0, st, p);
-    DEMIA_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(mask_neighbour_kernel<S>, dim3((unsigned)p.M), dim3(NB_THREADS), 0, st, p);
-    DEMIA_CHECK_LAUNCH(name);
-    return DEMIA_OK;
+    const int e = wreg::launch<mask_border_kernel<S>>(p, (unsigned)p.M, 0, st, name);
+    return e != DEMIA_OK ? e : wreg::launch<mask_neighbour_kernel<S>>(p, (unsigned)p.M, 0, st, name);
 }
 
 }  // namespace

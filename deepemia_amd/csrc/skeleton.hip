@@ -1,12 +1,10 @@
 // Morphological skeleton and its descriptors per external contour (demia_mask_skeleton / demia_crop_skeleton; definition:
-// include/deepemia_hip.h).  One kernel over a word source (maskwords.h), one workgroup per mask, the region machinery of
-// maskregion.h as it is -- the second measurement on the mask WORDS, built like the first (inscribed.hip).
+// include/deepemia_hip.h).  One kernel over a word source (maskwords.h), one workgroup per mask, on the region stage of
+// wordregion.h with TWO work buffers -- the second measurement on the mask WORDS.
 //
-// Per mask the region (tight box + 1 ring, clipped to the frame; mreg::region_of) is staged as the inscribed kernel stages it.
-// Three buffers of the region: A, the mask, which stays as it is, and P, Q, which the thinning plays ping-pong in -- in LDS up to
-// the tracer's large buffer; beyond it the planes read A in place and work in two scratch planes, the crops stage A and P in the
-// tracer's share and Q in a share of a second scratch.  Everything outside the region is background: the ring is, and where the
-// region ends on the frame the definition says so.
+// The stage hands over the region of the mask (tight box + 1 ring, clipped to the frame) as A, which stays as it is, and the
+// buffers P, Q, which the thinning plays ping-pong in; per contour it floods the contour's component K into P.  What is this
+// file's: the thinning, the skeleton written out, and the six sums over S & K.
 //
 // Thinning (Guo-Hall A1) is a Boolean function of a pixel's 3 x 3 neighbourhood, so it runs on 32 pixels per lane-operation:
 // lane = WORD, the eight neighbour planes of a word come from the three rows and the carry bits of the words left and right of
@@ -15,36 +13,18 @@
 // (the rectangle the pair before it changed, grown by two).  Then per contour: mreg::flood<true> of its component K into P, and six
 // popcount reductions over S & K.  Integer sums do not depend on which thread saw which word.  No per-pixel loop, no f32, plain
 // vector stores.
-#include <type_traits>
-#include "common.h"
-#include "maskregion.h"
-#include "maskwords.h"
+#include "wordregion.h"
 
 namespace {
 
 using mwords::CropWords;
 using mwords::PlaneWords;
 
-constexpr int SKEL_COLS = 8;
-constexpr int SKEL_WORDS = 8192;        // LDS words per region buffer: the tracer's TRACE_WORDS (contours.hip) -- its scratch contract
-constexpr int SKEL_LDS = 3 * SKEL_WORDS * 4;
+constexpr int SKEL_LDS = wreg::lds_words(2) * 4;
 
 template <class S>
-struct SkelP {
-    S src;
-    const int* select;           // [M] or NULL: position t reads the words of mask select[t]
-    uint32_t* scratch;           // the tracer's scratch
-    const long* scratch_off;     // crops: [set] words into scratch (demia_crop_contour_scratch)
-    uint32_t* scratch2;          // planes: one more plane per mask; crops: one more padded region per large room
-    const long* scratch2_off;    // crops: [set] words into scratch2 (demia_crop_skeleton_scratch)
-    const int* bbox;             // [M, 4]
-    const int* count;            // [M] or NULL (with out == NULL: thin only)
-    const int* info;             // [M, C, 4]
-    int H, W, C;
-    double um;
-    double* out;                 // [M, out_c, 8] or NULL
-    int out_c;
-    uint32_t* skel_out;          // NULL, or laid out like the source words
+struct SkelP : wreg::Params<S> {     // out == NULL (count, info too): thin only
+    uint32_t* skel_out;              // NULL, or laid out like the source words
 };
 
 // The eight neighbour planes of word (ly, lx) of X, named as the definition names them (y downwards): p2 = N, p3 = NE, p4 = E,
@@ -120,54 +100,13 @@ __global__ __launch_bounds__(256) void mask_skeleton_kernel(const SkelP<S> p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ int s_changed;
     __shared__ int s_win[4];
-    __shared__ long long s_acc[4][6];
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
-    const long t = blockIdx.x;
-    const long mw = p.select ? p.select[t] : t;
-    const int wpr = (p.W + 31) >> 5;
-    const mwords::View v = p.src.view(mw);
-    const int4 b4 = reinterpret_cast<const int4*>(p.bbox)[t];
-    int y0 = max(b4.x, 0), x0 = max(b4.y, 0), y1 = min(b4.z, p.H - 1), x1 = min(b4.w, p.W - 1);
-    if constexpr (!PLANE) {
-        // the box is inside the room by contract; clipped to it, the region lies inside the ROOM's region, which is what the
-        // host sized both scratches from
-        const int4 r = reinterpret_cast<const int4*>(p.src.room)[mw];
-        y0 = max(y0, r.x); x0 = max(x0, r.y); y1 = min(y1, r.z); x1 = min(x1, r.w);
-    }
-    const bool empty = b4.x < 0 || v.rows == 0 || y0 > y1 || x0 > x1;
-    double* out = p.out ? p.out + t * p.out_c * SKEL_COLS : nullptr;
-    int nc = 0;
-    if (out) {
-        nc = empty ? 0 : min(max(p.count[t], 0), min(p.out_c, p.C));
-        for (int i = nc * SKEL_COLS + tid; i < p.out_c * SKEL_COLS; i += nt) out[i] = 0.0;
-    }
-    if (empty || (nc == 0 && !p.skel_out)) return;
-    int ry0, wx0, rh, rw;
-    mreg::region_of(y0, x0, y1, x1, 1, p.H, p.W, ry0, wx0, rh, rw);
-    const int pn = (rh + 2) * (rw + 2), n = rh * rw;        // pn: the tracer's padded image, the unit of its LDS / scratch rule
-    const uint32_t* A = nullptr;
-    uint32_t *P, *Q;
-    int stride = rw;
-    uint32_t* stage = nullptr;
-    if (pn <= SKEL_WORDS) { stage = smem; P = smem + SKEL_WORDS; Q = smem + 2 * SKEL_WORDS; }
-    else if constexpr (PLANE) {                             // the plane itself and the two scratch planes, region in place
-        const long o = mw * p.H * wpr + (long)ry0 * wpr + wx0;
-        A = v.p + (long)ry0 * wpr + wx0;
-        P = p.scratch + o;
-        Q = p.scratch2 + o;
-        stride = wpr;
-    } else { stage = p.scratch + p.scratch_off[mw]; P = stage + pn; Q = p.scratch2 + p.scratch2_off[mw]; }
-    if (stage) {
-        // a word of the region outside the view (the ring of a box on the room's edge) is zero and is NEVER fetched: behind
-        // a room lie the next mask's words
-        for (int i = tid; i < n; i += nt) {
-            const int ly = i / rw, lx = i - ly * rw;
-            const int vy = ry0 + ly - v.y0, vx = wx0 + lx - v.c0;
-            const bool in = (unsigned)vy < (unsigned)v.rows && (unsigned)vx < (unsigned)v.cols;
-            stage[i] = in ? v.p[(long)vy * v.cols + vx] : 0u;
-        }
-        A = stage;
-    }
+    __shared__ long long s_red[wreg::WAVES * 6];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    wreg::Stage<2> r;
+    if (!wreg::stage(p, blockIdx.x, p.skel_out != nullptr, smem, r)) return;
+    const int rh = r.rh, rw = r.rw, n = r.n, stride = r.stride;
+    const uint32_t* A = r.A;
+    uint32_t *P = r.B[0], *Q = r.B[1];
     // Pairs of sub-iterations (A -> P -> Q, then Q -> P -> Q, ...) until a whole pair deletes nothing: the skeleton is in Q.  Every
     // pair that continues the loop deletes at least one pixel and none comes back, and the region has 32 * rh * rw of them: that
     // many pairs plus one always suffice, so the limit only bounds the loop and never cuts the thinning short.  (No smaller
@@ -203,33 +142,20 @@ __global__ __launch_bounds__(256) void mask_skeleton_kernel(const SkelP<S> p) {
         __syncthreads();
     }
     if (p.skel_out) {
+        const mwords::View v = r.v;
+        const int wpr = (p.W + 31) >> 5;
         for (int i = tid; i < n; i += nt) {
             const int ly = i / rw, lx = i - ly * rw;
             const uint32_t s = Q[ly * stride + lx];
-            if constexpr (PLANE) p.skel_out[mw * p.H * wpr + (long)(ry0 + ly) * wpr + wx0 + lx] = s;
+            if constexpr (PLANE) p.skel_out[r.mw * p.H * wpr + (long)(r.ry0 + ly) * wpr + r.wx0 + lx] = s;
             else {
-                const int vy = ry0 + ly - v.y0, vx = wx0 + lx - v.c0;
-                if ((unsigned)vy < (unsigned)v.rows && (unsigned)vx < (unsigned)v.cols) p.skel_out[p.src.offsets[mw] + (long)vy * v.cols + vx] = s;
+                const int vy = r.ry0 + ly - v.y0, vx = r.wx0 + lx - v.c0;
+                if ((unsigned)vy < (unsigned)v.rows && (unsigned)vx < (unsigned)v.cols) p.skel_out[p.src.offsets[r.mw] + (long)vy * v.cols + vx] = s;
             }
         }
     }
-    const int rpx = 32 * rw;
-    for (int c = 0; c < nc; ++c) {
-        const int4 inf = reinterpret_cast<const int4*>(p.info)[t * p.C + c];      // sx, sy, npts, offset
-        const int sy = inf.y - ry0, px = inf.x - 32 * wx0;
-        __syncthreads();                                     // P: the thinning's / the previous contour's readers are done
-        for (int i = tid; i < n; i += nt) P[(i / rw) * stride + i % rw] = 0u;
-        __syncthreads();
-        const bool ok = (unsigned)sy < (unsigned)rh && (unsigned)px < (unsigned)rpx && ((A[sy * stride + (px >> 5)] >> (px & 31)) & 1u);
-        double* o = out + c * SKEL_COLS;
-        if (!ok) {                                           // not a trace of these words: no component to measure
-            if (tid < SKEL_COLS) o[tid] = 0.0;
-            continue;
-        }
-        if (tid == 0) P[sy * stride + (px >> 5)] = 1u << (px & 31);
-        __syncthreads();
-        mreg::flood<true>(A, 0u, P, stride, rh, rw, &s_changed);
-        __syncthreads();
+    for (int c = 0; c < r.nc; ++c) {
+        if (!wreg::component(r, c, &s_changed)) continue;    // K into P, which the thinning has left
         // Sk = S & K.  Two components are never 8-adjacent and S is a subset of the mask, so every neighbour in S of a pixel of
         // Sk is in K: the neighbour planes are taken from S as they are.
         long long a[6] = {0, 0, 0, 0, 0, 0};                 // n, n4, nd, ends, branches, Npix
@@ -257,15 +183,9 @@ __global__ __launch_bounds__(256) void mask_skeleton_kernel(const SkelP<S> p) {
             a[3] += __popc(mid & g1 & ~g2);
             a[4] += __popc(mid & t3);
         }
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-            for (int s = 32; s > 0; s >>= 1) a[j] += __shfl_xor(a[j], s, 64);
-        if (lane == 0)
-            for (int j = 0; j < 6; ++j) s_acc[wave][j] = a[j];
-        __syncthreads();
+        wreg::block_sum(a, s_red);
         if (tid == 0) {
-            for (int w = 1; w < 4; ++w)
-                for (int j = 0; j < 6; ++j) a[j] += s_acc[w][j];
+            double* o = r.out + c * wreg::COLS;
             for (int j = 0; j < 6; ++j) o[j] = (double)a[j];
             o[6] = ((double)a[1] + sqrt(2.0) * (double)a[2]) * p.um;
             o[7] = a[0] > 0 ? (double)a[5] / (double)a[0] * p.um : 0.0;
@@ -273,65 +193,41 @@ __global__ __launch_bounds__(256) void mask_skeleton_kernel(const SkelP<S> p) {
     }
 }
 
-template <class S>
-int launch_skeleton(const SkelP<S>& p, int M, hipStream_t st, const char* name) {
-    auto k = mask_skeleton_kernel<S>;
-    static bool lds_set = false;                            // per instantiation
-    if (!lds_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, SKEL_LDS);
-        lds_set = true;
-    }
-    hipLaunchKernelGGL(k, dim3(M), dim3(256), SKEL_LDS, st, p);
-    DEMIA_CHECK_LAUNCH(name);
-    return DEMIA_OK;
-}
-
 }  // namespace
+
+// what both entries require, around the arguments that are the entry's own (distinct: no buffer of the call is another one)
+#define SKEL_REQUIRE(own_args, distinct)                                                                                      \
+    const bool measure = count || info || out;                                                                                \
+    DEMIA_REQUIRE(M >= 0 && H > 0 && W > 0 && (!measure || (C > 0 && out_c > 0)), "shapes");                                  \
+    if (M == 0) return DEMIA_OK;                                                                                              \
+    DEMIA_REQUIRE((own_args) && bbox && scratch && scratch2, "args");                                                         \
+    DEMIA_REQUIRE(measure ? (count && info && out) : skel_out != nullptr, "args");                                            \
+    DEMIA_REQUIRE(distinct, "args");                                                                                          \
+    DEMIA_REQUIRE((long)H * ((W + 31) >> 5) < (1L << 26), "sizes") /* 32 x the words of a region fit the loops' arithmetic */
 
 extern "C" int demia_mask_skeleton(const int32_t* select, const uint32_t* masks, uint32_t* scratch, const int32_t* bbox, const int32_t* count,
                                    const int32_t* info, int M, int H, int W, int C, double um_pix, double* out, int out_c,
                                    uint32_t* scratch2, uint32_t* skel_out, void* stream) {
-    const bool measure = count || info || out;
-    DEMIA_REQUIRE(M >= 0 && H > 0 && W > 0 && (!measure || (C > 0 && out_c > 0)), "shapes");
-    if (M == 0) return DEMIA_OK;
-    DEMIA_REQUIRE(masks && scratch && scratch2 && bbox && masks != scratch && masks != scratch2 && scratch != scratch2, "args");
-    DEMIA_REQUIRE(measure ? (count && info && out) : skel_out != nullptr, "args");
-    DEMIA_REQUIRE(skel_out != masks && skel_out != scratch && skel_out != scratch2, "args");
-    DEMIA_REQUIRE((long)H * ((W + 31) >> 5) < (1L << 26), "sizes");       // 32 x the words of a region fit the loops' arithmetic
-    SkelP<PlaneWords> p{PlaneWords{masks, H, (W + 31) >> 5, nullptr}, select, scratch, nullptr, scratch2, nullptr, bbox, count, info, H, W,
-                        measure ? C : 1, um_pix, out, measure ? out_c : 0, skel_out};
-    return launch_skeleton(p, M, (hipStream_t)stream, "mask_skeleton_kernel");
+    SKEL_REQUIRE(masks && masks != scratch && masks != scratch2 && scratch != scratch2,
+                 skel_out != masks && skel_out != scratch && skel_out != scratch2);
+    SkelP<PlaneWords> p{{PlaneWords{masks, H, (W + 31) >> 5, nullptr}, select, scratch, nullptr, scratch2, nullptr, bbox, count, info, H, W,
+                         measure ? C : 1, um_pix, out, measure ? out_c : 0}, skel_out};
+    return wreg::launch<mask_skeleton_kernel<PlaneWords>>(p, M, SKEL_LDS, (hipStream_t)stream, "mask_skeleton_kernel");
 }
 
-// Words of the SECOND scratch a crop-framed skeleton needs, from the host's room table alone: a mask whose ROOM's region (the rule
-// of demia_crop_contour_scratch) exceeds the large LDS buffer gets one more padded region buffer.
+// Words of the SECOND scratch a crop-framed skeleton needs: one more padded region buffer per large room.
 extern "C" int64_t demia_crop_skeleton_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch2_off) {
-    int64_t total = 0;
-    for (int64_t m = 0; m < M; ++m) {
-        const int32_t* r = room_host + 4 * m;
-        scratch2_off[m] = total;
-        if (r[0] < 0) continue;
-        int ry0, wx0, rh, rw;
-        mreg::region_of(r[0], r[1], r[2], r[3], 1, H, W, ry0, wx0, rh, rw);
-        const int64_t pn = (int64_t)(rh + 2) * (rw + 2);
-        if (pn > SKEL_WORDS) total += pn;
-    }
-    return total;
+    return wreg::room_scratch_words(room_host, M, H, W, 1, scratch2_off);
 }
 
 extern "C" int demia_crop_skeleton(const int32_t* select, const uint32_t* payload, const int32_t* room, const int64_t* offsets,
                                    const int32_t* bbox, const int32_t* count, const int32_t* info, int M, int H, int W, int C, double um_pix,
                                    double* out, int out_c, uint32_t* scratch, const int64_t* scratch_off, uint32_t* scratch2,
                                    const int64_t* scratch2_off, uint32_t* skel_out, void* stream) {
-    const bool measure = count || info || out;
-    DEMIA_REQUIRE(M >= 0 && H > 0 && W > 0 && (!measure || (C > 0 && out_c > 0)), "shapes");
-    if (M == 0) return DEMIA_OK;
-    DEMIA_REQUIRE(payload && room && offsets && bbox && scratch && scratch_off && scratch2 && scratch2_off, "args");
-    DEMIA_REQUIRE(measure ? (count && info && out) : skel_out != nullptr, "args");
-    DEMIA_REQUIRE(skel_out != payload, "args");
-    DEMIA_REQUIRE((long)H * ((W + 31) >> 5) < (1L << 26), "sizes");
-    SkelP<CropWords> p{CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, select, scratch,
-                       reinterpret_cast<const long*>(scratch_off), scratch2, reinterpret_cast<const long*>(scratch2_off), bbox, count, info,
-                       H, W, measure ? C : 1, um_pix, out, measure ? out_c : 0, skel_out};
-    return launch_skeleton(p, M, (hipStream_t)stream, "mask_skeleton_kernel<crop>");
+    SKEL_REQUIRE(payload && room && offsets && scratch_off && scratch2_off, skel_out != payload);
+    SkelP<CropWords> p{{CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, select, scratch,
+                        reinterpret_cast<const long*>(scratch_off), scratch2, reinterpret_cast<const long*>(scratch2_off), bbox, count, info,
+                        H, W, measure ? C : 1, um_pix, out, measure ? out_c : 0}, skel_out};
+    return wreg::launch<mask_skeleton_kernel<CropWords>>(p, M, SKEL_LDS, (hipStream_t)stream, "mask_skeleton_kernel<crop>");
 }
+
