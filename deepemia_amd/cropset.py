@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import _WORKLISTS, ContourSet, MaskOps, Neighbours, PlanePool, _neighbour_buffers, reads_words
+from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, PlanePool, _agglomerate_buffers, _neighbour_buffers,
+                      reads_words)
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
@@ -459,6 +460,22 @@ class CropMaskSet:
                                                  _lib.ptr(group_d), M, H, W, int(r2), _lib.ptr(off_d), _lib.ptr(res.points),
                                                  _lib.ptr(res.nborder), _lib.ptr(res.sums), _lib.ptr(res.table), ops._stream()),
                    "demia_crop_neighbours")
+        return res
+
+    def agglomerates(self, area=None, group=None, l2: int = 2, border: Optional[Neighbours] = None, label_lds_cap: int = 0) -> Agglomerates:
+        """``MaskOps.agglomerates`` on the words in place (``demia_crop_agglomerates``): the same tensors, no plane, no wait.
+        ``area``: the pixel counts on the host; None (and no ``border``): the set's own are read with a wait of their own.
+        ``border``: the ``Neighbours`` of :meth:`neighbours` on this set, whose border points are reused."""
+        M, ops = len(self), self.ops
+        H, W = self.hw
+        if area is None and border is None:
+            area = self.area.cpu().numpy() if M else np.zeros(0)
+        res, group_d, off_d = _agglomerate_buffers(ops, M, area, group, border)
+        _lib.check(ops.lib.demia_crop_agglomerates(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
+                                                   _lib.ptr(group_d), M, H, W, int(l2), _lib.ptr(off_d), _lib.ptr(res.points),
+                                                   _lib.ptr(res.nborder), _lib.ptr(res.sums), int(border is not None), _lib.ptr(res.links),
+                                                   _lib.ptr(res.degree), _lib.ptr(res.label), _lib.ptr(res.own), int(label_lds_cap),
+                                                   ops._stream()), "demia_crop_agglomerates")
         return res
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:

@@ -3,9 +3,7 @@
 // (maskwords.h: views, word_at, clipped_box, pair_count), one workgroup per mask each; the block reductions and the launch are
 // those of wordregion.h.
 //
-// mask_border_kernel    the border pixels of every mask as points (y << 16 | x), compacted into points[point_off[m] ..), with the
-//                       border count, the pixel count and the coordinate sums.  A border word is A & ~(up & down & left & right), 32
-//                       pixels per lane-operation; the neighbour words of a word outside the view read 0 and are never fetched.
+// mask_border_kernel    (maskborder.h, shared with agglomerates.hip) the border points, the pixel count and the coordinate sums.
 // mask_neighbour_kernel for mask a, d2(a, b) over the masks b that can still matter.  gap(a, b), the squared distance of the two
 //                       boxes, never exceeds d2(a, b), so b is evaluated only while gap <= max(best so far, r2, 2) -- in ascending
 //                       (gap, b), which makes `best` shrink after the first few.  A pair whose boxes meet is first asked for a shared
@@ -14,7 +12,7 @@
 //
 // Every decision is an integer comparison and every minimum and sum is order-free, so the result does not depend on which thread
 // saw which word or point.  No f32 / f64, no global atomics, plain vector stores.
-#include "wordregion.h"
+#include "maskborder.h"
 
 namespace {
 
@@ -32,80 +30,15 @@ constexpr int NB_THREADS = wreg::THREADS, NB_WAVES = wreg::WAVES;
 constexpr long long NB_INF = 0x7fffffffffffffffLL;
 constexpr int NB_IDX_BITS = 24;                      // a candidate's key is gap << 24 | b: gap < 2^34, M <= 2^24
 
+// the border stage's parameters (maskborder.h) and what the pairing adds
 template <class S>
-struct NeighP {
-    S src;
-    const int* bbox;             // [M, 4]
+struct NeighP : mborder::BorderP<S> {
     const int* group;            // [M] or NULL
-    long M;
-    int H, W;
     long long r2;
-    const long* point_off;       // [M + 1]
-    uint32_t* points;
-    int* nborder;                // [M]
-    long long* sums;             // [M, 3] N, Sx, Sy
     long long* table;            // [M, 6]
 };
 
-template <class S>
-__global__ __launch_bounds__(NB_THREADS) void mask_border_kernel(const NeighP<S> p) {
-    __shared__ int s_count;
-    __shared__ long long s_red[NB_WAVES * 3];
-    const int tid = threadIdx.x;
-    const long m = blockIdx.x;
-    const View v = p.src.view(m);
-    const int4 b = reinterpret_cast<const int4*>(p.bbox)[m];
-    const long off = p.point_off[m];
-    const long cap = p.point_off[m + 1] - off;               // border <= pixels: the host sized it from the pixel counts
-    uint32_t* out = p.points + off;
-    if (tid == 0) s_count = 0;
-    __syncthreads();
-    long long acc[3] = {0, 0, 0};
-    int y0, y1, c0, c1;
-    if (mwords::clipped_box(v, b, p.H, p.W, y0, y1, c0, c1)) {
-        const int rw = c1 - c0 + 1, n = (y1 - y0 + 1) * rw;
-        const int wlast = (p.W - 1) >> 5;
-        const uint32_t tail = (p.W & 31) ? (1u << (p.W & 31)) - 1u : 0xffffffffu;      // columns beyond W - 1 are nobody's pixels
-        for (int i = tid; i < n; i += NB_THREADS) {
-            const int ly = i / rw, y = y0 + ly, wx = c0 + (i - ly * rw);
-            uint32_t a = mwords::word_at(v, y, wx);
-            if (wx == wlast) a &= tail;
-            if (!a) continue;
-            const uint32_t up = y > 0 ? mwords::word_at(v, y - 1, wx) : 0u, dn = y < p.H - 1 ? mwords::word_at(v, y + 1, wx) : 0u;
-            const uint32_t wl = mwords::word_at(v, y, wx - 1);
-            uint32_t wr = wx < wlast ? mwords::word_at(v, y, wx + 1) : 0u;
-            if (wx + 1 == wlast) wr &= tail;
-            const uint32_t lf = (a << 1) | (wl >> 31), rt = (a >> 1) | (wr << 31);
-            uint32_t bd = a & ~(up & dn & lf & rt);
-            const int na = __popc(a);
-            // sum of the bit positions of a word, by bit of the position
-            const int sx = __popc(a & 0xaaaaaaaau) + 2 * __popc(a & 0xccccccccu) + 4 * __popc(a & 0xf0f0f0f0u) + 8 * __popc(a & 0xff00ff00u) +
-                           16 * __popc(a & 0xffff0000u);
-            acc[0] += na;
-            acc[1] += (long long)na * (32 * wx) + sx;
-            acc[2] += (long long)na * y;
-            if (bd) {
-                int k = atomicAdd(&s_count, __popc(bd));      // LDS; the order inside a mask is unspecified
-                while (bd) {
-                    const int bit = __ffs(bd) - 1;
-                    bd &= bd - 1;
-                    if (k < cap) out[k] = ((uint32_t)y << 16) | (uint32_t)(32 * wx + bit);
-                    ++k;
-                }
-            }
-        }
-    }
-    wreg::block_sum(acc, s_red);                             // (its barrier: s_count is final)
-    if (tid == 0) {
-        for (int j = 0; j < 3; ++j) p.sums[m * 3 + j] = acc[j];
-        p.nborder[m] = s_count;
-    }
-}
-
-__device__ __forceinline__ long long box_gap(const int4 a, const int4 b) {
-    const long long gy = max(0, max(b.x - a.z, a.x - b.z)), gx = max(0, max(b.y - a.w, a.y - b.w));
-    return gx * gx + gy * gy;
-}
+using mborder::box_gap;
 
 // (d, i) < (best, idx): a candidate that can still take the place of the nearest so far (idx < 0: none yet)
 __device__ __forceinline__ bool beats(long long d, long i, long long best, long idx) { return idx < 0 || d < best || (d == best && i < idx); }
@@ -230,7 +163,7 @@ __global__ __launch_bounds__(NB_THREADS) void mask_neighbour_kernel(const NeighP
 
 template <class S>
 int launch_neighbours(const NeighP<S>& p, hipStream_t st, const char* name) {
-    const int e = wreg::launch<mask_border_kernel<S>>(p, (unsigned)p.M, 0, st, name);
+    const int e = mborder::launch_border<S>(p, st, name);
     return e != DEMIA_OK ? e : wreg::launch<mask_neighbour_kernel<S>>(p, (unsigned)p.M, 0, st, name);
 }
 
@@ -246,9 +179,9 @@ extern "C" int demia_mask_neighbours(const uint32_t* masks, const int32_t* bbox,
                                      void* stream) {
     NB_REQUIRE_COMMON();
     DEMIA_REQUIRE(masks != nullptr, "args");
-    NeighP<PlaneWords> p{PlaneWords{masks, H, (W + 31) >> 5, nullptr}, bbox, group, (long)M, H, W, (long long)r2,
-                         reinterpret_cast<const long*>(point_off), points, nborder, reinterpret_cast<long long*>(sums),
-                         reinterpret_cast<long long*>(table)};
+    NeighP<PlaneWords> p{{PlaneWords{masks, H, (W + 31) >> 5, nullptr}, bbox, (long)M, H, W, reinterpret_cast<const long*>(point_off),
+                          points, nborder, reinterpret_cast<long long*>(sums)},
+                         group, (long long)r2, reinterpret_cast<long long*>(table)};
     return launch_neighbours(p, (hipStream_t)stream, "mask_neighbour_kernel");
 }
 
@@ -257,8 +190,8 @@ extern "C" int demia_crop_neighbours(const uint32_t* payload, const int32_t* roo
                                      int32_t* nborder, int64_t* sums, int64_t* table, void* stream) {
     NB_REQUIRE_COMMON();
     DEMIA_REQUIRE(payload && room && offsets, "args");
-    NeighP<CropWords> p{CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, bbox, group, (long)M, H, W, (long long)r2,
-                        reinterpret_cast<const long*>(point_off), points, nborder, reinterpret_cast<long long*>(sums),
-                        reinterpret_cast<long long*>(table)};
+    NeighP<CropWords> p{{CropWords{payload, room, reinterpret_cast<const long*>(offsets)}, bbox, (long)M, H, W,
+                         reinterpret_cast<const long*>(point_off), points, nborder, reinterpret_cast<long long*>(sums)},
+                        group, (long long)r2, reinterpret_cast<long long*>(table)};
     return launch_neighbours(p, (hipStream_t)stream, "mask_neighbour_kernel<crop>");
 }

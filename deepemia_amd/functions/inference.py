@@ -32,7 +32,7 @@ from ..data.models import choose_and_use_model, get_trained_model_paths
 from .. import _lib as _L
 from .. import parallel
 from ..cropset import CropMaskAlgebra, CropMaskSet, CropPlanes, crop_contours, crop_gray_histogram, crop_planes, rooms_of_placed_tiles, trace_chunks
-from ..maskset import FAMILIES, MaskOps, Neighbours, families
+from ..maskset import FAMILIES, Agglomerates, MaskOps, Neighbours, families
 from ..utils.config import get_config
 from ..utils.logger_utils import log_memory_usage, system_logger
 from ..utils.mask_algebra import DeviceMaskAlgebra
@@ -407,6 +407,99 @@ def write_neighbours(output_dir: str, image_names: Sequence[str], rows_by_image:
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(NEIGHBOUR_CSV_HEADER)
+        for name in image_names:
+            for r in rows_by_image.get(name, []):
+                w.writerow(r)
+    return path
+
+
+AGGLOMERATE_CSV_HEADER = ["Agglomerate_ID", "Members", "Member ids", "Class counts", "Links", "Mean coordination", "Pixels", "Member pixels",
+                          "Centroid x", "Centroid y", "Equivalent diameter", "Radius of gyration", "Major extent", "Minor extent", "Orientation",
+                          "Detected scale bar", "File name"]
+AGGLOMERATE_LINKS = ("any", "same_class")
+
+
+class AgglomerateSetting(NamedTuple):
+    enabled: bool
+    gap: Optional[float]             # in the CSV's length unit (um with a scale bar, else pixels); None: touching
+    link: str                        # one of AGGLOMERATE_LINKS
+
+
+def agglomerates_setting(inf_settings: dict) -> AgglomerateSetting:
+    """``inference_settings.agglomerate_statistics`` (per dataset, default false): ``true`` runs the agglomerate stage
+    (``demia_mask_agglomerates``) on every image's final instances and writes ``agglomerates_results.csv`` -- one row per cluster of
+    linked instances, singletons included -- in every mask frame; ``false`` launches, allocates, copies and writes nothing.
+    ``inference_settings.agglomerate_gap`` (optional): two instances link when their edge-to-edge distance is at most this, in the
+    CSV's length unit; unset (and anything below touching) is touching, 8-connected contact or overlap.
+    ``inference_settings.agglomerate_link``: ``"any"`` (the default) links across classes, ``"same_class"`` only within one.
+    Anything but a bool, a gap that is not a finite number >= 0 and any other link value are configuration errors."""
+    value = (inf_settings or {}).get("agglomerate_statistics", False)
+    if not isinstance(value, bool):
+        raise ValueError(f"inference_settings.agglomerate_statistics must be true or false, got {value!r}")
+    gap = (inf_settings or {}).get("agglomerate_gap", None)
+    if gap is not None:
+        if isinstance(gap, bool) or not isinstance(gap, (int, float)) or not math.isfinite(gap) or gap < 0:
+            raise ValueError(f"inference_settings.agglomerate_gap must be a finite number >= 0, got {gap!r}")
+        gap = float(gap)
+    link = (inf_settings or {}).get("agglomerate_link", "any")
+    if not isinstance(link, str) or link not in AGGLOMERATE_LINKS:
+        raise ValueError(f"inference_settings.agglomerate_link must be one of {', '.join(AGGLOMERATE_LINKS)}, got {link!r}")
+    return AgglomerateSetting(value, gap, link)
+
+
+def agglomerate_l2(gap: Optional[float], um_pix: float) -> int:
+    """The link threshold of one image in squared pixels: ``max(2, floor((gap / um_pix)^2))``, 2 (touching) without a gap."""
+    if gap is None:
+        return 2
+    return max(2, int(math.floor((gap / um_pix) ** 2)))
+
+
+class AgglomerateStage:
+    """The agglomerate stage of one image as ``measure_image`` runs it: the caller states gap and link, ``rows`` comes back."""
+
+    def __init__(self, gap: Optional[float] = None, link: str = "any"):
+        self.gap, self.link = gap, link
+        self.rows: List[list] = []
+
+
+def agglomerate_rows(image_name: str, classes: Sequence[int], thing_classes, label: np.ndarray, degree: np.ndarray, own: np.ndarray,
+                     pixels: Sequence[int], um_pix: float, psum: str = "0") -> List[list]:
+    """The rows of ``agglomerates_results.csv`` (``AGGLOMERATE_CSV_HEADER``) for one image from the stage's tables (``label`` [M],
+    ``degree`` [M], ``own`` [M, 6]; definitions in ``include/deepemia_hip.h``) and the instances' pixel counts ``pixels`` [M]: one
+    row per component with a pixel in ascending label, ids ``<image>_A<k>`` (k from 1), members as the ``<image>_<i + 1>`` of
+    ``measurements_results.csv``.  The totals N, Sx, Sy, Sxx, Syy, Sxy are the sums of ``own`` over the members as Python ints --
+    the moments of the union, a shared pixel counted once -- and the central moments come from them by one division each."""
+    members: Dict[int, List[int]] = {}
+    for i, lab in enumerate(label):
+        if int(lab) >= 0:
+            members.setdefault(int(lab), []).append(i)
+    rows = []
+    for k, lab in enumerate(sorted(members), start=1):
+        mem = members[lab]
+        n, sx, sy, sxx, syy, sxy = (sum(int(own[i][j]) for i in mem) for j in range(6))
+        if n <= 0:
+            continue
+        counts: Dict[int, int] = {}
+        for i in mem:
+            counts[int(classes[i])] = counts.get(int(classes[i]), 0) + 1
+        names = " ".join(f"{thing_classes[c] if c < len(thing_classes) else f'class_{c}'}:{counts[c]}" for c in sorted(counts))
+        links = sum(int(degree[i]) for i in mem) // 2
+        mxx, myy, mxy = (n * sxx - sx * sx) / (n * n), (n * syy - sy * sy) / (n * n), (n * sxy - sx * sy) / (n * n)
+        root = math.sqrt(((mxx - myy) / 2) ** 2 + mxy ** 2)
+        lam_hi, lam_lo = (mxx + myy) / 2 + root, (mxx + myy) / 2 - root
+        rows.append([f"{image_name}_A{k}", len(mem), " ".join(f"{image_name}_{i + 1}" for i in mem), names, links, 2 * links / len(mem), n,
+                     sum(int(pixels[i]) for i in mem), (sx / n) * um_pix, (sy / n) * um_pix, math.sqrt(4 * n / math.pi) * um_pix,
+                     math.sqrt(mxx + myy) * um_pix, 4 * math.sqrt(lam_hi) * um_pix, 4 * math.sqrt(max(lam_lo, 0.0)) * um_pix,
+                     math.degrees(0.5 * math.atan2(2 * mxy, mxx - myy)), psum, image_name])
+    return rows
+
+
+def write_agglomerates(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
+    """``agglomerates_results.csv``: the header and every image's rows of ``agglomerate_rows``, in the images' order."""
+    path = os.path.join(output_dir, "agglomerates_results.csv")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(AGGLOMERATE_CSV_HEADER)
         for name in image_names:
             for r in rows_by_image.get(name, []):
                 w.writerow(r)
@@ -2228,6 +2321,7 @@ class PipelineSettings:
         self.detections_per_image = detections_per_image_setting(inf)     # (the model loader reads it too: a bad value ends the run here)
         self.descriptors = descriptors_setting(inf)
         self.neighbours = neighbours_setting(inf)
+        self.agglomerates = agglomerates_setting(inf)
         # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
         self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
 
@@ -2447,6 +2541,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
     rle_by_image: Dict[str, List[str]] = {}       # per image the EncodedPixels texts of its final instances (a16)
     rows_by_image: Dict[str, List[list]] = {}     # per image its measurement rows (a17-a19), measured while the image is still resident
     neighbour_rows_by_image: Dict[str, List[list]] = {}      # ... and, with neighbour_statistics, its rows of neighbours_results.csv
+    agglomerate_rows_by_image: Dict[str, List[list]] = {}    # ... and, with agglomerate_statistics, of agglomerates_results.csv
     keep_masks = os.environ.get("DEEPEMIA_KEEP_MASKS", "0") == "1"
     dedup_results: Dict[str, dict] = {}
     processed = set()
@@ -2578,11 +2673,15 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                     crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
                 extra = [crop[0]] if crop is not None else None
                 stage = NeighbourStage(st.neighbours.radius) if st.neighbours.enabled else None
+                agg = AgglomerateStage(st.agglomerates.gap, st.agglomerates.link) if st.agglomerates.enabled else None
                 rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
                                                     visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes,
-                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors, neighbours=stage)
+                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors, neighbours=stage,
+                                                    agglomerates=agg)
                 if stage is not None:
                     neighbour_rows_by_image[name] = stage.rows
+                if agg is not None:
+                    agglomerate_rows_by_image[name] = agg.rows
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final and pipe.crop:
@@ -2654,15 +2753,16 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                        f"{total / max(len(my_images), 1):.4f}s/image, {pipe.forward_calls} batched forwards")
     if shard_images:
         # the ONE exchange of the image-sharded job: every rank's rows and texts go to rank 0, which writes the files
-        mine = (rle_by_image, (rows_by_image, neighbour_rows_by_image),
+        mine = (rle_by_image, (rows_by_image, neighbour_rows_by_image, agglomerate_rows_by_image),
                 {k: {kk: vv for kk, vv in v.items() if kk != "masks"} for k, v in dedup_results.items()}, sorted(processed))
         gathered = [None] * job_world
         dist.all_gather_object(gathered, mine)         # (an all-gather: the object collective every backend, RCCL included, supports)
         if job_rank == 0:
-            for r_rle, (r_rows, r_nrows), r_res, r_done in gathered[1:]:
+            for r_rle, (r_rows, r_nrows, r_arows), r_res, r_done in gathered[1:]:
                 rle_by_image.update(r_rle)
                 rows_by_image.update(r_rows)
                 neighbour_rows_by_image.update(r_nrows)
+                agglomerate_rows_by_image.update(r_arows)
                 for k, v in r_res.items():
                     dedup_results.setdefault(k, dict(v, masks=None))
                 processed.update(r_done)
@@ -2681,9 +2781,12 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
 
         write_measurements(pipe.ops, dedup_results, inpath, output_dir, metadata, dataset_name, draw_scalebar, visualize,
                            rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, descriptors=st.descriptors,
-                           neighbours=st.neighbours, neighbour_rows_by_image=neighbour_rows_by_image)
+                           neighbours=st.neighbours, neighbour_rows_by_image=neighbour_rows_by_image,
+                           agglomerates=st.agglomerates, agglomerate_rows_by_image=agglomerate_rows_by_image)
         if st.neighbours.enabled:
             write_neighbours(output_dir, images_name, neighbour_rows_by_image)
+        if st.agglomerates.enabled:
+            write_agglomerates(output_dir, images_name, agglomerate_rows_by_image)
         with open(os.path.join(output_dir, "class_color_legend.txt"), "w") as f:
             f.write("Class Color Legend (BGR)\n")
             for i, cname in enumerate(metadata.thing_classes):
@@ -2818,12 +2921,16 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
                   extra: Optional[list] = None, note_planes=None, crop_direct: bool = False,
-                  descriptors: Sequence[str] = (), neighbours: Optional[NeighbourStage] = None) -> List[list]:
+                  descriptors: Sequence[str] = (), neighbours: Optional[NeighbourStage] = None,
+                  agglomerates: Optional[AgglomerateStage] = None) -> List[list]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
     mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
     ``neighbours``: the neighbour stage (``neighbours_setting``) runs on the same final set with the scale detected here; it is
     enqueued before the trace's fetch and its two tables ride in that fetch's copy, so it adds no wait; its rows of
     ``neighbours_results.csv`` come back in ``neighbours.rows``.
+    ``agglomerates``: the agglomerate stage (``agglomerates_setting``) likewise, behind the neighbour stage, whose border points it
+    reuses when both are on; its three small tables ride in the same copy and its rows of ``agglomerates_results.csv`` come back
+    in ``agglomerates.rows``.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
     the file here, which gives the same bytes).  ``crop_direct``: a crop-framed set is traced, measured and histogrammed on its
     words in place (``mask_frame: crop_direct``) instead of through the plane pool.  ``descriptors``: the contour records, and
@@ -2853,6 +2960,8 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     packed, classes = data["masks"], data["classes"]
     if neighbours is not None:
         neighbours.rows = []
+    if agglomerates is not None:
+        agglomerates.rows = []
     if packed is None or packed.shape[0] == 0:
         return []
     h, wd = data["hw"]
@@ -2866,8 +2975,10 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     if not crop and data.get("bbox") is not None:
         bbox_dev = ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32))
     # ``ride``: the int32 device tensors that come to the host in the trace's own copy -- the caller's ``extra`` (the cropped words of
-    # the RLE texts; replaced in place by their host arrays) and, behind them, the two tables of the neighbour stage
+    # the RLE texts; replaced in place by their host arrays) and, behind them, the two tables of the neighbour stage and the three
+    # of the agglomerate stage
     ride = extra
+    nb = None
     if neighbours is not None:
         group = np.asarray(classes, dtype=np.int32)
         r2 = neighbour_r2(neighbours.radius, um_pix)
@@ -2876,6 +2987,14 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
         else:
             nb = ops.neighbours(packed, bbox_dev, data.get("area") if bbox_dev is not None else None, group=group, r2=r2)
         ride = list(extra or []) + [nb.table_i32, nb.sums_i32]
+    if agglomerates is not None:
+        grp = np.asarray(classes, dtype=np.int32) if agglomerates.link == "same_class" else None
+        l2 = agglomerate_l2(agglomerates.gap, um_pix)
+        if crop:
+            ag = packed.agglomerates(area=data.get("area"), group=grp, l2=l2, border=nb)
+        else:
+            ag = ops.agglomerates(packed, bbox_dev, data.get("area") if bbox_dev is not None else None, group=grp, l2=l2, border=nb)
+        ride = list(ride or []) + ag.ride
     if direct:
         # a crop-framed set traced and measured on its words in place: one trace, one fetch, no plane
         area_h = data.get("area")
@@ -2898,9 +3017,16 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
             ride_host = [e.cpu().numpy() for e in ride]
     if extra is not None:
         extra[:] = ride_host[:len(extra)]
+    n_extra = 0 if extra is None else len(extra)
     if neighbours is not None:
-        table, sums = Neighbours.from_i32(ride_host[-2], ride_host[-1])
+        table, sums = Neighbours.from_i32(ride_host[n_extra], ride_host[n_extra + 1])
         neighbours.rows = neighbour_rows(test_img, classes, metadata.thing_classes, table, sums, um_pix, psum)
+    if agglomerates is not None:
+        label, degree, own = Agglomerates.from_i32(*ride_host[-3:])
+        pixels = data.get("area")
+        if pixels is None:          # (a caller outside the pipeline: the border stage's counts, with a wait of their own)
+            pixels = ag.sums[:, 0].cpu().numpy()
+        agglomerates.rows = agglomerate_rows(test_img, classes, metadata.thing_classes, label, degree, own, pixels, um_pix, psum)
     contrast = [(None, None, None)] * int(packed.shape[0])
     if measure_contrast:
         # measurements.py:195-215: gray levels under the whole instance mask; the histogram is a device reduction
@@ -2921,13 +3047,16 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
                        dataset_name: str, draw_scalebar: bool = False, visualize: bool = False,
                        rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False,
                        descriptors: Sequence[str] = (), neighbours: Optional[NeighbourSetting] = None,
-                       neighbour_rows_by_image: Optional[Dict[str, List[list]]] = None) -> str:
+                       neighbour_rows_by_image: Optional[Dict[str, List[list]]] = None,
+                       agglomerates: Optional[AgglomerateSetting] = None,
+                       agglomerate_rows_by_image: Optional[Dict[str, List[list]]] = None) -> str:
     """Measurement phase (``inference.py:983-1291``): one CSV row per external contour that passes
     the area gate, 20 columns, ``None`` -> empty field, floats through ``csv.writer``.  ``rows_by_image``: rows the image
     loop (or another rank, when images are sharded over ranks) has already measured; images without an entry are measured here.
     ``descriptors``: each requested family of ``DESCRIPTOR_CSV`` appends its columns behind "File name", in table order (rows
     measured elsewhere come with them).  ``neighbours`` enabled: an image measured here also runs the neighbour stage, as the image
-    loop does, and files its rows of ``neighbours_results.csv`` in ``neighbour_rows_by_image``."""
+    loop does, and files its rows of ``neighbours_results.csv`` in ``neighbour_rows_by_image``; ``agglomerates`` and
+    ``agglomerate_rows_by_image`` likewise for ``agglomerates_results.csv``."""
     csv_filename = os.path.join(output_dir, "measurements_results.csv")
     with open(csv_filename, "w", newline="") as csvfile:
         w = csv.writer(csvfile)
@@ -2940,10 +3069,13 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
                 rows = rows_by_image[test_img]
             else:
                 stage = NeighbourStage(neighbours.radius) if (neighbours is not None and neighbours.enabled) else None
+                agg = AgglomerateStage(agglomerates.gap, agglomerates.link) if (agglomerates is not None and agglomerates.enabled) else None
                 rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                                     crop_direct=crop_direct, descriptors=descriptors, neighbours=stage)
+                                     crop_direct=crop_direct, descriptors=descriptors, neighbours=stage, agglomerates=agg)
                 if stage is not None and neighbour_rows_by_image is not None:
                     neighbour_rows_by_image[test_img] = stage.rows
+                if agg is not None and agglomerate_rows_by_image is not None:
+                    agglomerate_rows_by_image[test_img] = agg.rows
             for r in rows:
                 w.writerow(r)
             csvfile.flush()

@@ -141,6 +141,7 @@ class Neighbours:
     nborder: torch.Tensor        # [M] int32
     points: torch.Tensor         # int32 words: mask m's border pixels (y << 16 | x) from point_off[m]
     point_off: np.ndarray        # [M + 1] int64, on the host
+    point_off_dev: Optional[torch.Tensor] = None             # ... and where the stage uploaded it (the agglomerate stage reuses it)
 
     # int32 views of the two tables: what rides in ContourSet.fetch(extra=...)
     @property
@@ -159,12 +160,15 @@ class Neighbours:
         return t, s
 
 
-def _neighbour_buffers(ops: "MaskOps", M: int, area, group) -> Tuple[Neighbours, Optional[torch.Tensor], torch.Tensor]:
-    """The outputs of one neighbour stage and its two host tables on the device, in ONE upload: (result, group or None, point_off)."""
+def _neighbour_buffers(ops: "MaskOps", M: int, area, group,
+                       with_table: bool = True) -> Tuple[Neighbours, Optional[torch.Tensor], torch.Tensor]:
+    """The outputs of one neighbour stage and its two host tables on the device, in ONE upload: (result, group or None, point_off).
+    ``with_table`` false: the border stage alone, for a caller that pairs the points itself."""
     off = neighbour_offsets(area)
     assert len(off) == M + 1
     dev = ops.device
-    res = Neighbours(torch.empty((M, 6), dtype=torch.int64, device=dev), torch.empty((M, 3), dtype=torch.int64, device=dev),
+    res = Neighbours(torch.empty((M, 6), dtype=torch.int64, device=dev) if with_table else None,
+                     torch.empty((M, 3), dtype=torch.int64, device=dev),
                      torch.empty((M,), dtype=torch.int32, device=dev), torch.empty((max(int(off[-1]), 1),), dtype=torch.int32, device=dev), off)
     parts = [off.view(np.int32)]
     if group is not None:
@@ -172,7 +176,68 @@ def _neighbour_buffers(ops: "MaskOps", M: int, area, group) -> Tuple[Neighbours,
         assert len(g) == M
         parts.append(g)
     tab = ops.upload(np.concatenate(parts))
-    return res, (tab[2 * (M + 1):] if group is not None else None), tab[:2 * (M + 1)].view(torch.int64)
+    res.point_off_dev = tab[:2 * (M + 1)].view(torch.int64)
+    return res, (tab[2 * (M + 1):] if group is not None else None), res.point_off_dev
+
+
+@dataclass
+class Agglomerates:
+    """What ``MaskOps.agglomerates`` / ``CropMaskSet.agglomerates`` enqueued (``demia_mask_agglomerates``), all on the device."""
+    links: torch.Tensor          # [M, ceil(M / 32)] int32 words: bit b of row a = link(a, b); stays on the device
+    degree: torch.Tensor         # [M] int32
+    label: torch.Tensor          # [M] int32: the smallest index of the mask's component, -1 without a pixel
+    own: torch.Tensor            # [M, 6] int64: N, Sx, Sy, Sxx, Syy, Sxy of the pixels no linked lower mask holds
+    sums: torch.Tensor           # [M, 3] int64, nborder, points, point_off: the border stage's (a Neighbours' own when reused)
+    nborder: torch.Tensor
+    points: torch.Tensor
+    point_off: np.ndarray
+
+    # int32 views of the three small tables: what rides in ContourSet.fetch(extra=...), 56 bytes per mask
+    @property
+    def label_i32(self) -> torch.Tensor:
+        return self.label
+
+    @property
+    def degree_i32(self) -> torch.Tensor:
+        return self.degree
+
+    @property
+    def own_i32(self) -> torch.Tensor:
+        return self.own.view(torch.int32)
+
+    @property
+    def ride(self) -> List[torch.Tensor]:
+        return [self.label_i32, self.degree_i32, self.own_i32]
+
+    @staticmethod
+    def from_i32(label_i32: np.ndarray, degree_i32: np.ndarray, own_i32: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The host copies of the ride as ``label`` [M] int32, ``degree`` [M] int32 and ``own`` [M, 6] int64."""
+        lab = np.ascontiguousarray(label_i32, dtype=np.int32).reshape(-1)
+        deg = np.ascontiguousarray(degree_i32, dtype=np.int32).reshape(-1)
+        own = np.ascontiguousarray(own_i32, dtype=np.int32).reshape(-1).view(np.int64).reshape(-1, 6)
+        return lab, deg, own
+
+
+def _agglomerate_buffers(ops: "MaskOps", M: int, area, group, border: Optional[Neighbours]):
+    """The outputs of one agglomerate stage and its host tables on the device: (result, group or None, point_off).  Without
+    ``border`` the border tensors and the one upload are those of a neighbour stage (its pair table is not made); with it -- a
+    ``Neighbours`` of the same masks -- its border tensors and its uploaded ``point_off`` are reused and only ``group``, if any,
+    is uploaded."""
+    dev = ops.device
+    wpl = (M + 31) // 32
+    if border is not None:
+        assert len(border.point_off) == M + 1 and border.point_off_dev is not None
+        nb, off_d, group_d = border, border.point_off_dev, None
+        if group is not None and M:
+            g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+            assert len(g) == M
+            group_d = ops.upload(g)
+    else:
+        nb, group_d, off_d = _neighbour_buffers(ops, M, area, group, with_table=False)
+    res = Agglomerates(torch.empty((M, wpl), dtype=torch.int32, device=dev), torch.empty((M,), dtype=torch.int32, device=dev),
+                       torch.empty((M,), dtype=torch.int32, device=dev), torch.empty((M, 6), dtype=torch.int64, device=dev),
+                       nb.sums, nb.nborder, nb.points, nb.point_off)
+    return res, group_d, off_d
 
 
 class PlanePool:
@@ -526,6 +591,27 @@ class MaskOps:
         _lib.check(self.lib.demia_mask_neighbours(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(group_d), M, H, self._w(packed), int(r2),
                                                   _lib.ptr(off_d), _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums),
                                                   _lib.ptr(res.table), self._stream()), "demia_mask_neighbours")
+        return res
+
+    def agglomerates(self, packed: torch.Tensor, bbox: Optional[torch.Tensor], area, group=None, l2: int = 2,
+                     border: Optional[Neighbours] = None, label_lds_cap: int = 0) -> Agglomerates:
+        """The link graph between the masks of ``packed``, its components and the moments that count shared pixels once
+        (``demia_mask_agglomerates``; the definitions are in ``include/deepemia_hip.h``): enqueued without a wait, the device
+        tensors returned.  ``bbox``, ``area``, ``group``: as for :meth:`neighbours`; ``l2``: the link threshold in squared pixels,
+        at least 2; ``border``: the ``Neighbours`` that :meth:`neighbours` returned for the same ``packed``, ``bbox`` and ``area``
+        on this stream -- its border points are reused and the border kernel is not launched again."""
+        M, H, wpr = packed.shape
+        if M and border is None and (area is None or bbox is None):
+            a, bbox = self.area_bbox(packed, bbox)
+            area = a.cpu().numpy()
+        elif M and bbox is None:
+            _, bbox = self.area_bbox(packed, bbox)
+        res, group_d, off_d = _agglomerate_buffers(self, M, area if M else np.zeros(0), group, border)
+        _lib.check(self.lib.demia_mask_agglomerates(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(group_d), M, H, self._w(packed), int(l2),
+                                                    _lib.ptr(off_d), _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums),
+                                                    int(border is not None), _lib.ptr(res.links), _lib.ptr(res.degree),
+                                                    _lib.ptr(res.label), _lib.ptr(res.own), int(label_lds_cap), self._stream()),
+                   "demia_mask_agglomerates")
         return res
 
     def skeleton(self, packed: torch.Tensor, bbox: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -656,6 +656,45 @@ int demia_crop_neighbours(const uint32_t* payload, const int32_t* room, const in
                           const int64_t* point_off /* [M + 1] */, uint32_t* points, int32_t* nborder /* [M] */,
                           int64_t* sums /* [M, 3] */, int64_t* table /* [M, 6] */, void* stream);
 
+/* demia_mask_agglomerates / demia_crop_agglomerates = which masks of one frame together form one body: the link graph between the
+ * masks, its connected components, and moments that count a pixel shared by linked masks once (not in the reference program;
+ * opt-in: inference_settings.agglomerate_statistics).  One row per mask on the device; the host sums the rows of a component.
+ * P, N, d2, bbox, points, point_off, nborder and sums [M, 3] are those of demia_mask_neighbours above.
+ *   L2   the link threshold in squared pixels, L2 >= 2; 2 is the neighbour stage's "touching": 8-connected contact.
+ *   link(a, b)   a != b, N(a) > 0, N(b) > 0, d2(a, b) <= L2 and, with a group array, group[a] == group[b].  Symmetric.
+ *   links [M, ceil(M / 32)] u32: bit (b & 31) of word (b >> 5) of row a is link(a, b); symmetric, the diagonal and the pad bits
+ *       beyond M - 1 are zero.  It stays on the device.
+ *   degree [M] i32 = the popcount of row m.
+ *   label [M] i32 = the smallest index in m's connected component of the link graph; -1 for a mask with N = 0.  It does not
+ *       depend on the order of evaluation.
+ *   own [M, 6] i64 = N, Sx, Sy, Sxx, Syy, Sxy over the pixels of m in columns < W that belong to no mask b < m with link(b, m), in
+ *       absolute pixel coordinates.  Two overlapping masks of one component are linked directly (d2 = 0, same group), so the sum
+ *       of own over a component is exactly the moments of the OR of its members; with group == NULL the sum of own[:, 0] over all
+ *       masks is the pixel count of the OR of every mask.
+ * Limits (DEMIA_EINVAL with a message): M <= 32768 (links is at most 128 MiB); H, W <= 32767 (N * x^2 stays below 2^60); L2 >= 2.
+ * have_border   1: points, nborder and sums were filled on this stream already (the caller's neighbour stage on the same masks,
+ *       bbox and point_off) and the border kernel is not launched again; 0: it is launched here.
+ * label_lds_cap   the component kernel holds the labels in LDS while M <= the cap and in `label` itself beyond; <= 0: the
+ *       default, 8192 (also the most).  Both paths give the same labels; a small cap lets a test take the second.
+ * Three kernels behind the border kernel: link (one workgroup per a; candidates by group and box gap <= L2 -- the gap never
+ * exceeds d2 --, boxes that meet are first asked for a shared pixel, otherwise "some border point of a within L2 of some border
+ * point of b", left at the first pair; each pair is decided from both sides, so a workgroup writes its own row only), component
+ * (ONE workgroup: minimum-label propagation with pointer jumping to the fixed point), own (one workgroup per m: a & ~b word by
+ * word over m's clipped box).  A word outside a view reads 0 and is never fetched.  All sums are int64 and order-free; no f32 or
+ * f64 on the device, no global atomics, plain vector stores.  Nothing outside points[0 .. point_off[M]), nborder, sums, links,
+ * degree, label and own is written.  M == 0: DEMIA_OK, nothing is touched.  No allocation, one stream, capturable. */
+int demia_mask_agglomerates(const uint32_t* masks, const int32_t* bbox, const int32_t* group /* [M] or NULL */, int64_t M, int H, int W,
+                            int64_t L2, const int64_t* point_off /* [M + 1] */, uint32_t* points, int32_t* nborder /* [M] */,
+                            int64_t* sums /* [M, 3] */, int have_border, uint32_t* links /* [M, ceil(M / 32)] */,
+                            int32_t* degree /* [M] */, int32_t* label /* [M] */, int64_t* own /* [M, 6] */, int label_lds_cap,
+                            void* stream);
+int demia_crop_agglomerates(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox,
+                            const int32_t* group /* [M] or NULL */, int64_t M, int H, int W, int64_t L2,
+                            const int64_t* point_off /* [M + 1] */, uint32_t* points, int32_t* nborder /* [M] */,
+                            int64_t* sums /* [M, 3] */, int have_border, uint32_t* links /* [M, ceil(M / 32)] */,
+                            int32_t* degree /* [M] */, int32_t* label /* [M] */, int64_t* own /* [M, 6] */, int label_lds_cap,
+                            void* stream);
+
 /* Evaluate task (COCO box / mask AP on a test split) ---------------------------------------------------------------------
  * poly_rasterize: pycocotools' frPyObjects + merge of polygons into packed masks [M, H, ceil(W/32)] (rleFrPoly's rule:
  *   x5 lattice, (int)(5c + .5), the y-boundary points of the edge walk, a pixel set iff an odd number of points lie at

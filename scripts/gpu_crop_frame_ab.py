@@ -7,7 +7,10 @@ full,crop,crop_direct), same models, same image, same box.  A frame written as `
 as ``<frame>+inscribed`` with `inference_settings.inscribed_descriptors: true`, one written as ``<frame>+skeleton`` with
 `inference_settings.skeleton_descriptors: true` -- any family of `maskset.FAMILIES`; several suffixes may follow one frame.  The suffix
 ``+neighbours`` runs with `inference_settings.neighbour_statistics: true` (the neighbour stage of `measure_image`; a radius of 50
-pixels): its rows are counted and digested apart (`neighbour_rows`, `neighbour_rows_sha256`).
+pixels): its rows are counted and digested apart (`neighbour_rows`, `neighbour_rows_sha256`).  The suffix ``+agglomerates`` runs with
+`inference_settings.agglomerate_statistics: true` (the agglomerate stage of `measure_image`, touching links across classes): its rows
+are counted and digested apart too, with the number of components and the largest; ``+neighbours+agglomerates`` runs both, the second
+on the first's border points (one border launch per image).
 
 Per frame: the first image's time and the steady-state times apart (host clock around work that ends in a device synchronise; the
 forwards are re-run every repetition, as a folder of such images would), the peak device memory of a repetition
@@ -60,8 +63,9 @@ pred = Predictor(MaskRCNNEngine(sds[101], 101, len(T.CLASSES), 0.3, dev, "f16x2"
 spatial_cfg = load_spatial_constraints(T.DATASET)
 metadata = types.SimpleNamespace(thing_classes=T.CLASSES)
 pipes = {f: I.InferencePipeline([pred], T.DATASET, dict(st.inf, mask_frame=f.split("+")[0]), st.global_config) for f in frames}
-descriptors = {f: tuple(fam.name for fam in families([x for x in f.split("+")[1:] if x != "neighbours"])) for f in frames}      # (an unknown suffix: ValueError)
+descriptors = {f: tuple(fam.name for fam in families([x for x in f.split("+")[1:] if x not in ("neighbours", "agglomerates")])) for f in frames}      # (an unknown suffix: ValueError)
 neighbours = {f: "neighbours" in f.split("+")[1:] for f in frames}
+agglomerates = {f: "agglomerates" in f.split("+")[1:] for f in frames}
 NEIGHBOUR_RADIUS = 50.0
 host_copies = [0]
 for _name in ("cpu", "item"):
@@ -79,8 +83,8 @@ small = I.determine_small_classes(pipes[frames[0]].calculate_average_mask_sizes(
 pipes[frames[0]].drop_cached("big.tif")
 
 
-def one_image(pipe, descriptors=(), with_neighbours=False):
-    """process_image of run_inference for this image: instances, RLE texts, measurement rows (and the neighbour rows)."""
+def one_image(pipe, descriptors=(), with_neighbours=False, with_agglomerates=False):
+    """process_image of run_inference for this image: instances, RLE texts, measurement rows (and the neighbour / agglomerate rows)."""
     name = "big.tif"
     pipe.begin_image_stats()
     packed, scores, classes, tabs = I.final_instances(pipe, st, name, image_dev, small, len(T.CLASSES), spatial_cfg, I.image_phases_enabled(pipe))
@@ -93,16 +97,22 @@ def one_image(pipe, descriptors=(), with_neighbours=False):
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
     stage = I.NeighbourStage(NEIGHBOUR_RADIUS) if with_neighbours else None
+    agg = I.AgglomerateStage() if with_agglomerates else None
     rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors, neighbours=stage)
+                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors, neighbours=stage,
+                           agglomerates=agg)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     if with_neighbours and pipe.crop:      # (a crop-framed set is a few MiB: keeping it does not move the next repetition's peak)
         last_set[pipe.mask_frame] = (pipe, packed, classes, tabs)
+    if with_agglomerates and pipe.crop:
+        last_agg[pipe.mask_frame] = (pipe, packed, classes, tabs)
     pipe.drop_cached(name)
-    return n, rows, texts, pipe.end_image_stats((size, size)), (stage.rows if stage is not None else None)
+    return n, rows, texts, pipe.end_image_stats((size, size)), (stage.rows if stage is not None else None), (agg.rows if agg is not None else None)
 
 
 last_set = {}                        # crop frame -> the final set of the last image measured with +neighbours
+last_agg = {}                        # ... and with +agglomerates
+digest_ag = {}
 runs = {f: [] for f in pipes}
 digest, digest_all, digest_nb = {}, {}, {}          # per frame: texts + the 20 reference columns; ALL columns of the rows; the neighbour rows
 for rep in range(reps):
@@ -111,7 +121,7 @@ for rep in range(reps):
         torch.cuda.reset_peak_memory_stats()
         w0, c0, f0 = pipe.d2h_waits, host_copies[0], fallbacks[0]
         t0 = time.perf_counter()
-        n, rows, texts, stats, nrows = one_image(pipe, descriptors[frame], neighbours[frame])
+        n, rows, texts, stats, nrows, arows = one_image(pipe, descriptors[frame], neighbours[frame], agglomerates[frame])
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert all(len(r) == 20 + sum(len(I.DESCRIPTOR_CSV[name][0]) for name in descriptors[frame]) for r in rows)
@@ -121,15 +131,20 @@ for rep in range(reps):
         digest_all.setdefault(frame, h_all)
         h_nb = None if nrows is None else hashlib.sha256(repr(nrows).encode()).hexdigest()
         digest_nb.setdefault(frame, h_nb)
-        assert digest[frame] == h and digest_all[frame] == h_all and digest_nb[frame] == h_nb, "a repetition wrote other rows"
+        h_ag = None if arows is None else hashlib.sha256(repr(arows).encode()).hexdigest()
+        digest_ag.setdefault(frame, h_ag)
+        assert digest[frame] == h and digest_all[frame] == h_all and digest_nb[frame] == h_nb and digest_ag[frame] == h_ag, "a repetition wrote other rows"
         runs[frame].append(dict(seconds=dt, peak_bytes=int(torch.cuda.max_memory_allocated()), d2h_waits=pipe.d2h_waits - w0,
                                 host_copies=host_copies[0] - c0, fetch_fallbacks=fallbacks[0] - f0, instances=n,
-                                rows=len(rows), neighbour_rows=None if nrows is None else len(nrows), full_frame_planes_peak=stats["full_frame_planes_peak"]))
+                                rows=len(rows), neighbour_rows=None if nrows is None else len(nrows),
+                                agglomerate_rows=None if arows is None else len(arows), largest_agglomerate=None if not arows else max(r[1] for r in arows),
+                                full_frame_planes_peak=stats["full_frame_planes_peak"]))
         print(f"rep {rep} {frame:11s}: {dt:.3f} s, {n} instances, {len(rows)} rows, peak {torch.cuda.max_memory_allocated() / 2**30:.2f} GiB, "
               f"{pipe.d2h_waits - w0} waits, {host_copies[0] - c0} device-to-host copies ({fallbacks[0] - f0} fetch fallbacks), {stats['full_frame_planes_peak']} planes", flush=True)
 
 res = {"image": f"{size}x{size}", "tiles": k * k, "tile": tile, "model": "R101 f16x2", "reps_per_frame": reps, "order": "alternating " + ", ".join(frames),
-       "same_rows_and_texts": len(set(digest.values())) == 1, "same_neighbour_rows": len({v for v in digest_nb.values() if v is not None}) <= 1, "device": torch.cuda.get_device_name(0), "frames": {}}
+       "same_rows_and_texts": len(set(digest.values())) == 1, "same_neighbour_rows": len({v for v in digest_nb.values() if v is not None}) <= 1,
+       "same_agglomerate_rows": len({v for v in digest_ag.values() if v is not None}) <= 1, "device": torch.cuda.get_device_name(0), "frames": {}}
 for frame, rr in runs.items():
     steady = [r["seconds"] for r in rr[1:]]
     res["frames"][frame] = dict(first_image_seconds=rr[0]["seconds"], steady_seconds=steady,
@@ -139,6 +154,8 @@ for frame, rr in runs.items():
                                 d2h_waits_per_image=rr[-1]["d2h_waits"], host_copies_per_image=rr[-1]["host_copies"], fetch_fallbacks_per_image=rr[-1]["fetch_fallbacks"], instances=rr[-1]["instances"], rows=rr[-1]["rows"],
                                 rows20_texts_sha256=digest[frame], rows_sha256=digest_all[frame],
                                 neighbour_rows=rr[-1]["neighbour_rows"], neighbour_rows_sha256=digest_nb[frame],
+                                agglomerate_rows=rr[-1]["agglomerate_rows"], largest_agglomerate=rr[-1]["largest_agglomerate"],
+                                agglomerate_rows_sha256=digest_ag[frame],
                                 full_frame_planes_peak=max(r["full_frame_planes_peak"] for r in rr))
 
 
@@ -173,8 +190,43 @@ def stage_alone(frame):
     return out
 
 
+def agglomerate_stage_alone(frame):
+    """The agglomerate stage by itself on the last final set of ``frame``: device time (events, 5 runs, the median) of its four
+    launches, of the three behind a neighbour stage's border points, and of all four with the masks of the longest borders or of the
+    most links left out -- a launch that ends on one slow workgroup gets much shorter without it."""
+    pipe, packed, classes, tabs = last_agg[frame]
+    area = np.asarray(tabs[0])
+
+    def timed(keep, border=False):
+        sub = packed if keep is None else packed.select(keep)
+        a = area if keep is None else area[keep]
+        nb = sub.neighbours(area=a, r2=-1) if border else None
+        ms = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            ag = sub.agglomerates(area=a, l2=2, border=nb)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), ag
+    t_all, ag = timed(None)
+    nborder, degree, label = (t.cpu().numpy().astype(np.int64) for t in (ag.nborder, ag.degree, ag.label))
+    sizes = np.bincount(label[label >= 0])
+    out = dict(masks=int(len(label)), device_ms_all=t_all, device_ms_border_reused=timed(None, border=True)[0], components=int((sizes > 0).sum()),
+               largest_component=int(sizes.max()), singletons=int((sizes == 1).sum()), links=int(degree.sum() // 2), degree_max=int(degree.max()),
+               border_points_max=int(nborder.max()), link_matrix_bytes=int(ag.links.numel() * 4))
+    for what, order in (("longest_borders", np.argsort(-nborder, kind="stable")), ("most_linked", np.argsort(-degree, kind="stable"))):
+        for drop in (1, 8):
+            out[f"device_ms_without_{drop}_{what}"] = timed(np.sort(order[drop:]))[0]
+    return out
+
+
 if last_set:
     res["neighbour_stage_alone"] = {f: stage_alone(f) for f in last_set}
+if last_agg:
+    res["agglomerate_stage_alone"] = {f: agglomerate_stage_alone(f) for f in last_agg}
 out_path.parent.mkdir(parents=True, exist_ok=True)
 out_path.write_text(json.dumps(res, indent=1))
 print(json.dumps(res))
