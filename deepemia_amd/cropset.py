@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, PlanePool, _agglomerate_buffers, _neighbour_buffers,
+from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, PlanePool, _launch_agglomerates, _launch_neighbours,
                       reads_words)
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
@@ -455,12 +455,7 @@ class CropMaskSet:
         H, W = self.hw
         if area is None:
             area = self.area.cpu().numpy() if M else np.zeros(0)
-        res, group_d, off_d = _neighbour_buffers(ops, M, area, group)
-        _lib.check(ops.lib.demia_crop_neighbours(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
-                                                 _lib.ptr(group_d), M, H, W, int(r2), _lib.ptr(off_d), _lib.ptr(res.points),
-                                                 _lib.ptr(res.nborder), _lib.ptr(res.sums), _lib.ptr(res.table), ops._stream()),
-                   "demia_crop_neighbours")
-        return res
+        return _launch_neighbours(ops, "demia_crop_neighbours", (self.payload, self.room, self.offsets, self.bbox), M, H, W, area, group, r2)
 
     def agglomerates(self, area=None, group=None, l2: int = 2, border: Optional[Neighbours] = None, label_lds_cap: int = 0) -> Agglomerates:
         """``MaskOps.agglomerates`` on the words in place (``demia_crop_agglomerates``): the same tensors, no plane, no wait.
@@ -470,13 +465,8 @@ class CropMaskSet:
         H, W = self.hw
         if area is None and border is None:
             area = self.area.cpu().numpy() if M else np.zeros(0)
-        res, group_d, off_d = _agglomerate_buffers(ops, M, area, group, border)
-        _lib.check(ops.lib.demia_crop_agglomerates(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(self.bbox),
-                                                   _lib.ptr(group_d), M, H, W, int(l2), _lib.ptr(off_d), _lib.ptr(res.points),
-                                                   _lib.ptr(res.nborder), _lib.ptr(res.sums), int(border is not None), _lib.ptr(res.links),
-                                                   _lib.ptr(res.degree), _lib.ptr(res.label), _lib.ptr(res.own), int(label_lds_cap),
-                                                   ops._stream()), "demia_crop_agglomerates")
-        return res
+        return _launch_agglomerates(ops, "demia_crop_agglomerates", (self.payload, self.room, self.offsets, self.bbox), M, H, W, area, group,
+                                    l2, border, label_lds_cap)
 
     def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
         """``MaskOps.gray_histogram`` on the words in place (``demia_crop_gray_histogram``): [M, 256] gray-level counts."""

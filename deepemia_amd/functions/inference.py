@@ -22,7 +22,7 @@ import os
 import threading
 import time
 from pathlib import Path
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -338,6 +338,22 @@ def descriptors_setting(inf_settings: dict) -> Tuple[str, ...]:
     return tuple(on)
 
 
+# ---- the per-image statistics stages, each stated once, down to their table IMAGE_STATISTICS and the writers under the old names;
+# ---- nothing outside this block names a stage
+
+def _switch_and_length(inf_settings: dict, switch: str, length: str) -> Tuple[bool, Optional[float]]:
+    """A stage's bool switch (default false) and its optional length, a finite number >= 0 in the CSV's length unit."""
+    value = (inf_settings or {}).get(switch, False)
+    if not isinstance(value, bool):
+        raise ValueError(f"inference_settings.{switch} must be true or false, got {value!r}")
+    x = (inf_settings or {}).get(length, None)
+    if x is not None:
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+            raise ValueError(f"inference_settings.{length} must be a finite number >= 0, got {x!r}")
+        x = float(x)
+    return value, x
+
+
 NEIGHBOUR_CSV_HEADER = ["Instance_ID", "Class", "Class_Name", "Pixels", "Centroid x", "Centroid y", "Nearest neighbour", "Nearest distance",
                         "Nearest same-class neighbour", "Nearest same-class distance", "Touching neighbours", "Neighbours within radius",
                         "Detected scale bar", "File name"]
@@ -355,15 +371,7 @@ def neighbours_setting(inf_settings: dict) -> NeighbourSetting:
     ``inference_settings.neighbour_radius`` (optional): the radius of the "Neighbours within radius" count, in the CSV's length
     unit; unset leaves the column empty.  Anything but a bool, and a radius that is not a finite number >= 0, is a configuration
     error."""
-    value = (inf_settings or {}).get("neighbour_statistics", False)
-    if not isinstance(value, bool):
-        raise ValueError(f"inference_settings.neighbour_statistics must be true or false, got {value!r}")
-    radius = (inf_settings or {}).get("neighbour_radius", None)
-    if radius is not None:
-        if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius < 0:
-            raise ValueError(f"inference_settings.neighbour_radius must be a finite number >= 0, got {radius!r}")
-        radius = float(radius)
-    return NeighbourSetting(value, radius)
+    return NeighbourSetting(*_switch_and_length(inf_settings, "neighbour_statistics", "neighbour_radius"))
 
 
 def neighbour_r2(radius: Optional[float], um_pix: float) -> int:
@@ -373,12 +381,13 @@ def neighbour_r2(radius: Optional[float], um_pix: float) -> int:
     return int(math.floor((radius / um_pix) ** 2))
 
 
-class NeighbourStage:
-    """The neighbour stage of one image as ``measure_image`` runs it: the caller states the radius, ``rows`` comes back."""
+def _neighbours_launch(source, classes, um_pix: float, setting: NeighbourSetting, area, border) -> Neighbours:
+    # source: the image's masks (``_MeasuredMasks``); area: the pixel counts on the host or None; border: the result of the stage before
+    return source.statistic("neighbours", area, group=np.asarray(classes, dtype=np.int32), r2=neighbour_r2(setting.radius, um_pix))
 
-    def __init__(self, radius: Optional[float] = None):
-        self.radius = radius
-        self.rows: List[list] = []
+
+def _neighbours_decode(image_name: str, classes, thing_classes, ride_host, um_pix: float, psum: str, area, result) -> List[list]:
+    return neighbour_rows(image_name, classes, thing_classes, *Neighbours.from_i32(*ride_host), um_pix, psum)
 
 
 def neighbour_rows(image_name: str, classes: Sequence[int], thing_classes, table: np.ndarray, sums: np.ndarray, um_pix: float,
@@ -401,18 +410,6 @@ def neighbour_rows(image_name: str, classes: Sequence[int], thing_classes, table
     return rows
 
 
-def write_neighbours(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
-    """``neighbours_results.csv``: the header and every image's rows of ``neighbour_rows``, in the images' order."""
-    path = os.path.join(output_dir, "neighbours_results.csv")
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow(NEIGHBOUR_CSV_HEADER)
-        for name in image_names:
-            for r in rows_by_image.get(name, []):
-                w.writerow(r)
-    return path
-
-
 AGGLOMERATE_CSV_HEADER = ["Agglomerate_ID", "Members", "Member ids", "Class counts", "Links", "Mean coordination", "Pixels", "Member pixels",
                           "Centroid x", "Centroid y", "Equivalent diameter", "Radius of gyration", "Major extent", "Minor extent", "Orientation",
                           "Detected scale bar", "File name"]
@@ -433,14 +430,7 @@ def agglomerates_setting(inf_settings: dict) -> AgglomerateSetting:
     CSV's length unit; unset (and anything below touching) is touching, 8-connected contact or overlap.
     ``inference_settings.agglomerate_link``: ``"any"`` (the default) links across classes, ``"same_class"`` only within one.
     Anything but a bool, a gap that is not a finite number >= 0 and any other link value are configuration errors."""
-    value = (inf_settings or {}).get("agglomerate_statistics", False)
-    if not isinstance(value, bool):
-        raise ValueError(f"inference_settings.agglomerate_statistics must be true or false, got {value!r}")
-    gap = (inf_settings or {}).get("agglomerate_gap", None)
-    if gap is not None:
-        if isinstance(gap, bool) or not isinstance(gap, (int, float)) or not math.isfinite(gap) or gap < 0:
-            raise ValueError(f"inference_settings.agglomerate_gap must be a finite number >= 0, got {gap!r}")
-        gap = float(gap)
+    value, gap = _switch_and_length(inf_settings, "agglomerate_statistics", "agglomerate_gap")
     link = (inf_settings or {}).get("agglomerate_link", "any")
     if not isinstance(link, str) or link not in AGGLOMERATE_LINKS:
         raise ValueError(f"inference_settings.agglomerate_link must be one of {', '.join(AGGLOMERATE_LINKS)}, got {link!r}")
@@ -454,12 +444,16 @@ def agglomerate_l2(gap: Optional[float], um_pix: float) -> int:
     return max(2, int(math.floor((gap / um_pix) ** 2)))
 
 
-class AgglomerateStage:
-    """The agglomerate stage of one image as ``measure_image`` runs it: the caller states gap and link, ``rows`` comes back."""
+def _agglomerates_launch(source, classes, um_pix: float, setting: AgglomerateSetting, area, border) -> Agglomerates:
+    # ``border``: the neighbour stage's result when that stage ran on this image -- its border points are reused
+    group = np.asarray(classes, dtype=np.int32) if setting.link == "same_class" else None
+    return source.statistic("agglomerates", area, group=group, l2=agglomerate_l2(setting.gap, um_pix), border=border)
 
-    def __init__(self, gap: Optional[float] = None, link: str = "any"):
-        self.gap, self.link = gap, link
-        self.rows: List[list] = []
+
+def _agglomerates_decode(image_name: str, classes, thing_classes, ride_host, um_pix: float, psum: str, area, result) -> List[list]:
+    if area is None:          # (a caller outside the pipeline: the border stage's counts, with a wait of their own)
+        area = result.sums[:, 0].cpu().numpy()
+    return agglomerate_rows(image_name, classes, thing_classes, *Agglomerates.from_i32(*ride_host), area, um_pix, psum)
 
 
 def agglomerate_rows(image_name: str, classes: Sequence[int], thing_classes, label: np.ndarray, degree: np.ndarray, own: np.ndarray,
@@ -494,16 +488,82 @@ def agglomerate_rows(image_name: str, classes: Sequence[int], thing_classes, lab
     return rows
 
 
-def write_agglomerates(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
-    """``agglomerates_results.csv``: the header and every image's rows of ``agglomerate_rows``, in the images' order."""
-    path = os.path.join(output_dir, "agglomerates_results.csv")
+class ImageStatistic(NamedTuple):
+    """One opt-in per-image statistics stage on the final instances: all that ``PipelineSettings``, ``measure_image``, the
+    exchange between image-sharded ranks and the output section know of it.  ``launch`` and ``decode``: as ``_neighbours_launch``
+    and ``_neighbours_decode``; a launch is enqueued without a wait and its result's int32 tensors for the trace's fetch are
+    ``result.ride``, of which ``decode`` gets the host arrays."""
+    name: str                # key of ``PipelineSettings.statistics`` and of every ``{stage name: ...}`` dict
+    key: str                 # the switch, ``inference_settings.<key>``
+    setting: Callable        # inference_settings -> the parsed setting, with ``.enabled``; a bad value raises ValueError
+    filename: str            # its CSV in the output folder
+    header: List[str]
+    launch: Callable
+    decode: Callable
+
+
+# in the order the stages are launched and their tensors ride: the agglomerate stage reuses the neighbour stage's border points
+IMAGE_STATISTICS = {s.name: s for s in (
+    ImageStatistic("neighbours", "neighbour_statistics", neighbours_setting, "neighbours_results.csv", NEIGHBOUR_CSV_HEADER,
+                   _neighbours_launch, _neighbours_decode),
+    ImageStatistic("agglomerates", "agglomerate_statistics", agglomerates_setting, "agglomerates_results.csv", AGGLOMERATE_CSV_HEADER,
+                   _agglomerates_launch, _agglomerates_decode),
+)}
+
+
+def write_statistic(output_dir: str, stage: ImageStatistic, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
+    """The CSV of one stage: its header and every image's rows, in the images' order."""
+    path = os.path.join(output_dir, stage.filename)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(AGGLOMERATE_CSV_HEADER)
+        w.writerow(stage.header)
         for name in image_names:
             for r in rows_by_image.get(name, []):
                 w.writerow(r)
     return path
+
+
+def write_neighbours(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
+    return write_statistic(output_dir, IMAGE_STATISTICS["neighbours"], image_names, rows_by_image)
+
+
+def write_agglomerates(output_dir: str, image_names: Sequence[str], rows_by_image: Dict[str, List[list]]) -> str:
+    return write_statistic(output_dir, IMAGE_STATISTICS["agglomerates"], image_names, rows_by_image)
+
+
+def statistics_setting(inf_settings: dict) -> Dict[str, NamedTuple]:
+    """``{stage name: parsed setting}`` of every entry of ``IMAGE_STATISTICS``, enabled or not."""
+    return {s.name: s.setting(inf_settings) for s in IMAGE_STATISTICS.values()}
+
+
+def enabled_statistics(statistics: Optional[Dict[str, NamedTuple]]) -> List[Tuple[ImageStatistic, NamedTuple]]:
+    """The enabled stages of ``statistics`` (``{stage name: setting}``) with their settings, in table order."""
+    return [(s, statistics[s.name]) for s in IMAGE_STATISTICS.values() if s.name in (statistics or {}) and statistics[s.name].enabled]
+
+
+def take_rides(ride_host: Sequence[np.ndarray], n_extra: int, lengths: Sequence[Tuple[str, int]]) -> Dict[str, List[np.ndarray]]:
+    """The host arrays of a fetched ride by stage: behind the caller's ``n_extra`` arrays, each stage's ``len(result.ride)`` arrays
+    (``lengths``: ``(stage name, count)``) in launch order."""
+    out, at = {}, n_extra
+    for name, n in lengths:
+        out[name] = list(ride_host[at:at + n])
+        at += n
+    assert at == len(ride_host), (at, len(ride_host))
+    return out
+
+
+def merge_statistic_rows(into: Dict[str, Dict[str, List[list]]], other: Dict[str, Dict[str, List[list]]]) -> Dict[str, Dict[str, List[list]]]:
+    """``{stage name: {image: rows}}`` of another rank merged into this one's, by stage name: the images are disjoint."""
+    for name, rows_by_image in other.items():
+        into.setdefault(name, {}).update(rows_by_image)
+    return into
+
+
+def write_statistics(output_dir: str, statistics: Dict[str, NamedTuple], image_names: Sequence[str],
+                     statistic_rows_by_image: Dict[str, Dict[str, List[list]]]) -> List[str]:
+    """One CSV per enabled stage, in table order (``write_statistic``); a stage that is off writes nothing."""
+    return [write_statistic(output_dir, stage, image_names, statistic_rows_by_image.get(stage.name, {}))
+            for stage, _ in enabled_statistics(statistics)]
 
 
 DETECTIONS_PER_IMAGE_MAX = 1000
@@ -2320,10 +2380,12 @@ class PipelineSettings:
         self.rank_exchange = rank_exchange_setting(inf)
         self.detections_per_image = detections_per_image_setting(inf)     # (the model loader reads it too: a bad value ends the run here)
         self.descriptors = descriptors_setting(inf)
-        self.neighbours = neighbours_setting(inf)
-        self.agglomerates = agglomerates_setting(inf)
+        self.statistics = statistics_setting(inf)
         # what the evaluate task's pipeline mode scores (evaluate_model.score_frame_setting validates it there; inference never reads it)
         self.score_frame = str((dataset_config.get("evaluation", {}) or {}).get("score_frame", "planes")).strip().lower()
+
+    neighbours = property(lambda self: self.statistics["neighbours"])          # (read by name outside this module only)
+    agglomerates = property(lambda self: self.statistics["agglomerates"])
 
     def target_classes(self, num_classes: int) -> List[int]:
         return list(range(num_classes) if self.classes_to_infer is None else [c for c in self.classes_to_infer if c < num_classes])
@@ -2540,8 +2602,7 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
 
     rle_by_image: Dict[str, List[str]] = {}       # per image the EncodedPixels texts of its final instances (a16)
     rows_by_image: Dict[str, List[list]] = {}     # per image its measurement rows (a17-a19), measured while the image is still resident
-    neighbour_rows_by_image: Dict[str, List[list]] = {}      # ... and, with neighbour_statistics, its rows of neighbours_results.csv
-    agglomerate_rows_by_image: Dict[str, List[list]] = {}    # ... and, with agglomerate_statistics, of agglomerates_results.csv
+    statistic_rows_by_image: Dict[str, Dict[str, List[list]]] = {}      # ... and, per enabled stage of IMAGE_STATISTICS, its rows of that CSV
     keep_masks = os.environ.get("DEEPEMIA_KEEP_MASKS", "0") == "1"
     dedup_results: Dict[str, dict] = {}
     processed = set()
@@ -2672,16 +2733,12 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                 else:
                     crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n_final else None
                 extra = [crop[0]] if crop is not None else None
-                stage = NeighbourStage(st.neighbours.radius) if st.neighbours.enabled else None
-                agg = AgglomerateStage(st.agglomerates.gap, st.agglomerates.link) if st.agglomerates.enabled else None
-                rows_by_image[name] = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name, draw_scalebar,
-                                                    visualize, image_dev=image_dev, extra=extra, note_planes=pipe._note_planes,
-                                                    crop_direct=pipe.crop_direct, descriptors=st.descriptors, neighbours=stage,
-                                                    agglomerates=agg)
-                if stage is not None:
-                    neighbour_rows_by_image[name] = stage.rows
-                if agg is not None:
-                    agglomerate_rows_by_image[name] = agg.rows
+                rows_by_image[name], stat_rows = measure_image(pipe.ops, name, result, inpath, output_dir, metadata, dataset_name,
+                                                               draw_scalebar, visualize, image_dev=image_dev, extra=extra,
+                                                               note_planes=pipe._note_planes, crop_direct=pipe.crop_direct,
+                                                               descriptors=st.descriptors, statistics=st.statistics)
+                for stage, rows in stat_rows.items():
+                    statistic_rows_by_image.setdefault(stage, {})[name] = rows
                 if crop is not None:
                     texts = rle_text_from_payload(extra[0], crop[1], crop[2], int(packed.shape[1]))
             elif n_final and pipe.crop:
@@ -2753,16 +2810,15 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
                        f"{total / max(len(my_images), 1):.4f}s/image, {pipe.forward_calls} batched forwards")
     if shard_images:
         # the ONE exchange of the image-sharded job: every rank's rows and texts go to rank 0, which writes the files
-        mine = (rle_by_image, (rows_by_image, neighbour_rows_by_image, agglomerate_rows_by_image),
+        mine = (rle_by_image, rows_by_image, statistic_rows_by_image,
                 {k: {kk: vv for kk, vv in v.items() if kk != "masks"} for k, v in dedup_results.items()}, sorted(processed))
         gathered = [None] * job_world
         dist.all_gather_object(gathered, mine)         # (an all-gather: the object collective every backend, RCCL included, supports)
         if job_rank == 0:
-            for r_rle, (r_rows, r_nrows, r_arows), r_res, r_done in gathered[1:]:
+            for r_rle, r_rows, r_stat_rows, r_res, r_done in gathered[1:]:
                 rle_by_image.update(r_rle)
                 rows_by_image.update(r_rows)
-                neighbour_rows_by_image.update(r_nrows)
-                agglomerate_rows_by_image.update(r_arows)
+                merge_statistic_rows(statistic_rows_by_image, r_stat_rows)
                 for k, v in r_res.items():
                     dedup_results.setdefault(k, dict(v, masks=None))
                 processed.update(r_done)
@@ -2781,12 +2837,8 @@ def run_inference(dataset_name, output_dir, visualize=True, threshold=0.65, draw
 
         write_measurements(pipe.ops, dedup_results, inpath, output_dir, metadata, dataset_name, draw_scalebar, visualize,
                            rows_by_image=rows_by_image, crop_direct=pipe.crop_direct, descriptors=st.descriptors,
-                           neighbours=st.neighbours, neighbour_rows_by_image=neighbour_rows_by_image,
-                           agglomerates=st.agglomerates, agglomerate_rows_by_image=agglomerate_rows_by_image)
-        if st.neighbours.enabled:
-            write_neighbours(output_dir, images_name, neighbour_rows_by_image)
-        if st.agglomerates.enabled:
-            write_agglomerates(output_dir, images_name, agglomerate_rows_by_image)
+                           statistics=st.statistics, statistic_rows_by_image=statistic_rows_by_image)
+        write_statistics(output_dir, st.statistics, images_name, statistic_rows_by_image)
         with open(os.path.join(output_dir, "class_color_legend.txt"), "w") as f:
             f.write("Class Color Legend (BGR)\n")
             for i, cname in enumerate(metadata.thing_classes):
@@ -2918,19 +2970,59 @@ def measurement_csv_text(tiles, thing_classes, min_area: float, psum: str = "0")
     return "".join(h + f + t for h, f, t in zip(heads, floats, tails))
 
 
+class _MeasuredMasks:
+    """The final masks of one image as ``measure_image`` reads them, whatever their frame: full-frame planes (``bbox``: their tight
+    boxes on the device when the caller has them on the host), a crop-framed set through the plane pool, or that set's words in
+    place (``direct``).  ``area``: the pixel counts on the host, if known."""
+
+    def __init__(self, ops: MaskOps, data: dict, crop_direct: bool):
+        self.ops, self.packed, self.hw, self.area = ops, data["masks"], data["hw"], data.get("area")
+        self.crop = isinstance(self.packed, CropMaskSet)
+        self.direct = self.crop and crop_direct
+        self.bbox = None
+        if not self.crop and data.get("bbox") is not None:
+            self.bbox = ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32))
+
+    def contours(self, um_pix: float, descriptors: Sequence[str], ride: Optional[list]):
+        """(contour records per mask, the host arrays of ``ride`` or None): ``ride`` comes over in the trace's own copy."""
+        kw = dict(um_pix=um_pix, extra=ride, descriptors=descriptors)
+        if self.direct:          # traced and measured on its words in place: one trace, one fetch, no plane
+            got = self.packed.contours(max_contours=256, total_area=None if self.area is None else int(np.sum(self.area)), **kw)
+        elif self.crop:          # the same trace + measurements, a chunk of the plane pool at a time
+            return crop_contours(self.packed, crop_planes(self.ops, self.hw), total_area=self.area, **kw)
+        elif self.bbox is not None:      # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
+            got = self.ops.contours(self.packed, max_contours=256, bbox=self.bbox, total_area=int(np.sum(self.area)), **kw)
+        else:                    # (a caller outside the pipeline: ``ride`` is fetched with a wait of its own)
+            recs = self.ops.contours(self.packed, max_contours=256, um_pix=um_pix, descriptors=descriptors)
+            return recs, (None if ride is None else [e.cpu().numpy() for e in ride])
+        return got if ride is not None else (got, None)
+
+    def gray_histogram(self, image: torch.Tensor) -> np.ndarray:
+        if self.direct:
+            return self.packed.gray_histogram(image)
+        return crop_gray_histogram(self.packed, crop_planes(self.ops, self.hw), image) if self.crop else self.ops.gray_histogram(self.packed, image)
+
+    def host_crops(self):
+        return self.packed.host_crops() if self.crop else mask_crops(self.ops, self.packed)
+
+    def statistic(self, method: str, area, **kw):
+        """The launch hook of the stages of ``IMAGE_STATISTICS``: ``CropMaskSet.<method>`` or ``MaskOps.<method>``."""
+        if self.crop:
+            return getattr(self.packed, method)(area=area, **kw)
+        return getattr(self.ops, method)(self.packed, self.bbox, area if self.bbox is not None else None, **kw)
+
+
 def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, output_dir: str, metadata, dataset_name: str,
                   draw_scalebar: bool = False, visualize: bool = False, image_dev: Optional[torch.Tensor] = None,
                   extra: Optional[list] = None, note_planes=None, crop_direct: bool = False,
-                  descriptors: Sequence[str] = (), neighbours: Optional[NeighbourStage] = None,
-                  agglomerates: Optional[AgglomerateStage] = None) -> List[list]:
+                  descriptors: Sequence[str] = (), statistics: Optional[Dict[str, NamedTuple]] = None) -> Tuple[List[list], Dict[str, List[list]]]:
     """The measurement phase of ONE image (``inference.py:1030-1291``): scale bar, contours + the 12 measurements of every final
-    mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns the image's CSV rows.
-    ``neighbours``: the neighbour stage (``neighbours_setting``) runs on the same final set with the scale detected here; it is
-    enqueued before the trace's fetch and its two tables ride in that fetch's copy, so it adds no wait; its rows of
-    ``neighbours_results.csv`` come back in ``neighbours.rows``.
-    ``agglomerates``: the agglomerate stage (``agglomerates_setting``) likewise, behind the neighbour stage, whose border points it
-    reuses when both are on; its three small tables ride in the same copy and its rows of ``agglomerates_results.csv`` come back
-    in ``agglomerates.rows``.
+    mask, optional contrast percentiles, optional overlay / scale-bar debug images; returns (the image's CSV rows, ``{stage name:
+    rows}`` of the statistics stages that ran -- empty without any).
+    ``statistics``: ``{stage name: setting}`` (``statistics_setting``); the enabled stages of ``IMAGE_STATISTICS`` run in table
+    order on the same final set with the scale detected here.  Each is enqueued before the trace's fetch, gets the result of the
+    one before it (whose border points it may reuse) and its small tables (``result.ride``) ride in that fetch's copy, so it adds
+    no wait; an image without masks yields ``[]`` for each.
     ``image_dev``: the decoded image when the caller still holds it on the device (the image loop does: the reference re-reads
     the file here, which gives the same bytes).  ``crop_direct``: a crop-framed set is traced, measured and histogrammed on its
     words in place (``mask_frame: crop_direct``) instead of through the plane pool.  ``descriptors``: the contour records, and
@@ -2958,105 +3050,55 @@ def measure_image(ops: MaskOps, test_img: str, data: dict, test_img_path: str, o
     else:
         psum, um_pix = detect_scale_bar(im, roi_config=None, dataset_name=dataset_name)
     packed, classes = data["masks"], data["classes"]
-    if neighbours is not None:
-        neighbours.rows = []
-    if agglomerates is not None:
-        agglomerates.rows = []
+    on = enabled_statistics(statistics)
+    stat_rows: Dict[str, List[list]] = {stage.name: [] for stage, _ in on}
     if packed is None or packed.shape[0] == 0:
-        return []
+        return [], stat_rows
     h, wd = data["hw"]
     ops.set_frame_width(wd)
     min_area = max(5, h * wd * 0.000005 * 0.05)
-    crop = isinstance(packed, CropMaskSet)
-    direct = crop and crop_direct
-    if note_planes is not None and not direct:
-        note_planes(crop_planes(ops, (h, wd)).cap if crop else 2 * int(packed.shape[0]))      # (the masks + the trace's scratch planes)
-    bbox_dev = None
-    if not crop and data.get("bbox") is not None:
-        bbox_dev = ops.upload(np.ascontiguousarray(data["bbox"], dtype=np.int32))
+    masks = _MeasuredMasks(ops, data, crop_direct)
+    if note_planes is not None and not masks.direct:
+        note_planes(crop_planes(ops, (h, wd)).cap if masks.crop else 2 * int(packed.shape[0]))      # (the masks + the trace's scratch planes)
     # ``ride``: the int32 device tensors that come to the host in the trace's own copy -- the caller's ``extra`` (the cropped words of
-    # the RLE texts; replaced in place by their host arrays) and, behind them, the two tables of the neighbour stage and the three
-    # of the agglomerate stage
-    ride = extra
-    nb = None
-    if neighbours is not None:
-        group = np.asarray(classes, dtype=np.int32)
-        r2 = neighbour_r2(neighbours.radius, um_pix)
-        if crop:
-            nb = packed.neighbours(area=data.get("area"), group=group, r2=r2)
-        else:
-            nb = ops.neighbours(packed, bbox_dev, data.get("area") if bbox_dev is not None else None, group=group, r2=r2)
-        ride = list(extra or []) + [nb.table_i32, nb.sums_i32]
-    if agglomerates is not None:
-        grp = np.asarray(classes, dtype=np.int32) if agglomerates.link == "same_class" else None
-        l2 = agglomerate_l2(agglomerates.gap, um_pix)
-        if crop:
-            ag = packed.agglomerates(area=data.get("area"), group=grp, l2=l2, border=nb)
-        else:
-            ag = ops.agglomerates(packed, bbox_dev, data.get("area") if bbox_dev is not None else None, group=grp, l2=l2, border=nb)
-        ride = list(ride or []) + ag.ride
-    if direct:
-        # a crop-framed set traced and measured on its words in place: one trace, one fetch, no plane
-        area_h = data.get("area")
-        recs = packed.contours(max_contours=256, um_pix=um_pix, total_area=None if area_h is None else int(np.sum(area_h)), extra=ride,
-                               descriptors=descriptors)
-        if ride is not None:
-            recs, ride_host = recs
-    elif crop:
-        # a crop-framed set: the same trace + measurements, a chunk of the plane pool at a time
-        recs, ride_host = crop_contours(packed, crop_planes(ops, (h, wd)), um_pix, total_area=data.get("area"), extra=ride,
-                                        descriptors=descriptors)
-    elif bbox_dev is not None:       # pixel counts / tight boxes already on the host (the image loop): no reduction, no wait for it
-        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, bbox=bbox_dev, total_area=int(np.sum(data["area"])), extra=ride,
-                            descriptors=descriptors)
-        if ride is not None:
-            recs, ride_host = recs
-    else:
-        recs = ops.contours(packed, max_contours=256, um_pix=um_pix, descriptors=descriptors)
-        if ride is not None:
-            ride_host = [e.cpu().numpy() for e in ride]
-    if extra is not None:
-        extra[:] = ride_host[:len(extra)]
+    # the RLE texts; replaced in place by their host arrays) and, behind them, the tables of every stage in launch order
+    ride, launched, result = extra, [], None
+    for stage, setting in on:
+        result = stage.launch(masks, classes, um_pix, setting, masks.area, result)
+        launched.append((stage, result))
+        ride = list(ride or []) + result.ride
+    recs, ride_host = masks.contours(um_pix, descriptors, ride)
     n_extra = 0 if extra is None else len(extra)
-    if neighbours is not None:
-        table, sums = Neighbours.from_i32(ride_host[n_extra], ride_host[n_extra + 1])
-        neighbours.rows = neighbour_rows(test_img, classes, metadata.thing_classes, table, sums, um_pix, psum)
-    if agglomerates is not None:
-        label, degree, own = Agglomerates.from_i32(*ride_host[-3:])
-        pixels = data.get("area")
-        if pixels is None:          # (a caller outside the pipeline: the border stage's counts, with a wait of their own)
-            pixels = ag.sums[:, 0].cpu().numpy()
-        agglomerates.rows = agglomerate_rows(test_img, classes, metadata.thing_classes, label, degree, own, pixels, um_pix, psum)
+    if extra is not None:
+        extra[:] = ride_host[:n_extra]
+    if launched:
+        rides = take_rides(ride_host, n_extra, [(stage.name, len(result.ride)) for stage, result in launched])
+        for stage, result in launched:
+            stat_rows[stage.name] = stage.decode(test_img, classes, metadata.thing_classes, rides[stage.name], um_pix, psum, masks.area, result)
     contrast = [(None, None, None)] * int(packed.shape[0])
     if measure_contrast:
         # measurements.py:195-215: gray levels under the whole instance mask; the histogram is a device reduction
         dev_im = image_dev if image_dev is not None else (None if im_host() is None else torch.from_numpy(im_host()).to(ops.device))
         if dev_im is not None:
-            if direct:
-                hist = packed.gray_histogram(dev_im)
-            else:
-                hist = crop_gray_histogram(packed, crop_planes(ops, (h, wd)), dev_im) if crop else ops.gray_histogram(packed, dev_im)
-            contrast = [contrast_percentiles(hh) for hh in hist]
+            contrast = [contrast_percentiles(hh) for hh in masks.gray_histogram(dev_im)]
     if visualize and im_host() is not None:
-        write_predictions_png(os.path.join(output_dir, f"{test_img}_predictions.png"), im_host(), packed.host_crops() if crop else mask_crops(ops, packed),
-                              classes, recs, metadata.thing_classes)
-    return measurement_rows(test_img, classes, recs, metadata.thing_classes, min_area, contrast, psum)
+        write_predictions_png(os.path.join(output_dir, f"{test_img}_predictions.png"), im_host(), masks.host_crops(), classes, recs,
+                              metadata.thing_classes)
+    return measurement_rows(test_img, classes, recs, metadata.thing_classes, min_area, contrast, psum), stat_rows
 
 
 def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_path: str, output_dir: str, metadata,
                        dataset_name: str, draw_scalebar: bool = False, visualize: bool = False,
                        rows_by_image: Optional[Dict[str, List[list]]] = None, crop_direct: bool = False,
-                       descriptors: Sequence[str] = (), neighbours: Optional[NeighbourSetting] = None,
-                       neighbour_rows_by_image: Optional[Dict[str, List[list]]] = None,
-                       agglomerates: Optional[AgglomerateSetting] = None,
-                       agglomerate_rows_by_image: Optional[Dict[str, List[list]]] = None) -> str:
+                       descriptors: Sequence[str] = (), statistics: Optional[Dict[str, NamedTuple]] = None,
+                       statistic_rows_by_image: Optional[Dict[str, Dict[str, List[list]]]] = None) -> str:
     """Measurement phase (``inference.py:983-1291``): one CSV row per external contour that passes
     the area gate, 20 columns, ``None`` -> empty field, floats through ``csv.writer``.  ``rows_by_image``: rows the image
     loop (or another rank, when images are sharded over ranks) has already measured; images without an entry are measured here.
     ``descriptors``: each requested family of ``DESCRIPTOR_CSV`` appends its columns behind "File name", in table order (rows
-    measured elsewhere come with them).  ``neighbours`` enabled: an image measured here also runs the neighbour stage, as the image
-    loop does, and files its rows of ``neighbours_results.csv`` in ``neighbour_rows_by_image``; ``agglomerates`` and
-    ``agglomerate_rows_by_image`` likewise for ``agglomerates_results.csv``."""
+    measured elsewhere come with them).  ``statistics`` (``statistics_setting``): an image measured here also runs the enabled
+    stages of ``IMAGE_STATISTICS``, as the image loop does, and files their rows in ``statistic_rows_by_image``, ``{stage name:
+    {image: rows}}``."""
     csv_filename = os.path.join(output_dir, "measurements_results.csv")
     with open(csv_filename, "w", newline="") as csvfile:
         w = csv.writer(csvfile)
@@ -3068,14 +3110,11 @@ def write_measurements(ops: MaskOps, dedup_results: Dict[str, dict], test_img_pa
             if rows_by_image is not None and test_img in rows_by_image:
                 rows = rows_by_image[test_img]
             else:
-                stage = NeighbourStage(neighbours.radius) if (neighbours is not None and neighbours.enabled) else None
-                agg = AgglomerateStage(agglomerates.gap, agglomerates.link) if (agglomerates is not None and agglomerates.enabled) else None
-                rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar, visualize,
-                                     crop_direct=crop_direct, descriptors=descriptors, neighbours=stage, agglomerates=agg)
-                if stage is not None and neighbour_rows_by_image is not None:
-                    neighbour_rows_by_image[test_img] = stage.rows
-                if agg is not None and agglomerate_rows_by_image is not None:
-                    agglomerate_rows_by_image[test_img] = agg.rows
+                rows, stat_rows = measure_image(ops, test_img, data, test_img_path, output_dir, metadata, dataset_name, draw_scalebar,
+                                                visualize, crop_direct=crop_direct, descriptors=descriptors, statistics=statistics)
+                if statistic_rows_by_image is not None:
+                    for stage, srows in stat_rows.items():
+                        statistic_rows_by_image.setdefault(stage, {})[test_img] = srows
             for r in rows:
                 w.writerow(r)
             csvfile.flush()

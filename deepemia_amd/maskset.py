@@ -152,6 +152,10 @@ class Neighbours:
     def sums_i32(self) -> torch.Tensor:
         return self.sums.view(torch.int32)
 
+    @property
+    def ride(self) -> List[torch.Tensor]:
+        return [self.table_i32, self.sums_i32]
+
     @staticmethod
     def from_i32(table_i32: np.ndarray, sums_i32: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """The host copies of :attr:`table_i32` / :attr:`sums_i32` as the int64 tables ``[M, 6]`` / ``[M, 3]``."""
@@ -180,6 +184,18 @@ def _neighbour_buffers(ops: "MaskOps", M: int, area, group,
     return res, (tab[2 * (M + 1):] if group is not None else None), res.point_off_dev
 
 
+def _launch_neighbours(ops: "MaskOps", entry: str, source: Sequence[Optional[torch.Tensor]], M: int, H: int, W: int, area, group,
+                       r2: int) -> Neighbours:
+    """One neighbour stage, enqueued without a wait.  ``entry`` and ``source``, the entry's leading word-source arguments:
+    ``demia_mask_neighbours`` with planes ``(packed, bbox)`` or ``demia_crop_neighbours`` with crops ``(payload, room, offsets,
+    bbox)``.  ``area``: the pixel counts on the host."""
+    res, group_d, off_d = _neighbour_buffers(ops, M, area, group)
+    _lib.check(getattr(ops.lib, entry)(*(_lib.ptr(t) for t in source), _lib.ptr(group_d), M, H, W, int(r2), _lib.ptr(off_d),
+                                       _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums), _lib.ptr(res.table),
+                                       ops._stream()), entry)
+    return res
+
+
 @dataclass
 class Agglomerates:
     """What ``MaskOps.agglomerates`` / ``CropMaskSet.agglomerates`` enqueued (``demia_mask_agglomerates``), all on the device."""
@@ -194,20 +210,8 @@ class Agglomerates:
 
     # int32 views of the three small tables: what rides in ContourSet.fetch(extra=...), 56 bytes per mask
     @property
-    def label_i32(self) -> torch.Tensor:
-        return self.label
-
-    @property
-    def degree_i32(self) -> torch.Tensor:
-        return self.degree
-
-    @property
-    def own_i32(self) -> torch.Tensor:
-        return self.own.view(torch.int32)
-
-    @property
     def ride(self) -> List[torch.Tensor]:
-        return [self.label_i32, self.degree_i32, self.own_i32]
+        return [self.label, self.degree, self.own.view(torch.int32)]
 
     @staticmethod
     def from_i32(label_i32: np.ndarray, degree_i32: np.ndarray, own_i32: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -218,11 +222,12 @@ class Agglomerates:
         return lab, deg, own
 
 
-def _agglomerate_buffers(ops: "MaskOps", M: int, area, group, border: Optional[Neighbours]):
-    """The outputs of one agglomerate stage and its host tables on the device: (result, group or None, point_off).  Without
-    ``border`` the border tensors and the one upload are those of a neighbour stage (its pair table is not made); with it -- a
-    ``Neighbours`` of the same masks -- its border tensors and its uploaded ``point_off`` are reused and only ``group``, if any,
-    is uploaded."""
+def _launch_agglomerates(ops: "MaskOps", entry: str, source: Sequence[Optional[torch.Tensor]], M: int, H: int, W: int, area, group,
+                         l2: int, border: Optional[Neighbours], label_lds_cap: int) -> Agglomerates:
+    """One agglomerate stage, enqueued without a wait; ``entry`` and ``source`` as for ``_launch_neighbours``
+    (``demia_mask_agglomerates`` / ``demia_crop_agglomerates``).  Without ``border`` the border tensors and the one upload are
+    those of a neighbour stage (its pair table is not made); with it -- a ``Neighbours`` of the same masks -- its border tensors
+    and its uploaded ``point_off`` are reused and only ``group``, if any, is uploaded."""
     dev = ops.device
     wpl = (M + 31) // 32
     if border is not None:
@@ -237,7 +242,11 @@ def _agglomerate_buffers(ops: "MaskOps", M: int, area, group, border: Optional[N
     res = Agglomerates(torch.empty((M, wpl), dtype=torch.int32, device=dev), torch.empty((M,), dtype=torch.int32, device=dev),
                        torch.empty((M,), dtype=torch.int32, device=dev), torch.empty((M, 6), dtype=torch.int64, device=dev),
                        nb.sums, nb.nborder, nb.points, nb.point_off)
-    return res, group_d, off_d
+    _lib.check(getattr(ops.lib, entry)(*(_lib.ptr(t) for t in source), _lib.ptr(group_d), M, H, W, int(l2), _lib.ptr(off_d),
+                                       _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums), int(border is not None),
+                                       _lib.ptr(res.links), _lib.ptr(res.degree), _lib.ptr(res.label), _lib.ptr(res.own),
+                                       int(label_lds_cap), ops._stream()), entry)
+    return res
 
 
 class PlanePool:
@@ -587,11 +596,7 @@ class MaskOps:
         if M and (area is None or bbox is None):
             a, bbox = self.area_bbox(packed, bbox)
             area = a.cpu().numpy()
-        res, group_d, off_d = _neighbour_buffers(self, M, area if M else np.zeros(0), group)
-        _lib.check(self.lib.demia_mask_neighbours(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(group_d), M, H, self._w(packed), int(r2),
-                                                  _lib.ptr(off_d), _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums),
-                                                  _lib.ptr(res.table), self._stream()), "demia_mask_neighbours")
-        return res
+        return _launch_neighbours(self, "demia_mask_neighbours", (packed, bbox), M, H, self._w(packed), area if M else np.zeros(0), group, r2)
 
     def agglomerates(self, packed: torch.Tensor, bbox: Optional[torch.Tensor], area, group=None, l2: int = 2,
                      border: Optional[Neighbours] = None, label_lds_cap: int = 0) -> Agglomerates:
@@ -606,13 +611,8 @@ class MaskOps:
             area = a.cpu().numpy()
         elif M and bbox is None:
             _, bbox = self.area_bbox(packed, bbox)
-        res, group_d, off_d = _agglomerate_buffers(self, M, area if M else np.zeros(0), group, border)
-        _lib.check(self.lib.demia_mask_agglomerates(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(group_d), M, H, self._w(packed), int(l2),
-                                                    _lib.ptr(off_d), _lib.ptr(res.points), _lib.ptr(res.nborder), _lib.ptr(res.sums),
-                                                    int(border is not None), _lib.ptr(res.links), _lib.ptr(res.degree),
-                                                    _lib.ptr(res.label), _lib.ptr(res.own), int(label_lds_cap), self._stream()),
-                   "demia_mask_agglomerates")
-        return res
+        return _launch_agglomerates(self, "demia_mask_agglomerates", (packed, bbox), M, H, self._w(packed), area if M else np.zeros(0), group,
+                                    l2, border, label_lds_cap)
 
     def skeleton(self, packed: torch.Tensor, bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The morphological skeleton (Guo-Hall thinning; ``demia_mask_skeleton`` in its thin-only form) of every mask, as packed

@@ -96,18 +96,17 @@ def one_image(pipe, descriptors=(), with_neighbours=False, with_agglomerates=Fal
     else:
         crop = rle_crop_launch(pipe.ops, packed, tabs[0], tabs[1]) if n else None
     extra = [crop[0]] if crop is not None else None
-    stage = I.NeighbourStage(NEIGHBOUR_RADIUS) if with_neighbours else None
-    agg = I.AgglomerateStage() if with_agglomerates else None
-    rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev, extra=extra,
-                           note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors, neighbours=stage,
-                           agglomerates=agg)
+    statistics = {"neighbours": I.NeighbourSetting(with_neighbours, NEIGHBOUR_RADIUS), "agglomerates": I.AgglomerateSetting(with_agglomerates, None, "any")}
+    rows, stat_rows = I.measure_image(pipe.ops, name, result, str(root), str(split), metadata, T.DATASET, False, False, image_dev=image_dev,
+                                      extra=extra, note_planes=pipe._note_planes, crop_direct=pipe.crop_direct, descriptors=descriptors,
+                                      statistics=statistics)
     texts = rle_text_from_payload(extra[0], crop[1], crop[2], size) if crop is not None else []
     if with_neighbours and pipe.crop:      # (a crop-framed set is a few MiB: keeping it does not move the next repetition's peak)
         last_set[pipe.mask_frame] = (pipe, packed, classes, tabs)
     if with_agglomerates and pipe.crop:
         last_agg[pipe.mask_frame] = (pipe, packed, classes, tabs)
     pipe.drop_cached(name)
-    return n, rows, texts, pipe.end_image_stats((size, size)), (stage.rows if stage is not None else None), (agg.rows if agg is not None else None)
+    return n, rows, texts, pipe.end_image_stats((size, size)), stat_rows.get("neighbours"), stat_rows.get("agglomerates")
 
 
 last_set = {}                        # crop frame -> the final set of the last image measured with +neighbours
