@@ -54,6 +54,7 @@ class ConvP32Desc(C.Structure):
         ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("head_out", C.c_void_p),
         ("head_n", C.c_int32), ("head_ld", C.c_int32), ("head_act", C.c_int32),
         ("groups", C.c_int32), ("group_rows", C.c_int32), ("row0", C.c_int32), ("single", C.c_int32),
+        ("head_planes", C.c_void_p), ("head_scale", C.c_void_p), ("head_bias", C.c_void_p), ("head_cout", C.c_int32),
     ]
 
 

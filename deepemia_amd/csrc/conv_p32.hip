@@ -87,6 +87,10 @@ struct ConvQ {
     const float* head_b;    // activated output row, + bias, sigmoid -> head_out[(m * ntn + tile_n) * head_ld + j]; the P32
     float* head_out;        // output itself is then not written
     int head_n, head_ld, head_act;
+    const void* hp_w;       // fused 1x1 layer (EPI_HEAD_PLANES): its tiled weight planes, scale and bias, hp_cout <= 16 output
+    const float* hp_scale;  // channels -> head_out[m * head_ld + j]
+    const float* hp_bias;
+    int hp_cout;
     int groups, group_rows, row0;   // scale groups (images): in_meta / res_meta / out_meta are [groups][2]; output row m of this
                                     // call belongs to group (m + row0) / group_rows
     int no_hk;              // single-plane build only (A/B switch DEMIA_P32_NO_HK=1): the plain K-step of 32 with both planes moved
@@ -179,7 +183,9 @@ __device__ __forceinline__ void write_acc16(const f32x4 (&r0)[2 * TN], const f32
 // hands tile-row i of its accumulators to LDS, then the 512 threads walk the WM * 32 rows x BN columns in 8-channel
 // groups: scale / bias / residual / activation, split into planes, 16-byte stores.  The planes one (p32_epilogue_planes,
 // every ordinary P32 layer) does the same wave by wave without workgroup barriers, in straight-line code with hardware
-// bounded buffer accesses of whole 128-byte lines.  All waves have passed a barrier after their last LDS read.
+// bounded buffer accesses of whole 128-byte lines.  Two more serve fused consumers whose producer output never reaches HBM:
+// p32_epilogue_head_direct (f32 head weights, <= 4 rows: the mask predictor) and p32_epilogue_head_planes (a whole 1x1 P32 layer
+// of <= 16 channels on the matrix pipe: the RPN predictor).  All waves have passed a barrier after their last LDS read.
 __device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // Scales are per GROUP of rows (one group per image, so that a tile's result does not depend on its batch neighbours).  A
@@ -211,6 +217,46 @@ __device__ __forceinline__ GroupScales load_group_scales(const ConvQ& p, int m0,
     load_group_scale(p, gs.g0 + 1, planes_out, gs.post1, gs.resi1, gs.sout1);
     load_group_scale(p, gs.g0 + 2, planes_out, gs.post2, gs.resi2, gs.sout2);
     return gs;
+}
+
+// The two per-element expressions every epilogue shares (stated ONCE: the fused RPN head below must round exactly like the two
+// launches it replaces, and a differently contracted multiply-add is a different result).
+// f32 result of an accumulator: un-scale (exact power of two), FrozenBN / weight scale, bias
+__device__ __forceinline__ float scale_shift(float acc, float post, float sc, float bs) { return (acc * post) * sc + bs; }
+// 8 channels of one row of a planes layer, from the accumulators (x0, x1) to the two fp16 planes of v * s_out; vm = max |v|
+__device__ __forceinline__ void planes_item(const float4 x0, const float4 x1, float post, float res_inv, float s_out, const float (&sc)[8],
+                                            const float (&bs)[8], const f16x8 ch, const f16x8 cl, float act_lo, bool sigmoid_on,
+                                            f16x8& h, f16x8& l, float& vm) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 v2[4] = {{x0.x, x0.y}, {x0.z, x0.w}, {x1.x, x1.y}, {x1.z, x1.w}};
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                                       // packed f32: two channels per instruction
+        const f32x2 scq = {sc[2 * q], sc[2 * q + 1]}, bsq = {bs[2 * q], bs[2 * q + 1]};
+        const f32x2 t = (v2[q] * post) * scq + bsq;
+        v[2 * q] = t.x;
+        v[2 * q + 1] = t.y;
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        // residual (h + l) r as two mixed-precision FMAs (h r and l r are exact: r is a power of two)
+        v[q] = fmaf((float)cl[q], res_inv, fmaf((float)ch[q], res_inv, v[q]));
+        v[q] = fmaxf(v[q], act_lo);
+    }
+    if (sigmoid_on && !(P32_ABLATE & 256)) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = 1.0f / (1.0f + expf(-v[q]));
+    }
+    vm = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; q += 2) {
+        vm = fmaxf(vm, fmaxf(fabsf(v[q]), fabsf(v[q + 1])));
+        const f32x2 y = f32x2{v[q], v[q + 1]} * s_out;
+        h[q] = (_Float16)y.x;
+        h[q + 1] = (_Float16)y.y;
+        l[q] = (_Float16)fmaf(-(float)h[q], 1.0f, y.x);
+        l[q + 1] = (_Float16)fmaf(-(float)h[q + 1], 1.0f, y.y);
+    }
 }
 
 template <int WM, int WN, int TM, int TN, bool HEAD, typename WriteRow>
@@ -314,7 +360,7 @@ __device__ __forceinline__ void p32_epilogue(const ConvQ& p, const GroupScales& 
                 const int gd = (m >= b1) + (m >= b2);
                 const float post = gd == 0 ? post0 : (gd == 1 ? post1 : post2);     // exact powers of two
 #pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = (v[q] * post) * sc[q] + bs[q];
+                for (int q = 0; q < 8; ++q) v[q] = scale_shift(v[q], post, sc[q], bs[q]);
                 if (res_on) {
                     const float res_inv = gd == 0 ? resi0 : (gd == 1 ? resi1 : resi2);
 #pragma unroll
@@ -521,41 +567,13 @@ __device__ __forceinline__ void p32_epilogue_planes(const ConvQ& p, const GroupS
             const int m = row_of(i, k);
             const float4 x0 = *reinterpret_cast<const float4*>(wsm + lr * (LDW * 4) + (line * 4 + cj) * 32);
             const float4 x1 = *reinterpret_cast<const float4*>(wsm + lr * (LDW * 4) + (line * 4 + cj) * 32 + 16);
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            f32x2 v2[4] = {{x0.x, x0.y}, {x0.z, x0.w}, {x1.x, x1.y}, {x1.z, x1.w}};
             const int gd = (m >= b1) + (m >= b2);
             const float post = gd == 0 ? post0 : (gd == 1 ? post1 : post2);     // exact powers of two
             const float res_inv = gd == 0 ? resi0 : (gd == 1 ? resi1 : resi2);  // 0 without a residual
             const float s_out = gd == 0 ? sout0 : (gd == 1 ? sout1 : sout2);
-            float v[8];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                                       // packed f32: two channels per instruction
-                const f32x2 scq = {sc[2 * q], sc[2 * q + 1]}, bsq = {bs[2 * q], bs[2 * q + 1]};
-                const f32x2 t = (v2[q] * post) * scq + bsq;
-                v[2 * q] = t.x;
-                v[2 * q + 1] = t.y;
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                // residual (h + l) r as two mixed-precision FMAs (h r and l r are exact: r is a power of two)
-                v[q] = fmaf((float)cl[k][q], res_inv, fmaf((float)ch[k][q], res_inv, v[q]));
-                v[q] = fmaxf(v[q], act_lo);
-            }
-            if (sigmoid_on && !(P32_ABLATE & 256)) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = 1.0f / (1.0f + expf(-v[q]));
-            }
             f16x8 h, l;
-            float vm = 0.f;
-#pragma unroll
-            for (int q = 0; q < 8; q += 2) {
-                vm = fmaxf(vm, fmaxf(fabsf(v[q]), fabsf(v[q + 1])));
-                const f32x2 y = f32x2{v[q], v[q + 1]} * s_out;
-                h[q] = (_Float16)y.x;
-                h[q + 1] = (_Float16)y.y;
-                l[q] = (_Float16)fmaf(-(float)h[q], 1.0f, y.x);
-                l[q + 1] = (_Float16)fmaf(-(float)h[q + 1], 1.0f, y.y);
-            }
+            float vm;
+            planes_item(x0, x1, post, res_inv, s_out, sc, bs, ch[k], cl[k], act_lo, sigmoid_on, h, l, vm);
             if (single) l = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
             vm = m < p.M ? vm : 0.f;                                            // rows beyond M hold bias only: not part of the tensor
             vmax0 = fmaxf(vmax0, gd == 0 ? vm : 0.f);
@@ -662,7 +680,133 @@ __device__ __forceinline__ void p32_epilogue_head_direct(const ConvQ& p, const G
 }
 
 
-constexpr int EPI_GENERIC = 0, EPI_PLANES = 1, EPI_HEAD = 2;
+// ---------------------------------------------------------------------------------------------------------------------
+// Epilogue of a planes layer whose only consumer is a 1x1 stride-1 f32-out layer of <= 16 channels (the RPN head: 3x3 conv +
+// ReLU, then objectness + anchor deltas), BIT FOR BIT what the two launches compute.  The consumer needs the producer's planes
+// and its output scale s -- not the measured max |x| -- and s is known before the first store (load_group_scale), so the planes
+// go to LDS instead of HBM (1 KiB per row written and read back, nothing else reads them):
+//   producer: the passes of p32_epilogue_planes (wave-local, planes_item), but h and l of a pass go into an LDS image in the K
+//     loop's stage format -- one 128-byte line per row and 32-channel group, chunk plane * 4 + k / 8, swizzled with (row >> 1) & 7;
+//     WM * 32 rows x 8 groups per pass, every wave contributing its TN groups of its 32 rows;
+//   consumer: per 16 rows ONE wave walks groups 0..7 into one accumulator with a_h b_l, a_l b_h, a_h b_h per group -- the K-step
+//     order and MFMA order of compute(), i.e. the summation order of the stand-alone 1x1 launch -- on the first 16 output channels
+//     of the consumer's tiled weight planes (16 KiB, staged once per workgroup), then scale_shift with post = 1 / s of the row's
+//     image, and 16 floats per row.
+// Two workgroup barriers per pass (A: the image is free again, B: it is complete), executed by every wave; the producers of pass
+// i + 1 compute under the consumers of pass i and meet them at A only when they want to write.  No max |x|, no out_meta.
+// LDS: [8 waves x 32 rows x (TN * 32 + 4) floats | image | weights], after the K loop's last barrier.
+template <int WM, int WN, int TM, int TN>
+struct HeadPlanesLds {
+    static constexpr int LDW = TN * 32 + 4, ROWS = WM * 32;
+    static constexpr int STG = WM * WN * 32 * LDW * 4, IMG = ROWS * 8 * 128, WB = 8 * 16 * 128;
+    static constexpr int BYTES = STG + IMG + WB;
+};
+template <int WM, int WN, int TM, int TN, typename WriteRow>
+__device__ __forceinline__ void p32_epilogue_head_planes(const ConvQ& p, const GroupScales& gs, char* smem, WriteRow&& write_tile_row, int wm, int wn, int m0) {
+    typedef HeadPlanesLds<WM, WN, TM, TN> L;
+    static_assert(WN * TN == 8 && WM * WN == 8, "one N tile of 256 channels, eight waves");
+    constexpr int LDW = L::LDW, ROWS = L::ROWS;
+    constexpr int PPW = 8 / TN, RPI = 2 * PPW, ITEMS = 32 / RPI;       // the lane mapping of p32_epilogue_planes
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    char* const wsm = smem + wave * (32 * LDW * 4);
+    char* const img = smem + L::STG;
+    char* const wimg = img + L::IMG;
+    const int b1 = __builtin_amdgcn_readfirstlane(gs.b1), b2 = __builtin_amdgcn_readfirstlane(gs.b2);
+    const float post0 = uniform(gs.post0), post1 = uniform(gs.post1), post2 = uniform(gs.post2);
+    const float sout0 = uniform(gs.sout0), sout1 = uniform(gs.sout1), sout2 = uniform(gs.sout2);
+    // the consumer's `post` = 1 / s_in of its input = 1 / s_out of this layer (load_group_scale), per image
+    const float ipost0 = uniform(1.0f / sout0), ipost1 = uniform(1.0f / sout1), ipost2 = uniform(1.0f / sout2);
+    // the consumer's weights: 8 K-steps x the first 16 rows of its first 64-channel block; 1024 16-byte chunks, two per thread
+    u32x4 wreg[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int c = tid + q * 512, g = c >> 7, row = (c >> 3) & 15, ck = c & 7;
+        wreg[q] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(p.hp_w) + g * 8192 + row * 128 + ck * 16);
+    }
+    const int cj = lane & 3, rs = (lane >> 2) & 1, lg = lane >> 3;
+    const int line = lg % TN;
+    const int r_first = (lg / TN) * 2 + rs;
+    const int cgrp = wn * TN + line;                         // 32-channel group of this lane's 8 channels
+    const int co = (cgrp * 4 + cj) * 8;
+    float sc[8], bs[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        sc[q] = p.scale ? p.scale[co + q] : 1.0f;
+        bs[q] = p.bias ? p.bias[co + q] : 0.0f;
+    }
+    const bool sigmoid_on = p.act == DEMIA_ACT_SIGMOID;
+    const float act_lo = p.act == DEMIA_ACT_RELU ? 0.f : -INFINITY;
+    const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    // consumer side: this lane's output channel (16x16 MFMA C layout: column = lane & 15, rows 4 (lane >> 4) + r)
+    const int r16 = lane & 15, kq = lane >> 4, fsw = (r16 >> 1) & 7;
+    const bool c_ok = r16 < p.hp_cout;
+    const float hsc = (p.hp_scale && c_ok) ? p.hp_scale[r16] : 1.0f;
+    const float hbs = (p.hp_bias && c_ok) ? p.hp_bias[r16] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        write_tile_row(i, reinterpret_cast<float*>(wsm));
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        f16x8 h[ITEMS], l[ITEMS];
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const int lr = r_first + k * RPI;
+            const int m = m0 + wm * (TM * 32) + i * 32 + lr;
+            const float4 x0 = *reinterpret_cast<const float4*>(wsm + lr * (LDW * 4) + (line * 4 + cj) * 32);
+            const float4 x1 = *reinterpret_cast<const float4*>(wsm + lr * (LDW * 4) + (line * 4 + cj) * 32 + 16);
+            const int gd = (m >= b1) + (m >= b2);
+            const float post = gd == 0 ? post0 : (gd == 1 ? post1 : post2);
+            const float s_out = gd == 0 ? sout0 : (gd == 1 ? sout1 : sout2);
+            float vm;
+            planes_item(x0, x1, post, 0.f, s_out, sc, bs, zero8, zero8, act_lo, sigmoid_on, h[k], l[k], vm);   // (no residual: as the planes epilogue, 0 x 0)
+        }
+        if (i > 0) __syncthreads();                          // A: the consumers of pass i - 1 have read the image
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k) {
+            const int R = wm * 32 + r_first + k * RPI, sw = (R >> 1) & 7;
+            char* ln = img + (cgrp * ROWS + R) * 128;
+            *reinterpret_cast<f16x8*>(ln + ((cj ^ sw) * 16)) = h[k];
+            *reinterpret_cast<f16x8*>(ln + (((4 + cj) ^ sw) * 16)) = l[k];
+        }
+        if (i == 0) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int c = tid + q * 512, g = c >> 7, row = (c >> 3) & 15, ck = c & 7;
+                *reinterpret_cast<u32x4*>(wimg + g * 2048 + row * 128 + ((ck ^ ((row >> 1) & 7)) * 16)) = wreg[q];
+            }
+        }
+        __syncthreads();                                     // B: the image of pass i (and, in pass 0, the weights) is complete
+        if (wave < ROWS / 16) {                              // (wave-uniform; no barrier inside)
+            f32x4 c = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const char* ab = img + (g * ROWS + wave * 16 + r16) * 128;
+                const char* bb = wimg + g * 2048 + r16 * 128;
+                const f16x8 ah = *reinterpret_cast<const f16x8*>(ab + ((kq ^ fsw) * 16));
+                const f16x8 al = *reinterpret_cast<const f16x8*>(ab + (((4 + kq) ^ fsw) * 16));
+                const f16x8 bh = *reinterpret_cast<const f16x8*>(bb + ((kq ^ fsw) * 16));
+                const f16x8 bl = *reinterpret_cast<const f16x8*>(bb + (((4 + kq) ^ fsw) * 16));
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int R = wave * 16 + kq * 4 + r;
+                const int m = m0 + (R >> 5) * (TM * 32) + i * 32 + (R & 31);
+                const int gd = (m >= b1) + (m >= b2);
+                const float ipost = gd == 0 ? ipost0 : (gd == 1 ? ipost1 : ipost2);
+                const float z = fmaxf(scale_shift(c[r], ipost, hsc, hbs), -INFINITY);     // the f32-out epilogue without activation
+                if (m < p.M && c_ok) p.head_out[(long)m * p.head_ld + r16] = z;
+            }
+        }
+    }
+}
+
+constexpr int EPI_GENERIC = 0, EPI_PLANES = 1, EPI_HEAD = 2, EPI_HEAD_PLANES = 3;
 
 // HK (single-plane build only, Cin % 64 == 0): the K-step is 64 channels of ONE plane.  A single-plane product reads the high
 // planes only, and with the plain K-step half of every DMA'd line (the low halves) is dead weight: at one MFMA per product the
@@ -1068,7 +1212,10 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 2 : 1) void conv_p32_k
             for (int j = 0; j < 2 * TN; ++j) asm volatile("" :: "v"(acc16[i][j]));
         return;
     }
-    if constexpr (EPI == EPI_PLANES) {
+    if constexpr (EPI == EPI_HEAD_PLANES) {
+        static_assert(M16, "the fused 1x1 layer rides on the 16x16x32 kernel");
+        p32_epilogue_head_planes<WM, WN, TM, TN>(p, gs, smem, [&](int i, float* e) { write_acc16<TN, TN * 32 + 4>(acc16[2 * i], acc16[2 * i + 1], e, lane); }, wm, wn, m0);
+    } else if constexpr (EPI == EPI_PLANES) {
         if constexpr (M16) {
             p32_epilogue_planes<WM, WN, TM, TN>(p, gs, smem, [&](int i, float* e) { write_acc16<TN, TN * 32 + 4>(acc16[2 * i], acc16[2 * i + 1], e, lane); }, wm, wn, m0, n0);
         } else {
@@ -1096,8 +1243,9 @@ template <int WM, int WN, int TM, int TN, bool M16 = true, int EPI = EPI_PLANES,
 int launch_q_(ConvQ p, hipStream_t st) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     // LDS: the K-loop stages, overlaid in the epilogue by the accumulator image (planes epilogue: one 32-row block per wave)
-    constexpr int stages = NST * (BM + BN) * 128, image = EPI == EPI_PLANES ? WM * WN * 32 * (TN * 128 + 16) : WM * 32 * (BN * 4 + 16);
-    static_assert(stages <= 160 * 1024, "LDS");
+    constexpr int stages = NST * (BM + BN) * 128, image = EPI == EPI_HEAD_PLANES ? HeadPlanesLds<WM, WN, TM, TN>::BYTES
+                                                         : (EPI == EPI_PLANES ? WM * WN * 32 * (TN * 128 + 16) : WM * 32 * (BN * 4 + 16));
+    static_assert(stages <= 160 * 1024 && image <= 160 * 1024, "LDS");
     constexpr int smem = stages > image ? stages : image;
     p.ntn = p.CoutPad / BN;
     p.nwg = p.ntn * cdiv(p.M, BM);
@@ -1169,8 +1317,8 @@ extern "C" int demia_conv2d_p32_single(const demia_conv_p32_desc* d, void* strea
 extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
     if (d && d->single) return demia_conv2d_p32_single(d, stream);                    // one MFMA per product, chosen per launch
 #endif
-    DEMIA_REQUIRE(d && d->in && d->in_meta && d->w && (d->out || d->head_n > 0), "null pointer");
-    DEMIA_REQUIRE(d->out_f32 || d->out_meta || d->head_n > 0, "P32 output needs out_meta");
+    DEMIA_REQUIRE(d && d->in && d->in_meta && d->w && (d->out || d->head_n > 0 || d->head_planes), "null pointer");
+    DEMIA_REQUIRE(d->out_f32 || d->out_meta || d->head_n > 0 || d->head_planes, "P32 output needs out_meta");
     DEMIA_REQUIRE(d->Cin > 0 && d->Cin % 32 == 0, "Cin must be a multiple of 32");
     DEMIA_REQUIRE(d->CoutPad >= d->Cout && d->CoutPad % 64 == 0, "CoutPad must be a multiple of 64");
     DEMIA_REQUIRE(d->out_f32 || d->Cout % 32 == 0, "P32 output needs Cout % 32 == 0");
@@ -1215,6 +1363,16 @@ extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
         DEMIA_REQUIRE(d->head_n <= 4 && d->head_w && d->head_b && d->head_out && d->head_ld >= d->head_n, "fused head: at most 4 rows, pointers, head_ld");
         DEMIA_REQUIRE(d->CoutPad % 256 == 0 && d->Cout == d->CoutPad && !d->out_f32, "fused head needs Cout % 256 == 0 and a planes layer");
     }
+    p.hp_w = d->head_planes; p.hp_scale = d->head_scale; p.hp_bias = d->head_bias; p.hp_cout = d->head_cout;
+    if (d->head_planes) {
+#if P32_SINGLE
+        DEMIA_REQUIRE(false, "fused 1x1 layer (head_planes): not in the single-plane build");
+#endif
+        DEMIA_REQUIRE(d->head_n == 0 && d->head_out && d->head_cout >= 1 && d->head_cout <= 16 && d->head_ld >= d->head_cout,
+                      "fused 1x1 layer: head_n == 0, head_out, 1 <= head_cout <= 16, head_ld >= head_cout");
+        DEMIA_REQUIRE(d->Cout == 256 && d->CoutPad == 256 && !d->out_f32 && d->res_mode == DEMIA_RES_NONE,
+                      "fused 1x1 layer needs a planes layer of exactly 256 channels without residual");
+    }
     p.stagger_ticks = 0;
 #if P32_DEV_TILES
     {
@@ -1225,8 +1383,23 @@ extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
     if (p.M == 0) return DEMIA_OK;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // tile_hint: 0 = auto (the model above), else one of the instantiated tiles (dev / tuning: scripts/gpu_conv_p32_check.py)
-    int tile = d->tile_hint ? d->tile_hint : choose_tile(p.M, d->CoutPad, p.ksteps, d->res_mode != DEMIA_RES_NONE, d->head_n > 0);
+    int tile = d->tile_hint ? d->tile_hint : choose_tile(p.M, d->CoutPad, p.ksteps, d->res_mode != DEMIA_RES_NONE, d->head_n > 0 || d->head_planes);
     const bool n256 = d->CoutPad % 256 == 0, n128 = d->CoutPad % 128 == 0;
+#if !P32_SINGLE
+    if (d->head_planes) {
+        // the fused 1x1 layer: the same three tiles as the fused head, and 64 x 256 (id 15, this mode only) where 128-row tiles would
+        // leave more than half of the 256 CUs without a workgroup -- the layer needs all 256 channels in one workgroup, so rows are
+        // the only way to more workgroups (RPN level p6 at 48 tiles: 8 112 rows, measured 86 us on 64 tiles of 128 x 256 against 62 us
+        // for the plain layer on 256 tiles of 128 x 64)
+        if (!d->tile_hint && cdiv(p.M, 128) <= 128) tile = 15;
+        switch (tile) {
+            case 1: return launch_q<2, 4, 4, 2, true, EPI_HEAD_PLANES>(p, st);
+            case 2: return launch_q<2, 4, 2, 2, true, EPI_HEAD_PLANES>(p, st);
+            case 15: return launch_q<1, 8, 2, 1, true, EPI_HEAD_PLANES>(p, st);
+            default: return launch_q<1, 8, 6, 1, true, EPI_HEAD_PLANES>(p, st);
+        }
+    }
+#endif
     if (d->head_n > 0) {
         // the fused head has its own instantiations: 256 x 256, 128 x 256 and 192 x 256
         switch (tile) {

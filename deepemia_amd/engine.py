@@ -316,6 +316,8 @@ class MaskRCNNEngine:
         # forward: L2 hit rate of roi_align_kernel 33.5 % -> 50.9 % (TCC_HIT / TCC_MISS), kernel time 1 079 -> 1 108 us per launch --
         # the misses were Infinity-Cache hits at the same cost; the kernel is bound by bytes through L1, not by where they come from
         self.roi_order = os.environ.get("DEEPEMIA_ROI_ORDER", "0") == "1"
+        # (A/B switch, default ON) the RPN predictor fused into the RPN conv's epilogue (f16x2 only; see ``rpn``)
+        self.rpn_fused = os.environ.get("DEEPEMIA_RPN_FUSED", "1") != "0"
         self.conv_events = None   # bench hook: list of (start_event, end_event, algorithmic_flops, kernel kind, algorithmic_bytes)
         self.unmatched_keys: List[str] = []
         self._used = set()
@@ -541,16 +543,28 @@ class MaskRCNNEngine:
         return p32.to_f32(x) if isinstance(x, p32.P32) else x.float()
 
     def conv_p32(self, x: p32.P32, L: ConvLayer, act=ACT_NONE, residual: Optional[p32.P32] = None, res_mode=RES_NONE,
-                 out_f32: bool = False, out_ld: int = 0, tile_hint: int = 0, head=None):
+                 out_f32: bool = False, out_ld: int = 0, tile_hint: int = 0, head=None, then: Optional[ConvLayer] = None):
         """``demia_conv2d_p32``: P32 in, P32 out (or plain f32 [.., out_ld] for the prediction heads).  ``head`` =
         (weights [hn, 256] f32, bias [hn] f32, ld, activation): the fused 1x1 head -- returns f32 [pixels * Cout / 256, ld]
-        instead of the layer's own output, which is never written."""
+        instead of the layer's own output, which is never written.  ``then`` = a 1x1 stride-1 layer of at most 16 output
+        channels consumed in this layer's epilogue (``head_planes`` of the descriptor): returns what
+        ``conv_p32(conv_p32(x, L, act), then, out_f32=True, out_ld=out_ld)`` returns, bit for bit, in one launch and without
+        the intermediate planes."""
         n, h, w, cin = x.shape
         assert cin == L.cin, (cin, L.cin)
         ho = (h + 2 * L.pad - L.kh) // L.stride + 1
         wo = (w + 2 * L.pad - L.kw) // L.stride + 1
         hw_ptr = hb_ptr = ho_ptr = hn = hld = hact = 0
-        if head is not None:
+        tp_ptr = ts_ptr = tb_ptr = tcout = 0
+        if then is not None:
+            assert head is None and residual is None and not out_f32, "a fused 1x1 layer follows a plain planes layer"
+            assert L.cout == L.cout_pad == 256 == then.cin and then.cout <= 16 and not L.single and not then.single, (L.cout, then.cout)
+            assert (then.kh, then.kw, then.stride, then.pad) == (1, 1, 1, 0), "the fused consumer is a 1x1 stride-1 layer"
+            hld = out_ld if out_ld > 0 else then.cout
+            out = self._scratch(n * ho * wo * hld, torch.float32).view(n, ho, wo, hld)
+            ho_ptr, tp_ptr, ts_ptr, tb_ptr, tcout = _lib.ptr(out), _lib.ptr(then.w3), _lib.ptr(then.scale3), _lib.ptr(then.bias), then.cout
+            optr, ometa, out_ld = 0, 0, 0
+        elif head is not None:
             hw_t, hb_t, hld, hact = head
             hn = int(hw_t.shape[0])
             out = self._scratch(n * ho * wo * (L.cout // 256) * hld, torch.float32).view(n * ho * wo * (L.cout // 256), hld)
@@ -589,14 +603,18 @@ class MaskRCNNEngine:
                                  (optr + c0 * (ld if out_f32 else L.cout) * 4) if optr else 0, ometa, L.wbound, L.bbound, cn, h, w, cin,
                                  ho, wo, L.cout, L.cout_pad, L.kh, L.kw, L.stride, L.pad, act, res_mode, 1 if out_f32 else 0, out_ld,
                                  tile_hint, hw_ptr, hb_ptr, (ho_ptr + c0 * (L.cout // 256) * hld * 4) if ho_ptr else 0, hn, hld, hact,
-                                 groups, group_rows, c0, L.single)
+                                 groups, group_rows, c0, L.single, tp_ptr, ts_ptr, tb_ptr, tcout)
             _lib.check(self.lib.demia_conv2d_p32(C.byref(d), self._stream()), "demia_conv2d_p32")
         if ev is not None:
             e1.record(torch.cuda.current_stream(self.device))
             # every operand once (planes are 4 bytes per element, like f32): the algorithmic traffic
             nbytes = (n * h * w * cin * 4 + L.cout_pad * L.kh * L.kw * cin * 4 + n * ho * wo * L.cout * 4 +
                       (0 if residual is None else residual.pixels * residual.channels * 4))
-            ev.append((e0, e1, 2.0 * n * ho * wo * L.cout * L.kh * L.kw * cin, "f16" if L.single else self.precision, nbytes))
+            flops = 2.0 * n * ho * wo * L.cout * L.kh * L.kw * cin
+            if then is not None:                       # the planes are neither written nor read; the consumer's product is done
+                nbytes += then.cout_pad * then.cin * 4 + n * ho * wo * (then.cout - L.cout) * 4
+                flops += 2.0 * n * ho * wo * then.cout * then.cin
+            ev.append((e0, e1, flops, "f16" if L.single else self.precision, nbytes))
         return out
 
     def conv(self, x, L: ConvLayer, act=ACT_NONE, residual=None, res_mode=RES_NONE,
@@ -780,7 +798,13 @@ class MaskRCNNEngine:
     def rpn(self, feats, newh: int, neww: int):
         b = feats["p2"].shape[0]
         heads = []
+        # f16x2: the predictor runs in the epilogue of the 3x3 conv (one launch per level, the 256-channel planes never reach
+        # HBM), bit-identical to the two launches; a single-plane stage keeps the two launches (``rpn_fused = False``: A/B, tests)
+        fused = self.rpn_fused and self.precision == "f16x2" and not self.rpn_conv.single and not self.rpn_pred.single
         for name in ("p2", "p3", "p4", "p5", "p6"):
+            if fused:
+                heads.append(self.conv_p32(feats[name], self.rpn_conv, act=ACT_RELU, then=self.rpn_pred, out_ld=16))
+                continue
             t = self.conv(feats[name], self.rpn_conv, act=ACT_RELU)
             heads.append(self.conv(t, self.rpn_pred, out_dtype=torch.float32, out_ld=16))
         boxes = torch.empty((b, POST_NMS_TOPK, 4), dtype=torch.float32, device=self.device)

@@ -167,6 +167,18 @@ typedef struct demia_conv_p32_desc {
      * output still split into both planes -- the per-stage precision map of DESIGN.md section 7 runs single stages this way.
      * 2: as 1, and the output's low plane is written as zeros (`--precision f16`, flagged NON-parity, every layer).          */
     int32_t single;
+    /* Optional fused 1x1 LAYER (head_planes != NULL; head_n must be 0): the P32 output of this layer (Cout == CoutPad == 256, no
+     * residual, single == 0) is consumed in the epilogue by a 1x1 stride-1 layer of head_cout <= 16 output channels with f32
+     * output, and never written -- `out` and `out_meta` are not touched and may be NULL.  head_planes: that layer's weights in
+     * the `w` tiling above ([CoutPad / 64][8][64][2][32] fp16, Cin = 256; the first 16 output channels are read), head_scale /
+     * head_bias: its `scale` / `bias` ([head_cout] f32 or NULL).  Row m of the result goes to head_out[m * head_ld + j], j <
+     * head_cout (head_ld >= head_cout; the other columns are not written).  The result is BIT-IDENTICAL to running the two
+     * layers as two calls (planes out, then out_f32 = 1): same planes of v * s, same product order.  Used for the RPN head
+     * (3x3 conv + ReLU, then objectness + anchor deltas).                                                                  */
+    const void* head_planes;
+    const float* head_scale;
+    const float* head_bias;
+    int32_t head_cout;
 } demia_conv_p32_desc;
 int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream);
 
