@@ -572,9 +572,10 @@ extern "C" int demia_crop_pair_matrix(const uint32_t* payload, const int32_t* ro
 
 extern "C" int demia_mask_place_tiles(const uint32_t* src, uint32_t* dst, const int32_t* x_off, const int32_t* y_off, int64_t T,
                                       int src_h, int src_w, int tile_h, int tile_w, int H, int W, void* stream) {
-    DEMIA_REQUIRE(src && dst && x_off && y_off && W > 0 && src_w > 0, "args");
+    DEMIA_REQUIRE(T >= 0 && H >= 0 && W > 0 && src_w > 0, "shapes");
     const long n = (long)T * H * ((W + 31) / 32);
-    if (n == 0) return DEMIA_OK;
+    if (n == 0) return DEMIA_OK;                       // (no tiles: the tensors of an empty batch have no storage, so no pointers yet)
+    DEMIA_REQUIRE(src && dst && x_off && y_off, "args");
     hipLaunchKernelGGL(place_tile_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, x_off, y_off,
                        (int)T, src_h, src_w, tile_h, tile_w, H, W);
     DEMIA_CHECK_LAUNCH("place_tile_kernel");

@@ -367,7 +367,8 @@ class MaskOps:
     def column_counts(self, packed: torch.Tensor, seg: Optional[torch.Tensor] = None, n_seg: int = 1,
                       bbox: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-column pixel counts over all masks ([W]), or per segment ([n_seg, W]) when ``seg`` (int32,
-        non-decreasing segment id per mask) is given."""
+        non-decreasing segment id per mask) is given.  At most 65535 masks per call (one grid row per mask): the C side
+        refuses more with an error, it does not split the call."""
         M, H, wpr = packed.shape
         W = self._w(packed)
         shape = (W,) if seg is None else (n_seg, W)
