@@ -417,6 +417,26 @@ def mask_iou(inter: np.ndarray, dt_area: np.ndarray, gt_area: np.ndarray, crowd:
     return np.where(inter > 0, i / np.where(inter > 0, u, 1.0), 0.0)
 
 
+BOUNDARY_RATIO = 0.02        # Boundary IoU's default dilation ratio
+
+
+def boundary_width(H: int, W: int, ratio: float = BOUNDARY_RATIO, width: Optional[int] = None) -> int:
+    """The erosion width ``d`` of Boundary IoU for an ``H x W`` frame (``include/deepemia_hip.h`` states the definitions):
+    ``width`` itself when given (an integer >= 1), else ``max(1, int(round(ratio * sqrt(H*H + W*W))))`` with Python's ``round``."""
+    if width is not None:
+        if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or int(width) < 1:
+            raise ValueError(f"boundary width must be an integer >= 1, got {width!r}")
+        return int(width)
+    return max(1, int(round(float(ratio) * float(np.sqrt(float(H) * float(H) + float(W) * float(W))))))
+
+
+def boundary_iou(band_inter: np.ndarray, dt_band: np.ndarray, gt_band: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    """Boundary IoU from the band counts: :func:`mask_iou` of ``|band(d) & band(g)|``, ``|band(d)|`` and ``|band(g)|`` (the
+    denominator is ``|band(d)|`` for a crowd ground truth; 0 where the bands do not meet).  The band intersections are
+    :func:`cross_matrix` / :func:`cross_matrix_crop` of the band sets (``MaskOps.boundary_band`` / ``CropMaskSet.boundary_band``)."""
+    return mask_iou(band_inter, dt_band, gt_band, crowd)
+
+
 def box_iou(dt: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     """``maskUtils.iou``'s box branch (``bbIou``) on XYWH float64 boxes."""
     dt = np.asarray(dt, dtype=np.float64).reshape(-1, 4)

@@ -390,6 +390,31 @@ class CropMaskSet:
             return off[:M], total
         return self._lazy_scratch("_skel_scratch", sizer)
 
+    def boundary_band(self, d: int, bbox: Optional[torch.Tensor] = None) -> "CropMaskSet":
+        """The boundary bands ``m & ~eroded(m, d)`` of the set's masks as a set over the SAME rooms (``demia_crop_boundary_band``; the
+        definition is in ``include/deepemia_hip.h``): its ``area`` holds the band pixel counts, its ``bbox`` the masks' tight boxes
+        (a band has its mask's).  Enqueued without a wait; this set is left as it is.  ``bbox``: the tight boxes on the device
+        when the caller has its own copy (default: the set's)."""
+        ops, M = self.ops, len(self)
+        d = int(d)
+        if d < 1:
+            raise ValueError(f"boundary_band: d must be an integer >= 1, got {d}")
+        if M == 0:
+            return CropMaskSet.empty(ops, self.hw)
+        bbox = self.bbox if bbox is None else bbox
+        payload = torch.zeros((max(self.words, 1),), dtype=torch.int32, device=ops.device)
+        area = torch.zeros((M,), dtype=torch.int32, device=ops.device)
+
+        def sizer():
+            off = np.zeros(max(M, 1), dtype=np.int64)
+            total = int(ops.lib.demia_crop_boundary_scratch(self.room_h.ctypes.data, M, self.hw[0], self.hw[1], off.ctypes.data))
+            return off[:M], total
+        scratch, scratch_off = self._lazy_scratch("_band_scratch", sizer)
+        _lib.check(ops.lib.demia_crop_boundary_band(_lib.ptr(self.payload), _lib.ptr(self.room), _lib.ptr(self.offsets), _lib.ptr(bbox), M,
+                                                    self.hw[0], self.hw[1], d, _lib.ptr(payload), _lib.ptr(area), _lib.ptr(scratch),
+                                                    _lib.ptr(scratch_off), ops._stream()), "demia_crop_boundary_band")
+        return CropMaskSet(ops, self.hw, self.room_h, payload, bbox, area, room=self.room, offsets=self.offsets)
+
     def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None,
               keep_words: bool = False) -> ContourSet:
         """``MaskOps.trace`` over ALL masks of the set, read where they are (``demia_crop_contours_wl``): no plane, no chunk, no

@@ -17,7 +17,13 @@ need its last entry raised.  ``evaluation.score_frame`` (pipeline mode only) say
 default) full-frame planes, with ``mask_frame: full``; ``crops`` the image's final :class:`CropMaskSet` and a ground truth built
 as one too, with ``mask_frame: crop`` or ``crop_direct`` -- rooms are scored, no ``[*, H, W/32]`` tensor is allocated.
 
-Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task), ``coco_instances_results.json``
+``evaluation.boundary_ap: true`` (off by default; both modes, both score frames) adds a third task, ``boundary``: COCO AP with
+``min(mask IoU, Boundary IoU)`` as the IoU (Cheng et al., CVPR 2021; the definitions are stated in ``include/deepemia_hip.h``).
+The bands of the detections and of the rasterised ground truth come from ``demia_mask_boundary_band`` /
+``demia_crop_boundary_band`` in the frame being scored; their width is ``evaluation.boundary_dilation_ratio`` (default 0.02) of
+the image diagonal, or ``evaluation.boundary_width`` pixels.  With the switch off nothing of it is launched, allocated or copied.
+
+Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task: ``bbox``, ``segm`` and, when asked for, ``boundary``), ``coco_instances_results.json``
 (``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``.  Not provided: prediction
 images (``--visualize`` only logs a warning) and, in predictor mode, the ``combo`` model pair.
 """
@@ -83,6 +89,28 @@ def score_frame_setting(dataset_name: Optional[str] = None, mask_frame: Optional
                              "evaluation.score_frame: planes (that scoring runs on full-frame planes only); use evaluation.score_frame: "
                              "crops, or mask_frame: full, for this dataset")
     return frame
+
+
+def boundary_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float, Optional[int]]]:
+    """The boundary-AP switch of the ``evaluation`` key (global, or in the dataset's file): None when ``evaluation.boundary_ap`` is
+    false or absent (the default: nothing is launched, allocated or copied for it), else ``(ratio, width)`` --
+    ``evaluation.boundary_dilation_ratio`` (default 0.02) and ``evaluation.boundary_width`` (None, or the erosion width in pixels,
+    which then replaces the ratio); ``cocoeval.boundary_width`` makes an image's ``d`` of them.  ValueError, with the key named,
+    for a wrong type or range; all three keys are checked whether or not the switch is on."""
+    try:
+        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
+    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
+        cfg = {}
+    on = cfg.get("boundary_ap", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"evaluation.boundary_ap must be true or false, got {on!r}")
+    ratio = cfg.get("boundary_dilation_ratio", CE.BOUNDARY_RATIO)
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (0.0 < float(ratio) < 1.0):
+        raise ValueError(f"evaluation.boundary_dilation_ratio must be a number between 0 and 1 (exclusive), got {ratio!r}")
+    width = cfg.get("boundary_width")
+    if width is not None and (isinstance(width, bool) or not isinstance(width, int) or width < 1):
+        raise ValueError(f"evaluation.boundary_width must be an integer >= 1, got {width!r}")
+    return (float(ratio), width) if on else None
 
 
 def read_image_bgr(path: str) -> np.ndarray:
@@ -162,6 +190,7 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         raise ValueError(f"evaluation mode must be one of {MODES}, got {mode!r}")
     if mode == "predictor" and str(rcnn) == "combo":
         raise ValueError("the predictor mode scores one model: rcnn must be 50 or 101")
+    boundary = boundary_setting(dataset_name)          # (checked before any model is loaded)
     config = get_config()
     max_dets = CE.check_max_dets((get_config(dataset_name=dataset_name).get("evaluation", {}) or {}).get("max_dets"))
     split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
@@ -174,8 +203,8 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     recs, class_names, to_dataset_id = _test_records(dataset_name, dataset_format, dataset_info, split_dir)
     metadata = MetadataCatalog.get(f"{dataset_name}_train")
     if mode == "pipeline":
-        tables = {"bbox": CE.EvalTables(), "segm": CE.EvalTables()}
-        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id)
+        tables = _new_tables(boundary)
+        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id, boundary)
         return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline")
     predictor, _ = choose_and_use_model(get_trained_model_paths(str(split_dir), rcnn), dataset_name, SCORE_THRESH, metadata, rcnn)
     if predictor is None:
@@ -185,7 +214,7 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     system_logger.info(f"Evaluating {len(recs)} test images of {dataset_name} (R{rcnn}, score threshold {SCORE_THRESH})")
 
     t_read = t_fwd = t_score = 0.0
-    tables = {"bbox": CE.EvalTables(), "segm": CE.EvalTables()}
+    tables = _new_tables(boundary)
     per_image: Dict[int, dict] = {}
     # same-size images share a forward; the results keep the record order
     order = sorted(range(len(recs)), key=lambda i: (recs[i]["height"], recs[i]["width"], i))
@@ -208,7 +237,7 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
         for ri, out in zip(group, outs):
-            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id)
+            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id, boundary)
         t3 = time.perf_counter()
         t_read += t1 - t0
         t_fwd += t2 - t1
@@ -216,6 +245,14 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
 
     return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, (t_read, t_fwd, t_score),
                           "forwards")
+
+
+def _new_tables(boundary=None) -> Dict[str, CE.EvalTables]:
+    """The tasks' tables in the order of the results: ``bbox``, ``segm`` and, with the boundary-AP switch on, ``boundary``."""
+    tables = {"bbox": CE.EvalTables(), "segm": CE.EvalTables()}
+    if boundary is not None:
+        tables["boundary"] = CE.EvalTables()
+    return tables
 
 
 def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, work: str):
@@ -234,11 +271,11 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
     results = OrderedDict()
     if not coco_results:
         system_logger.warning("No predictions from the model!")
-        for task in ("bbox", "segm"):
+        for task in tables:
             results[task] = {m: float("nan") for m in CE.METRICS}
     else:
         ev = CE.evaluate(tables, [r["image_id"] for r in recs], cat_ids, max_dets)
-        for task in ("bbox", "segm"):
+        for task in tables:
             system_logger.info(f"Evaluation results for {task}:\n" + "\n".join(CE.summary_lines(ev[task]["stats"], max_dets)))
             results[task] = CE.derive_results(ev[task]["stats"], ev[task]["precision"], class_names)
     t_score += time.perf_counter() - t0
@@ -256,8 +293,10 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
     return results
 
 
-def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int]) -> dict:
-    """Device work of one image (ground-truth masks, intersections, run lengths) and its rows of the IoU tables."""
+def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
+                 boundary: Optional[Tuple[float, Optional[int]]] = None) -> dict:
+    """Device work of one image (ground-truth masks, intersections, run lengths) and its rows of the IoU tables.  ``boundary``:
+    :func:`boundary_setting`'s value; not None adds the bands of both sides and their intersections for the ``boundary`` task."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(inst.image_size) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {inst.image_size}, the annotation says {(H, W)}")
@@ -270,8 +309,10 @@ def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables]
     classes = inst.pred_classes.cpu().numpy().astype(np.int64) if n else np.zeros((0,), np.int64)
     g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
     inter_t = CE.cross_matrix(ops, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat, W)
+    band_t = _plane_bands(ops, boundary, H, W, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat)
     counts, off = CE.rle_counts(ops, packed, d_bbox_t, W)
     strings = CE.rle_strings(counts, off)
+    band = tuple(t.cpu().numpy().astype(np.int64) for t in band_t) if band_t else None
     inter = inter_t.cpu().numpy().astype(np.int64)
     d_area = d_area_t.cpu().numpy().astype(np.int64)
     g_px = g_area_t.cpu().numpy().astype(np.int64)
@@ -283,13 +324,27 @@ def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables]
     xywh_l, scores_l, classes_l = xywh.tolist(), scores.tolist(), classes.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter)
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter, band)
     return {"instances": instances}
 
 
-def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter) -> None:
-    """One image's rows of both tasks' tables: detections (contiguous classes, float64 scores and XYWH boxes, mask pixel
-    counts) against the record's annotations (``g_px`` their rasterised pixel counts, ``inter`` the intersection counts)."""
+def _plane_bands(ops: MaskOps, boundary, H: int, W: int, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat):
+    """The boundary task's device work on planes, enqueued without a wait: the bands of the detections and of the rasterised ground
+    truth at the image's width ``d`` and their cross matrix -- ``(band intersections [n, G], detection band areas [n], ground-truth
+    band areas [G])`` int32 on the device, or None with the switch off."""
+    if boundary is None:
+        return None
+    d = CE.boundary_width(H, W, *boundary)
+    d_band, d_ba = ops.boundary_band(packed, d_bbox_t, d, W)
+    g_band, g_ba = ops.boundary_band(g_packed, g_bbox_t, d, W)
+    return CE.cross_matrix(ops, d_band, d_bbox_t, classes, g_band, g_bbox_t, g_cat, W), d_ba, g_ba
+
+
+def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None) -> None:
+    """One image's rows of the tasks' tables: detections (contiguous classes, float64 scores and XYWH boxes, mask pixel
+    counts) against the record's annotations (``g_px`` their rasterised pixel counts, ``inter`` the intersection counts).
+    ``band`` = (band intersections, detection band areas, ground-truth band areas) fills the ``boundary`` task: its IoU is
+    ``min(mask IoU, boundary IoU)``, its areas are those of ``segm``."""
     anns = rec["annotations"]
     crowd = np.asarray([int(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8)
     g_area = np.asarray([float(a["area"]) for a in anns], dtype=np.float64)
@@ -297,8 +352,11 @@ def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_
     d_cat = np.asarray([to_dataset_id[c] for c in classes_l], dtype=np.int64)
     g_cat_ds = np.asarray([to_dataset_id[int(c)] for c in g_cat], dtype=np.int64)
     img = rec["image_id"]
-    tables["segm"].add_image(img, d_cat, scores64, d_area.astype(np.float64), g_cat_ds, g_area, crowd,
-                             CE.mask_iou(inter, d_area, g_px, crowd))
+    m_iou = CE.mask_iou(inter, d_area, g_px, crowd)
+    tables["segm"].add_image(img, d_cat, scores64, d_area.astype(np.float64), g_cat_ds, g_area, crowd, m_iou)
+    if band is not None:
+        b_iou = CE.boundary_iou(band[0].reshape(m_iou.shape), band[1], band[2], crowd)
+        tables["boundary"].add_image(img, d_cat, scores64, d_area.astype(np.float64), g_cat_ds, g_area, crowd, np.minimum(m_iou, b_iou))
     tables["bbox"].add_image(img, d_cat, scores64, d_box64[:, 2] * d_box64[:, 3], g_cat_ds, g_area, crowd,
                              CE.box_iou(d_box64, g_box, crowd))
 
@@ -382,7 +440,7 @@ class PipelineRunner:
         pipe.clear_cache()
 
 
-def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id):
+def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id, boundary=None):
     """Every test image through the inference pipeline and the scorer; ``(per_image, (reads, pipeline, scoring) seconds)``."""
     system_logger.info(f"Evaluating the inference pipeline on {len(recs)} test images of {dataset_name} (rcnn {rcnn}, threshold {threshold})")
     runner = PipelineRunner(dataset_name, metadata, split_dir, rcnn, threshold)
@@ -391,16 +449,18 @@ def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tabl
     t_score = 0.0
     for ri, (_, hw, packed, scores, classes, tabs) in enumerate(runner.instances([rec["file_name"] for rec in recs])):
         t0 = time.perf_counter()
-        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame)
+        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame, boundary)
         t_score += time.perf_counter() - t0
     return per_image, (runner.t_read, runner.t_pipe, t_score)
 
 
-def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None) -> dict:
+def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None,
+                          boundary: Optional[Tuple[float, Optional[int]]] = None) -> dict:
     """Device work of one image's final instances (ground-truth masks, intersections, run lengths) and its rows of the IoU
     tables.  Everything the host needs comes over in ONE device-to-host copy; the detections' pixel counts and boxes are
     already on the host (``tabs``).  Dispatches on what ``final_instances`` handed over: planes are scored on planes, a
-    :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no instance)."""
+    :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no instance).  ``boundary``:
+    :func:`boundary_setting`'s value; not None adds the band launches, and their counts ride the same copy."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(int(v) for v in hw) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
@@ -411,13 +471,13 @@ def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, 
         d_area, d_bbox = np.asarray(tabs[0]).astype(np.int64), np.ascontiguousarray(np.asarray(tabs[1]).reshape(-1, 4), dtype=np.int32)
     det = (np.asarray([int(c) for c in classes][:n], dtype=np.int64), np.asarray([float(v) for v in scores][:n], dtype=np.float64), d_area, d_bbox)
     if isinstance(packed, CropMaskSet) or (n == 0 and score_frame == "crops"):
-        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id)
+        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id, boundary)
     if n == 0:
         packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
-    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id)
+    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id, boundary)
 
 
-def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id) -> dict:
+def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id, boundary=None) -> dict:
     """``score_frame: planes``: the detections are full-frame planes and every annotation is rasterised into one."""
     anns = rec["annotations"]
     classes, _, _, d_bbox = det
@@ -433,30 +493,40 @@ def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor,
         g_packed, g_area_t, g_bbox_t = CE.rasterize_polygons(ops, [a["segmentation"] for a in anns], H, W, err_out=err)
     g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
     inter_t = CE.cross_matrix(ops, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat, W)
+    band_t = _plane_bands(ops, boundary, H, W, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat)
     n_t, counts_t = CE.rle_counts_launch(ops, packed, d_bbox_t, W, CE.rle_room(d_bbox))
-    host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [counts_t]).cpu().numpy()   # the ONE wait
+    host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [t.reshape(-1) for t in band_t or ()]
+                     + [counts_t]).cpu().numpy()                                                                                    # the ONE wait
     return _finish_pipeline_image(rec, H, det, g_cat, host, bool(err), int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W))
+                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W), band_t is not None)
 
 
-def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id) -> dict:
+def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id, boundary=None) -> dict:
     """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too, the cross
-    matrix and the run lengths read both sets' words in place.  No ``[*, H, W/32]`` tensor exists here."""
+    matrix and the run lengths read both sets' words in place, and the bands of the boundary task are sets over the same rooms.
+    No ``[*, H, W/32]`` tensor exists here."""
     anns = rec["annotations"]
     classes, _, _, d_bbox = det
     d_bbox_t = ops.upload(d_bbox) if len(cset) else cset.bbox
     gt, err = _gt_crops(ops, anns, H, W)
     g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
     inter_t = CE.cross_matrix_crop(ops, cset, classes, gt, g_cat, det_bbox=d_bbox_t)
+    band_t = []
+    if boundary is not None:
+        d = CE.boundary_width(H, W, *boundary)
+        d_band, g_band = cset.boundary_band(d, bbox=d_bbox_t), gt.boundary_band(d)
+        band_t = [CE.cross_matrix_crop(ops, d_band, classes, g_band, g_cat, det_bbox=d_bbox_t).reshape(-1), d_band.area, g_band.area]
     n_t, counts_t = CE.rle_counts_launch_crop(ops, cset, CE.rle_room(d_bbox), bbox=d_bbox_t)
-    host = torch.cat([n_t, inter_t.reshape(-1), gt.area.reshape(-1), err.reshape(-1), counts_t]).cpu().numpy()                       # the ONE wait
+    host = torch.cat([n_t, inter_t.reshape(-1), gt.area.reshape(-1), err.reshape(-1)] + band_t + [counts_t]).cpu().numpy()           # the ONE wait
     return _finish_pipeline_image(rec, H, det, g_cat, host, True, int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t))
+                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t), boundary is not None)
 
 
-def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_err: bool, room: int, tables, to_dataset_id, encode_again) -> dict:
+def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_err: bool, room: int, tables, to_dataset_id, encode_again,
+                           has_band: bool = False) -> dict:
     """Host side of both scorers, from the one copy ``host`` = run-length sizes [n], intersections [n, G], ground-truth pixel
-    counts [G], the rasteriser's error word (``has_err``), the run-length room: the result rows and the image's rows of the IoU
+    counts [G], the rasteriser's error word (``has_err``), with ``has_band`` the band intersections [n, G] and the band areas of
+    the detections [n] and of the ground truth [G], the run-length room: the result rows and the image's rows of the IoU
     tables.  ``encode_again`` runs the two-pass encoder (one more wait) when the room was too small."""
     classes, scores64, d_area, _ = det
     n, G, W = len(classes), len(g_cat), int(rec["width"])
@@ -469,6 +539,11 @@ def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_
     if has_err:
         CE.check_rasterize_error(int(host[pos]))
         pos += 1
+    band = None
+    if has_band:
+        band = (host[pos:pos + n * G].reshape(n, G).astype(np.int64), host[pos + n * G:pos + n * G + n].astype(np.int64),
+                host[pos + n * G + n:pos + n * G + n + G].astype(np.int64))
+        pos += n * G + n + G
     runs = CE.rle_counts_finish(n_host, host[pos:pos + room]) if n else (np.zeros((0,), np.uint32), np.zeros((1,), np.int64))
     if runs is None:
         system_logger.debug(f"{rec['file_name']}: run lengths need more than {room} counts; encoding again")
@@ -478,5 +553,5 @@ def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_
     xywh_l, scores_l = xywh.tolist(), scores64.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter)
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter, band)
     return {"instances": instances}

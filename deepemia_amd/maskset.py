@@ -629,6 +629,29 @@ class MaskOps:
                                                 0, 0, _lib.ptr(scratch2), _lib.ptr(out), self._stream()), "demia_mask_skeleton")
         return out
 
+    def boundary_band(self, packed: torch.Tensor, bbox: Optional[torch.Tensor], d: int, W: Optional[int] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The boundary band ``m & ~eroded(m, d)`` of every mask (``demia_mask_boundary_band``; the definition is in
+        ``include/deepemia_hip.h``): ``(band planes of packed's shape, band_area [M] int32)`` on the device, enqueued without a
+        wait; ``packed`` is left as it is.  ``bbox``: any superset of the tight boxes (None: ``area_bbox`` is launched first);
+        ``W``: the frame's pixel width (default: ``set_frame_width``'s rule)."""
+        M, H, wpr = packed.shape
+        d = int(d)
+        if d < 1:
+            raise ValueError(f"boundary_band: d must be an integer >= 1, got {d}")
+        out = torch.zeros_like(packed)
+        area = torch.zeros((M,), dtype=torch.int32, device=self.device)
+        if M == 0:
+            return out, area
+        if bbox is None:
+            _, bbox = self.area_bbox(packed)
+        scratch = torch.empty_like(packed)           # only touched by regions that do not fit in LDS
+        if W is not None and (int(W) + 31) // 32 != wpr:
+            raise ValueError(f"boundary_band: planes of {wpr} words per row are not {W} pixels wide")
+        _lib.check(self.lib.demia_mask_boundary_band(_lib.ptr(packed), _lib.ptr(bbox), M, H, self._w(packed) if W is None else int(W), d, _lib.ptr(out),
+                                                     _lib.ptr(area), _lib.ptr(scratch), self._stream()), "demia_mask_boundary_band")
+        return out, area
+
 
 class ContourSet:
     """Device-resident result of one contour trace over M masks (see :meth:`MaskOps.trace`)."""

@@ -761,6 +761,46 @@ int demia_host_coco_match(int64_t G, const int64_t* dt_off, const int64_t* gt_of
 int64_t demia_host_rle_string(const uint32_t* counts, const int64_t* offsets, int64_t M, char* out, int64_t cap,
                               int64_t* text_off);
 
+/* demia_mask_boundary_band / demia_crop_boundary_band = the boundary band of a mask, for Boundary IoU (Cheng et al., "Boundary
+ * IoU", CVPR 2021; not in the reference program; opt-in: evaluation.boundary_ap).  The definitions, stated here once:
+ *   width   the erosion width of an H x W frame is d = max(1, int(round(ratio * sqrt(H*H + W*W)))), round = Python's round (half to
+ *           even), ratio = evaluation.boundary_dilation_ratio (default 0.02); evaluation.boundary_width, an integer >= 1, gives d
+ *           directly in pixels.  (cocoeval.boundary_width computes it; the kernel takes d.)
+ *   eroded(m, d)[y, x] = 1 iff every pixel (y + j, x + i), |i| <= d, |j| <= d, is 1; pixels outside the frame count as 0.
+ *   band(m, d) = m & ~eroded(m, d).  A subset of the mask, so it fits the mask's room; it has the mask's tight box; a mask thinner
+ *           than 2d + 1 in either direction is its own band.
+ *   The published construction -- pad a 1-px zero ring, then d iterations of a 3 x 3 erosion whose own border counts as set -- gives
+ *           the same eroded mask.
+ *   bIoU(a, g) = |band(a) & band(g)| / (|band(a)| + |band(g)| - |band(a) & band(g)|), the denominator |band(a)| for a crowd g, 0
+ *           where the intersection is 0: cocoeval.mask_iou on band counts (cocoeval.boundary_iou).
+ *   The IoU of the evaluate task `boundary` is min(mask IoU, bIoU) element by element, crowd columns included; a detection's area
+ *           and the area ranges are those of `segm`: mask pixels, not band pixels.
+ * The entries:
+ *   band       laid out like the source words ([M, H, wpr] planes, or a payload with the SAME room and offsets).  The CALLER zeroes
+ *              it; the kernel writes the words of each mask's box (clipped to the frame; crops: to the room) and nothing else, so
+ *              planes stay zero outside each box and a room outside its box.  A mask with an empty box writes nothing.  The padding
+ *              bits beyond column W - 1 stay zero.
+ *   band_area  [M] i32 = |band(m, d)|, 0 for an empty box.
+ *   bbox       any superset of the tight box that is zero outside it (crops: inside the room).
+ *   d          1 <= d < 2^24.  If 2d + 1 exceeds the box's width or height the band is the mask: it is copied and counted.
+ * One workgroup per mask on the words of its box, 32 pixels per lane operation: the AND over 2d + 1 pixels of a row by doubling
+ * shifts (funnel shifts of two words), then the same over rows -- about 2 log2(2d + 1) passes, two buffers.  A region of at most
+ * 8192 words works in LDS.  A larger one works in the output's own words of the region and in scratch:
+ *   planes: `scratch` is [M, H, wpr], indexed like the planes; only the box's words of a large region are written;
+ *   crops:  scratch[scratch_off[m] ..), which demia_crop_boundary_scratch sizes from the HOST copy of the rooms alone: it fills
+ *           scratch_off [M] i64 and returns the total words, the room's words for a room of more than 8192 words, 0 for every other
+ *           mask.  With a total of 0 the scratch is not touched (any non-NULL pointer will do).
+ * A word outside the box, the room or the frame is a zero operand and is never fetched: a crop kernel never reads outside its mask's
+ * room.  The source words are only read; nothing but band, band_area and scratch is written; no buffer of a call may be another
+ * one.  Boolean word operations and popcounts, plain vector stores; the result does not depend on alignment, position, launch
+ * layout or the frame form.  H x ceil(W / 32) < 2^26.  M == 0: DEMIA_OK without a launch.  One launch, no allocation, capturable. */
+int demia_mask_boundary_band(const uint32_t* masks, const int32_t* bbox, int64_t M, int H, int W, int d, uint32_t* band,
+                             int32_t* band_area /* [M] */, uint32_t* scratch, void* stream);
+int64_t demia_crop_boundary_scratch(const int32_t* room_host, int64_t M, int H, int W, int64_t* scratch_off);
+int demia_crop_boundary_band(const uint32_t* payload, const int32_t* room, const int64_t* offsets, const int32_t* bbox, int64_t M,
+                             int H, int W, int d, uint32_t* band, int32_t* band_area /* [M] */, uint32_t* scratch,
+                             const int64_t* scratch_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
