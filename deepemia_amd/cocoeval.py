@@ -10,8 +10,10 @@ threshold) in one call (``match``) and ``rleToString`` (``rle_strings``).  numpy
 """
 from __future__ import annotations
 
+import csv
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+import os
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -435,6 +437,128 @@ def boundary_iou(band_inter: np.ndarray, dt_band: np.ndarray, gt_band: np.ndarra
     denominator is ``|band(d)|`` for a crowd ground truth; 0 where the bands do not meet).  The band intersections are
     :func:`cross_matrix` / :func:`cross_matrix_crop` of the band sets (``MaskOps.boundary_band`` / ``CropMaskSet.boundary_band``)."""
     return mask_iou(band_inter, dt_band, gt_band, crowd)
+
+
+# ---- outline agreement: surface distances per matched pair ------------------------------------------------------------------------
+OUTLINE_IOU = 0.5            # a detection and an annotation are a pair from this mask IoU on
+OUTLINE_TOLERANCE = 2        # NSD's tolerance in pixels: a choice, not a measurement
+OUTLINE_VALUES = ("assd", "rms", "hausdorff", "hd95", "nsd", "diameter_error", "area_error")
+OUTLINE_ROW_HEADER = ["image_id", "file_name", "category_id", "class_name", "detection", "annotation", "score", "iou", "detection_pixels",
+                      "annotation_pixels", "detection_border", "annotation_border", "assd_px", "rms_px", "hausdorff_px", "hd95_px", "nsd",
+                      "diameter_error_px", "relative_area_error"]
+OUTLINE_SUMMARY_HEADER = ["class_name", "annotations", "detections", "matched", "missed", "spurious", "mean_assd_px", "median_assd_px",
+                          "mean_hd95_px", "max_hausdorff_px", "mean_nsd", "mean_diameter_error_px", "mean_abs_relative_area_error"]
+
+
+def outline_match(iou: np.ndarray, scores: np.ndarray, d_cat: np.ndarray, g_cat: np.ndarray, crowd: np.ndarray,
+                  thr: float = OUTLINE_IOU) -> np.ndarray:
+    """The pairs of the outline-agreement report for one image, ``[P, 2]`` int64 (detection, annotation) in detection order, from
+    the ``segm`` IoU table (:func:`mask_iou`, f64).  Detections are taken in descending score, ties by ascending index; each
+    takes the still unmatched annotation that is not a crowd region, has its category and an IoU of at least ``thr``, and among
+    those the highest IoU, ties by the lower annotation index.  Crowd annotations are never matched and ``maxDets`` does not
+    apply.  Deliberately not COCOeval's matcher (no ignore flags, no area ranges, one threshold): AP stays COCOeval's business."""
+    iou = np.asarray(iou, dtype=np.float64).reshape(len(scores), len(g_cat))
+    d_cat, g_cat = np.asarray(d_cat, dtype=np.int64), np.asarray(g_cat, dtype=np.int64)
+    free = ~np.asarray(crowd).astype(bool)
+    pairs = []
+    for d in np.argsort(-np.asarray(scores, dtype=np.float64), kind="stable").tolist():
+        ok = free & (g_cat == d_cat[d]) & (iou[d] >= thr)
+        if ok.any():
+            g = int(np.argmax(np.where(ok, iou[d], -1.0)))           # (argmax: the first of the highest, so the lower index)
+            free[g] = False
+            pairs.append((d, g))
+    return np.asarray(sorted(pairs), dtype=np.int64).reshape(-1, 2)
+
+
+def outline_values(rec: Dict[str, np.ndarray], d_px: np.ndarray, g_px: np.ndarray, tolerance: int = OUTLINE_TOLERANCE) -> Dict[str, np.ndarray]:
+    """The report's seven values per pair, f64 from the integers alone.  ``rec``: ``OutlineAgreement.from_host``'s arrays (direction
+    0: detection -> annotation, 1: the reverse); ``d_px`` / ``g_px``: the rasterised pixel counts of the pairs' two masks.
+      assd            (sum_q_dg + sum_q_gd) / (256 (n_d + n_g))
+      rms             sqrt((sum_d2_dg + sum_d2_gd) / (n_d + n_g))
+      hausdorff       sqrt(max(max_d2_dg, max_d2_gd))
+      hd95            the larger, over the two directions, of the smallest c with 100 cum_hist[c] >= 95 n; SATURATES at 127
+      nsd             (cum_dg[tolerance] + cum_gd[tolerance]) / (n_d + n_g), tolerance an integer from 0 to 126
+      diameter_error  2 sqrt(A_d / pi) - 2 sqrt(A_g / pi): signed, positive = the detection is too large
+      area_error      (A_d - A_g) / A_g
+    All lengths in pixels."""
+    n = rec["n"].astype(np.int64)
+    both = (n[:, 0] + n[:, 1]).astype(np.float64)
+    cum = np.cumsum(rec["hist"].astype(np.int64), axis=2)
+    hd95 = np.argmax(100 * cum >= 95 * n[:, :, None], axis=2).max(axis=1) if len(n) else np.zeros(0, np.int64)
+    a_d, a_g = np.asarray(d_px, dtype=np.int64), np.asarray(g_px, dtype=np.int64)
+    return {"assd": (rec["sum_q"][:, 0] + rec["sum_q"][:, 1]).astype(np.float64) / (256.0 * both),
+            "rms": np.sqrt((rec["sum_d2"][:, 0] + rec["sum_d2"][:, 1]).astype(np.float64) / both),
+            "hausdorff": np.sqrt(np.maximum(rec["max_d2"][:, 0], rec["max_d2"][:, 1]).astype(np.float64)),
+            "hd95": hd95.astype(np.float64),
+            "nsd": (cum[:, 0, tolerance] + cum[:, 1, tolerance]).astype(np.float64) / both,
+            "diameter_error": 2.0 * np.sqrt(a_d.astype(np.float64) / np.pi) - 2.0 * np.sqrt(a_g.astype(np.float64) / np.pi),
+            "area_error": (a_d - a_g).astype(np.float64) / a_g.astype(np.float64)}
+
+
+class OutlineReport:
+    """The outline-agreement report of one evaluate run: one row per matched pair (:func:`outline_match`, image by image) with the
+    values of :func:`outline_values`, and per class the counts and the pooled statistics.  ``measure`` of :meth:`add_image` is the
+    device stage: ``measure(pairs, detection pixel counts, annotation pixel counts)`` is called only for an image with a pair and
+    returns ``OutlineAgreement.from_host``'s arrays."""
+
+    def __init__(self, iou: float = OUTLINE_IOU, tolerance: int = OUTLINE_TOLERANCE):
+        self.iou, self.tolerance = float(iou), int(tolerance)
+        self.rows: List[list] = []
+        self.counts: Dict[int, List[int]] = {}       # dataset category id -> [non-crowd annotations, detections, matched]
+
+    def add_image(self, image_id, file_name: str, d_cat, scores, d_px, g_cat, g_px, crowd, iou: np.ndarray,
+                  measure: Callable[[np.ndarray, np.ndarray, np.ndarray], Dict[str, np.ndarray]]) -> int:
+        """One image: ``d_cat`` / ``g_cat`` dataset category ids, ``scores`` f64, ``d_px`` / ``g_px`` pixel counts, ``iou`` the
+        ``segm`` IoU table.  Returns the number of pairs."""
+        d_cat, g_cat = np.asarray(d_cat, dtype=np.int64), np.asarray(g_cat, dtype=np.int64)
+        crowd = np.asarray(crowd).astype(bool)
+        for c in g_cat[~crowd].tolist():
+            self.counts.setdefault(c, [0, 0, 0])[0] += 1
+        for c in d_cat.tolist():
+            self.counts.setdefault(c, [0, 0, 0])[1] += 1
+        pairs = outline_match(iou, scores, d_cat, g_cat, crowd, self.iou)
+        if len(pairs) == 0:
+            return 0
+        d_all, g_all = np.asarray(d_px, dtype=np.int64).reshape(-1), np.asarray(g_px, dtype=np.int64).reshape(-1)
+        rec = measure(pairs, d_all, g_all)
+        d_px, g_px = d_all[pairs[:, 0]], g_all[pairs[:, 1]]
+        val = outline_values(rec, d_px, g_px, self.tolerance)
+        iou = np.asarray(iou, dtype=np.float64).reshape(len(d_cat), len(g_cat))
+        for k, (d, g) in enumerate(pairs.tolist()):
+            self.counts[int(d_cat[d])][2] += 1
+            self.rows.append([image_id, file_name, int(d_cat[d]), d, g, float(scores[d]), float(iou[d, g]), int(d_px[k]), int(g_px[k]),
+                              int(rec["n"][k, 0]), int(rec["n"][k, 1])] + [float(val[name][k]) for name in OUTLINE_VALUES])
+        return len(pairs)
+
+    def summary(self, cat_ids: Sequence[int], class_names: Sequence[str]) -> List[list]:
+        """One row per class (``cat_ids`` and ``class_names`` side by side) and the row ``all``, in ``OUTLINE_SUMMARY_HEADER``'s
+        columns; the values are pooled over the pairs, and None where a class has no pair."""
+        out = []
+        for cid, name in list(zip(cat_ids, class_names)) + [(None, "all")]:
+            cnt = [sum(v[i] for k, v in self.counts.items() if cid is None or k == cid) for i in range(3)]
+            rows = [r for r in self.rows if cid is None or r[2] == cid]
+            v = {n: np.asarray([r[11 + i] for r in rows], dtype=np.float64) for i, n in enumerate(OUTLINE_VALUES)}
+            stats = [None] * 7 if not rows else [float(v["assd"].mean()), float(np.median(v["assd"])), float(v["hd95"].mean()),
+                                                 float(v["hausdorff"].max()), float(v["nsd"].mean()), float(v["diameter_error"].mean()),
+                                                 float(np.abs(v["area_error"]).mean())]
+            out.append([name, cnt[0], cnt[1], cnt[2], cnt[0] - cnt[2], cnt[1] - cnt[2]] + stats)
+        return out
+
+    def write(self, output_dir: str, cat_ids: Sequence[int], class_names: Sequence[str]) -> List[list]:
+        """``outline_agreement.csv`` and ``outline_summary.csv`` in ``output_dir``; returns the summary rows."""
+        names = dict(zip(cat_ids, class_names))
+        with open(os.path.join(output_dir, "outline_agreement.csv"), "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(OUTLINE_ROW_HEADER)
+            for r in self.rows:
+                w.writerow(r[:3] + [names.get(r[2], "")] + [repr(x) if isinstance(x, float) else x for x in r[3:]])
+        summary = self.summary(cat_ids, class_names)
+        with open(os.path.join(output_dir, "outline_summary.csv"), "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(OUTLINE_SUMMARY_HEADER)
+            for r in summary:
+                w.writerow(["" if x is None else (repr(x) if isinstance(x, float) else x) for x in r])
+        return summary
 
 
 def box_iou(dt: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:

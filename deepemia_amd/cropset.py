@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, PlanePool, _launch_agglomerates, _launch_neighbours,
-                      reads_words)
+from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, OutlineAgreement, PlanePool, _launch_agglomerates,
+                      _launch_neighbours, _launch_outline, reads_words)
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
@@ -414,6 +414,21 @@ class CropMaskSet:
                                                     self.hw[0], self.hw[1], d, _lib.ptr(payload), _lib.ptr(area), _lib.ptr(scratch),
                                                     _lib.ptr(scratch_off), ops._stream()), "demia_crop_boundary_band")
         return CropMaskSet(ops, self.hw, self.room_h, payload, bbox, area, room=self.room, offsets=self.offsets)
+
+    def outline_agreement(self, gt: "CropMaskSet", pairs, area=None, gt_area=None, bbox: Optional[torch.Tensor] = None) -> OutlineAgreement:
+        """``MaskOps.outline_agreement`` of this set (the detections) against ``gt`` (the annotations) over the same frame, on the
+        words in place (``demia_crop_outline_agreement``): the same records, no plane, no wait.  ``area`` / ``gt_area``: the pixel
+        counts on the host; None: the sets' own are read with a wait of their own (callers outside the evaluate task).  ``bbox``:
+        this set's tight boxes on the device when the caller has its own copy (default: the set's)."""
+        ops, D, G = self.ops, len(self), len(gt)
+        if self.hw != gt.hw:
+            raise ValueError(f"outline_agreement: a set over {self.hw} against a set over {gt.hw}")
+        if area is None:
+            area = self.area.cpu().numpy() if D else np.zeros(0)
+        if gt_area is None:
+            gt_area = gt.area.cpu().numpy() if G else np.zeros(0)
+        return _launch_outline(ops, "demia_crop_outline_agreement", (self.payload, self.room, self.offsets, self.bbox if bbox is None else bbox),
+                               D, area, (gt.payload, gt.room, gt.offsets, gt.bbox), G, gt_area, self.hw[0], self.hw[1], pairs)
 
     def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None,
               keep_words: bool = False) -> ContourSet:

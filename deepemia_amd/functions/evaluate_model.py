@@ -23,8 +23,20 @@ The bands of the detections and of the rasterised ground truth come from ``demia
 ``demia_crop_boundary_band`` in the frame being scored; their width is ``evaluation.boundary_dilation_ratio`` (default 0.02) of
 the image diagonal, or ``evaluation.boundary_width`` pixels.  With the switch off nothing of it is launched, allocated or copied.
 
+``evaluation.outline_agreement: true`` (off by default; both modes, both score frames) adds a report beside the AP tables: how
+far the outline of every matched detection lies from the outline of its annotation, in pixels.  Per image the pairs are matched
+on the host from the ``segm`` IoU table (``cocoeval.outline_match``: IoU >= ``evaluation.outline_iou``, default 0.5; not
+COCOeval's matcher), ``demia_mask_outline_agreement`` / ``demia_crop_outline_agreement`` measure them in the frame being scored and
+return integers (the definitions are stated in ``include/deepemia_hip.h``), and ``cocoeval.outline_values`` makes ASSD, the RMS
+surface distance, Hausdorff, HD95 (it saturates at 127 px), the surface Dice at ``evaluation.outline_tolerance`` px (default 2),
+the signed equivalent-diameter error and the relative area error of them.  An image with a pair costs one more device-to-host
+copy; an image without one, and a run with the switch off, launch, allocate, copy and write nothing for it.  The AP tables, the
+result files and the returned dict are the same with the switch on or off.
+
 Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task: ``bbox``, ``segm`` and, when asked for, ``boundary``), ``coco_instances_results.json``
-(``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``.  Not provided: prediction
+(``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``; with the outline report,
+``outline_agreement.csv`` (one row per matched pair, in image order, then detection order) and ``outline_summary.csv`` (one row per
+class and the row ``all``, pooled over the pairs; a class without a pair has empty value fields).  Not provided: prediction
 images (``--visualize`` only logs a warning) and, in predictor mode, the ``combo`` model pair.
 """
 from __future__ import annotations
@@ -45,7 +57,7 @@ from ..cropset import CropMaskSet
 from ..data.datasets import (MetadataCatalog, get_split_dicts, load_coco_test, load_or_create_split, read_dataset_info,
                              register_datasets, rle_counts_of)
 from ..data.models import choose_and_use_model, get_trained_model_paths
-from ..maskset import MaskOps
+from ..maskset import MaskOps, OutlineAgreement
 from ..utils.config import get_config
 from ..utils.logger_utils import system_logger
 
@@ -111,6 +123,29 @@ def boundary_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float
     if width is not None and (isinstance(width, bool) or not isinstance(width, int) or width < 1):
         raise ValueError(f"evaluation.boundary_width must be an integer >= 1, got {width!r}")
     return (float(ratio), width) if on else None
+
+
+def outline_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float, int]]:
+    """The outline-agreement switch of the ``evaluation`` key (global, or in the dataset's file): None when
+    ``evaluation.outline_agreement`` is false or absent (the default: nothing is launched, allocated, copied or written for it),
+    else ``(iou, tolerance)`` -- ``evaluation.outline_iou`` (default 0.5, a number in (0, 1]: the mask IoU from which a detection and
+    an annotation are a pair) and ``evaluation.outline_tolerance`` (default 2, an integer from 0 to 126: the surface Dice's
+    tolerance in pixels).  ValueError, with the key named, for a wrong type or range; all three keys are checked whether or not
+    the switch is on."""
+    try:
+        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
+    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
+        cfg = {}
+    on = cfg.get("outline_agreement", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"evaluation.outline_agreement must be true or false, got {on!r}")
+    iou = cfg.get("outline_iou", CE.OUTLINE_IOU)
+    if isinstance(iou, bool) or not isinstance(iou, (int, float)) or not (0.0 < float(iou) <= 1.0):
+        raise ValueError(f"evaluation.outline_iou must be a number in (0, 1], got {iou!r}")
+    tol = cfg.get("outline_tolerance", CE.OUTLINE_TOLERANCE)
+    if isinstance(tol, bool) or not isinstance(tol, int) or not (0 <= tol <= 126):
+        raise ValueError(f"evaluation.outline_tolerance must be an integer from 0 to 126, got {tol!r}")
+    return (float(iou), int(tol)) if on else None
 
 
 def read_image_bgr(path: str) -> np.ndarray:
@@ -191,6 +226,8 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     if mode == "predictor" and str(rcnn) == "combo":
         raise ValueError("the predictor mode scores one model: rcnn must be 50 or 101")
     boundary = boundary_setting(dataset_name)          # (checked before any model is loaded)
+    outline = outline_setting(dataset_name)            # (likewise)
+    report = CE.OutlineReport(*outline) if outline is not None else None
     config = get_config()
     max_dets = CE.check_max_dets((get_config(dataset_name=dataset_name).get("evaluation", {}) or {}).get("max_dets"))
     split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
@@ -204,8 +241,8 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     metadata = MetadataCatalog.get(f"{dataset_name}_train")
     if mode == "pipeline":
         tables = _new_tables(boundary)
-        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id, boundary)
-        return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline")
+        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id, boundary, report)
+        return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline", report)
     predictor, _ = choose_and_use_model(get_trained_model_paths(str(split_dir), rcnn), dataset_name, SCORE_THRESH, metadata, rcnn)
     if predictor is None:
         raise FileNotFoundError(f"no trained rcnn_r{rcnn} model for dataset {dataset_name} under {split_dir}")
@@ -237,14 +274,14 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
         for ri, out in zip(group, outs):
-            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id, boundary)
+            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id, boundary, report)
         t3 = time.perf_counter()
         t_read += t1 - t0
         t_fwd += t2 - t1
         t_score += t3 - t2
 
     return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, (t_read, t_fwd, t_score),
-                          "forwards")
+                          "forwards", report)
 
 
 def _new_tables(boundary=None) -> Dict[str, CE.EvalTables]:
@@ -255,9 +292,11 @@ def _new_tables(boundary=None) -> Dict[str, CE.EvalTables]:
     return tables
 
 
-def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, work: str):
+def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, work: str,
+                   report: Optional[CE.OutlineReport] = None):
     """COCOeval over the tables of all images, the three result files and the timing line (``work`` names what ``times[1]``
-    measured: the predictor's forwards, or the whole inference pipeline of an image)."""
+    measured: the predictor's forwards, or the whole inference pipeline of an image).  ``report``: the run's outline-agreement
+    report, when asked for -- its two files are written beside the three and its ``all`` row is logged."""
     t_read, t_fwd, t_score = times
     t0 = time.perf_counter()
     predictions = [{"image_id": recs[i]["image_id"], "instances": per_image[i]["instances"]} for i in range(len(recs))]
@@ -286,6 +325,12 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
         w.writeheader()
         for key, value in results.items():
             w.writerow({"metric": key, "value": value})
+    if report is not None:
+        t0 = time.perf_counter()
+        summary = report.write(output_dir, [to_dataset_id[i] for i in range(len(class_names))], class_names)
+        system_logger.info(f"Outline agreement over {len(report.rows)} matched pairs (IoU >= {report.iou}, NSD at {report.tolerance} px): "
+                           + ", ".join(f"{k}={v}" for k, v in zip(CE.OUTLINE_SUMMARY_HEADER, summary[-1])))
+        t_score += time.perf_counter() - t0
     n = max(1, len(recs))
     system_logger.info(f"Evaluation wall time {time.perf_counter() - t_start:.2f}s: {work} {t_fwd:.3f}s ({1e3 * t_fwd / n:.1f} ms/image), "
                        f"scoring {t_score:.3f}s ({1e3 * t_score / n:.1f} ms/image), image reads {t_read:.3f}s; "
@@ -294,9 +339,10 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
 
 
 def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
-                 boundary: Optional[Tuple[float, Optional[int]]] = None) -> dict:
+                 boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
     """Device work of one image (ground-truth masks, intersections, run lengths) and its rows of the IoU tables.  ``boundary``:
-    :func:`boundary_setting`'s value; not None adds the bands of both sides and their intersections for the ``boundary`` task."""
+    :func:`boundary_setting`'s value; not None adds the bands of both sides and their intersections for the ``boundary`` task.
+    ``report``: the run's outline-agreement report; not None measures the image's matched pairs behind the copies (one more)."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(inst.image_size) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {inst.image_size}, the annotation says {(H, W)}")
@@ -324,8 +370,18 @@ def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables]
     xywh_l, scores_l, classes_l = xywh.tolist(), scores.tolist(), classes.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter, band)
+    outline = None if report is None else (report, _outline_stage(
+        lambda pairs, da, ga: ops.outline_agreement(packed, d_bbox_t, da, g_packed, g_bbox_t, ga, pairs, W=W)))
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter, band,
+                    outline)
     return {"instances": instances}
+
+
+def _outline_stage(launch):
+    """The device stage of the outline report for one image, as ``OutlineReport.add_image`` calls it when the image has a pair:
+    ``launch(pairs, detection pixel counts, annotation pixel counts)`` enqueues the kernels on the frame being scored, and the
+    records come over in ONE copy."""
+    return lambda pairs, d_px, g_px: OutlineAgreement.from_host(launch(pairs, d_px, g_px).records.cpu().numpy())
 
 
 def _plane_bands(ops: MaskOps, boundary, H: int, W: int, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat):
@@ -340,11 +396,12 @@ def _plane_bands(ops: MaskOps, boundary, H: int, W: int, packed, d_bbox_t, class
     return CE.cross_matrix(ops, d_band, d_bbox_t, classes, g_band, g_bbox_t, g_cat, W), d_ba, g_ba
 
 
-def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None) -> None:
+def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None, outline=None) -> None:
     """One image's rows of the tasks' tables: detections (contiguous classes, float64 scores and XYWH boxes, mask pixel
     counts) against the record's annotations (``g_px`` their rasterised pixel counts, ``inter`` the intersection counts).
     ``band`` = (band intersections, detection band areas, ground-truth band areas) fills the ``boundary`` task: its IoU is
-    ``min(mask IoU, boundary IoU)``, its areas are those of ``segm``."""
+    ``min(mask IoU, boundary IoU)``, its areas are those of ``segm``.  ``outline`` = (the run's ``OutlineReport``, the image's
+    device stage): the image's pairs are matched from the ``segm`` IoU table and measured."""
     anns = rec["annotations"]
     crowd = np.asarray([int(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8)
     g_area = np.asarray([float(a["area"]) for a in anns], dtype=np.float64)
@@ -359,6 +416,8 @@ def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_
         tables["boundary"].add_image(img, d_cat, scores64, d_area.astype(np.float64), g_cat_ds, g_area, crowd, np.minimum(m_iou, b_iou))
     tables["bbox"].add_image(img, d_cat, scores64, d_box64[:, 2] * d_box64[:, 3], g_cat_ds, g_area, crowd,
                              CE.box_iou(d_box64, g_box, crowd))
+    if outline is not None:
+        outline[0].add_image(img, os.path.basename(str(rec["file_name"])), d_cat, scores64, d_area, g_cat_ds, g_px, crowd, m_iou, outline[1])
 
 
 # ---- pipeline mode -----------------------------------------------------------------------------------------------------------
@@ -440,7 +499,7 @@ class PipelineRunner:
         pipe.clear_cache()
 
 
-def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id, boundary=None):
+def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id, boundary=None, report=None):
     """Every test image through the inference pipeline and the scorer; ``(per_image, (reads, pipeline, scoring) seconds)``."""
     system_logger.info(f"Evaluating the inference pipeline on {len(recs)} test images of {dataset_name} (rcnn {rcnn}, threshold {threshold})")
     runner = PipelineRunner(dataset_name, metadata, split_dir, rcnn, threshold)
@@ -449,18 +508,21 @@ def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tabl
     t_score = 0.0
     for ri, (_, hw, packed, scores, classes, tabs) in enumerate(runner.instances([rec["file_name"] for rec in recs])):
         t0 = time.perf_counter()
-        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame, boundary)
+        per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame, boundary,
+                                              report)
         t_score += time.perf_counter() - t0
     return per_image, (runner.t_read, runner.t_pipe, t_score)
 
 
 def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None,
-                          boundary: Optional[Tuple[float, Optional[int]]] = None) -> dict:
+                          boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
     """Device work of one image's final instances (ground-truth masks, intersections, run lengths) and its rows of the IoU
     tables.  Everything the host needs comes over in ONE device-to-host copy; the detections' pixel counts and boxes are
     already on the host (``tabs``).  Dispatches on what ``final_instances`` handed over: planes are scored on planes, a
     :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no instance).  ``boundary``:
-    :func:`boundary_setting`'s value; not None adds the band launches, and their counts ride the same copy."""
+    :func:`boundary_setting`'s value; not None adds the band launches, and their counts ride the same copy.  ``report``: the run's
+    outline-agreement report; not None matches the image's pairs from that copy and, where there is one, measures them in the
+    frame being scored -- exactly one more copy."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(int(v) for v in hw) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
@@ -471,13 +533,13 @@ def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, 
         d_area, d_bbox = np.asarray(tabs[0]).astype(np.int64), np.ascontiguousarray(np.asarray(tabs[1]).reshape(-1, 4), dtype=np.int32)
     det = (np.asarray([int(c) for c in classes][:n], dtype=np.int64), np.asarray([float(v) for v in scores][:n], dtype=np.float64), d_area, d_bbox)
     if isinstance(packed, CropMaskSet) or (n == 0 and score_frame == "crops"):
-        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id, boundary)
+        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id, boundary, report)
     if n == 0:
         packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
-    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id, boundary)
+    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id, boundary, report)
 
 
-def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id, boundary=None) -> dict:
+def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id, boundary=None, report=None) -> dict:
     """``score_frame: planes``: the detections are full-frame planes and every annotation is rasterised into one."""
     anns = rec["annotations"]
     classes, _, _, d_bbox = det
@@ -497,11 +559,13 @@ def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor,
     n_t, counts_t = CE.rle_counts_launch(ops, packed, d_bbox_t, W, CE.rle_room(d_bbox))
     host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [t.reshape(-1) for t in band_t or ()]
                      + [counts_t]).cpu().numpy()                                                                                    # the ONE wait
+    outline = None if report is None else (report, _outline_stage(
+        lambda pairs, da, ga: ops.outline_agreement(packed, d_bbox_t, da, g_packed, g_bbox_t, ga, pairs, W=W)))
     return _finish_pipeline_image(rec, H, det, g_cat, host, bool(err), int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W), band_t is not None)
+                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W), band_t is not None, outline)
 
 
-def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id, boundary=None) -> dict:
+def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id, boundary=None, report=None) -> dict:
     """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too, the cross
     matrix and the run lengths read both sets' words in place, and the bands of the boundary task are sets over the same rooms.
     No ``[*, H, W/32]`` tensor exists here."""
@@ -518,16 +582,19 @@ def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det
         band_t = [CE.cross_matrix_crop(ops, d_band, classes, g_band, g_cat, det_bbox=d_bbox_t).reshape(-1), d_band.area, g_band.area]
     n_t, counts_t = CE.rle_counts_launch_crop(ops, cset, CE.rle_room(d_bbox), bbox=d_bbox_t)
     host = torch.cat([n_t, inter_t.reshape(-1), gt.area.reshape(-1), err.reshape(-1)] + band_t + [counts_t]).cpu().numpy()           # the ONE wait
+    outline = None if report is None else (report, _outline_stage(
+        lambda pairs, da, ga: cset.outline_agreement(gt, pairs, area=da, gt_area=ga, bbox=d_bbox_t)))
     return _finish_pipeline_image(rec, H, det, g_cat, host, True, int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t), boundary is not None)
+                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t), boundary is not None, outline)
 
 
 def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_err: bool, room: int, tables, to_dataset_id, encode_again,
-                           has_band: bool = False) -> dict:
+                           has_band: bool = False, outline=None) -> dict:
     """Host side of both scorers, from the one copy ``host`` = run-length sizes [n], intersections [n, G], ground-truth pixel
     counts [G], the rasteriser's error word (``has_err``), with ``has_band`` the band intersections [n, G] and the band areas of
     the detections [n] and of the ground truth [G], the run-length room: the result rows and the image's rows of the IoU
-    tables.  ``encode_again`` runs the two-pass encoder (one more wait) when the room was too small."""
+    tables.  ``encode_again`` runs the two-pass encoder (one more wait) when the room was too small.  ``outline``: as for
+    :func:`_add_image_rows`."""
     classes, scores64, d_area, _ = det
     n, G, W = len(classes), len(g_cat), int(rec["width"])
     classes_l = classes.tolist()
@@ -553,5 +620,5 @@ def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_
     xywh_l, scores_l = xywh.tolist(), scores64.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter, band)
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter, band, outline)
     return {"instances": instances}

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from functools import partial
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import os
 import numpy as np
@@ -247,6 +247,66 @@ def _launch_agglomerates(ops: "MaskOps", entry: str, source: Sequence[Optional[t
                                        _lib.ptr(res.links), _lib.ptr(res.degree), _lib.ptr(res.label), _lib.ptr(res.own),
                                        int(label_lds_cap), ops._stream()), entry)
     return res
+
+
+OUTLINE_BINS = 128                       # bins of the distance histogram of demia_mask_outline_agreement; the last one saturates
+OUTLINE_REC = 8 + OUTLINE_BINS           # int32 words of one record
+
+
+@dataclass
+class OutlineAgreement:
+    """What ``MaskOps.outline_agreement`` / ``CropMaskSet.outline_agreement`` enqueued (``demia_mask_outline_agreement``; the
+    definitions are in ``include/deepemia_hip.h``), all on the device.  ``records`` is the whole result: a fixed size per pair, so
+    one copy brings it over and :meth:`from_host` decodes it."""
+    records: torch.Tensor        # [P, 2, OUTLINE_REC] int32: per pair and direction (0: detection -> annotation, 1: the reverse)
+    pairs: np.ndarray            # [P, 2] int32 on the host: detection index, annotation index
+    det: Optional[Neighbours] = None         # the border stages' outputs (table None); they stay on the device
+    gt: Optional[Neighbours] = None
+
+    @staticmethod
+    def from_host(records_i32: np.ndarray) -> Dict[str, np.ndarray]:
+        """The host copy of :attr:`records` as int64 arrays: ``n``, ``max_d2``, ``sum_d2``, ``sum_q`` ``[P, 2]`` and ``hist``
+        ``[P, 2, 128]``."""
+        r = np.ascontiguousarray(records_i32, dtype=np.int32).reshape(-1, 2, OUTLINE_REC)
+        head = np.ascontiguousarray(r[:, :, :8]).view(np.int64).reshape(-1, 2, 4)
+        return {"n": head[:, :, 0].copy(), "max_d2": head[:, :, 1].copy(), "sum_d2": head[:, :, 2].copy(), "sum_q": head[:, :, 3].copy(),
+                "hist": r[:, :, 8:].astype(np.int64)}
+
+
+def _launch_outline(ops: "MaskOps", entry: str, det_source: Sequence[Optional[torch.Tensor]], D: int, det_area,
+                    gt_source: Sequence[Optional[torch.Tensor]], G: int, gt_area, H: int, W: int, pairs) -> OutlineAgreement:
+    """One outline-agreement stage, enqueued without a wait.  ``entry`` with the leading word-source arguments of both sides:
+    ``demia_mask_outline_agreement`` with planes ``(packed, bbox)`` or ``demia_crop_outline_agreement`` with crops ``(payload, room,
+    offsets, bbox)``.  ``det_area`` / ``gt_area``: the pixel counts on the host (they size the border points and the grid);
+    ``pairs``: ``[P, 2]`` on the host.  The four host tables go up in ONE upload.  Without a pair, or with an empty side, nothing
+    is allocated beyond the empty result and nothing is launched."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    P = int(pairs.shape[0])
+    dev = ops.device
+    if P == 0 or D == 0 or G == 0:
+        return OutlineAgreement(torch.zeros((P, 2, OUTLINE_REC), dtype=torch.int32, device=dev), pairs)
+    if pairs[:, 0].min() < 0 or pairs[:, 0].max() >= D or pairs[:, 1].min() < 0 or pairs[:, 1].max() >= G:
+        raise ValueError(f"outline_agreement: a pair names a mask outside its set ({D} detections, {G} annotations)")
+    d_area = np.ascontiguousarray(np.maximum(np.asarray(det_area, dtype=np.int64).reshape(-1), 0))
+    g_area = np.ascontiguousarray(np.maximum(np.asarray(gt_area, dtype=np.int64).reshape(-1), 0))
+    assert len(d_area) == D and len(g_area) == G
+    d_off, g_off = neighbour_offsets(d_area), neighbour_offsets(g_area)
+    chunk_off = np.zeros(2 * P + 1, dtype=np.int64)
+    n_chunks = int(ops.lib.demia_outline_chunks(d_area.ctypes.data, D, g_area.ctypes.data, G, pairs.ctypes.data, P, chunk_off.ctypes.data))
+    tab = ops.upload(np.concatenate([d_off.view(np.int32), g_off.view(np.int32), chunk_off.view(np.int32), pairs.reshape(-1)]))
+    a, b, c = 2 * (D + 1), 2 * (D + 1) + 2 * (G + 1), 2 * (D + 1) + 2 * (G + 1) + 2 * (2 * P + 1)
+    d_off_d, g_off_d, chunk_d, pairs_d = tab[:a].view(torch.int64), tab[a:b].view(torch.int64), tab[b:c].view(torch.int64), tab[c:]
+
+    def border(M: int, off: np.ndarray, off_d: torch.Tensor) -> Neighbours:
+        return Neighbours(None, torch.empty((M, 3), dtype=torch.int64, device=dev), torch.empty((M,), dtype=torch.int32, device=dev),
+                          torch.empty((max(int(off[-1]), 1),), dtype=torch.int32, device=dev), off, off_d)
+    det, gt = border(D, d_off, d_off_d), border(G, g_off, g_off_d)
+    records = torch.zeros((P, 2, OUTLINE_REC), dtype=torch.int32, device=dev)       # (the entry's contract: the caller zeroes)
+    _lib.check(getattr(ops.lib, entry)(*(_lib.ptr(t) for t in det_source), D, *(_lib.ptr(t) for t in gt_source), G, H, W,
+                                       _lib.ptr(d_off_d), _lib.ptr(det.points), _lib.ptr(det.nborder), _lib.ptr(det.sums),
+                                       _lib.ptr(g_off_d), _lib.ptr(gt.points), _lib.ptr(gt.nborder), _lib.ptr(gt.sums),
+                                       _lib.ptr(pairs_d), P, _lib.ptr(chunk_d), n_chunks, _lib.ptr(records), ops._stream()), entry)
+    return OutlineAgreement(records, pairs, det, gt)
 
 
 class PlanePool:
@@ -651,6 +711,22 @@ class MaskOps:
         _lib.check(self.lib.demia_mask_boundary_band(_lib.ptr(packed), _lib.ptr(bbox), M, H, self._w(packed) if W is None else int(W), d, _lib.ptr(out),
                                                      _lib.ptr(area), _lib.ptr(scratch), self._stream()), "demia_mask_boundary_band")
         return out, area
+
+    def outline_agreement(self, det_packed: torch.Tensor, det_bbox: torch.Tensor, det_area, gt_packed: torch.Tensor,
+                          gt_bbox: torch.Tensor, gt_area, pairs, W: Optional[int] = None) -> OutlineAgreement:
+        """Surface distances between the outlines of the pairs ``pairs`` ``[P, 2]`` (host; detection index, annotation index) of
+        two plane sets over one frame, in both directions (``demia_mask_outline_agreement``; the definitions are in
+        ``include/deepemia_hip.h``): enqueued without a wait, the device tensors returned.  ``det_bbox`` / ``gt_bbox``: any superset
+        of the tight boxes, on the device; ``det_area`` / ``gt_area``: the pixel counts on the HOST; ``W``: the frame's pixel
+        width (default: ``set_frame_width``'s rule)."""
+        D, H, wpr = det_packed.shape
+        G = int(gt_packed.shape[0])
+        if G and tuple(gt_packed.shape[1:]) != (H, wpr):
+            raise ValueError(f"outline_agreement: planes of {tuple(gt_packed.shape[1:])} against planes of {(H, wpr)}")
+        if W is not None and (int(W) + 31) // 32 != wpr:
+            raise ValueError(f"outline_agreement: planes of {wpr} words per row are not {W} pixels wide")
+        return _launch_outline(self, "demia_mask_outline_agreement", (det_packed, det_bbox), D, det_area, (gt_packed, gt_bbox), G, gt_area,
+                               H, self._w(det_packed) if W is None else int(W), pairs)
 
 
 class ContourSet:

@@ -801,6 +801,58 @@ int demia_crop_boundary_band(const uint32_t* payload, const int32_t* room, const
                              int H, int W, int d, uint32_t* band, int32_t* band_area /* [M] */, uint32_t* scratch,
                              const int64_t* scratch_off, void* stream);
 
+/* demia_mask_outline_agreement / demia_crop_outline_agreement = surface distances between the outlines of matched pairs of masks of
+ * one frame, a detection and its annotation (not in the reference program; opt-in: evaluation.outline_agreement).  The device
+ * returns integers only; the report (ASSD, RMS, Hausdorff, HD95, NSD; cocoeval.outline_values) is f64 on the host from them.
+ * The definitions, stated here once:
+ *   border pixel   a set pixel in columns < W with an unset 4-neighbour, positions outside the frame counting as unset: what the
+ *           border stage of demia_mask_neighbours writes, by the same kernel.  B(m) = the border pixels of mask m; every mask with
+ *           a pixel has one.
+ *   d2(p, T) = min over t in B(T) of (px - tx)^2 + (py - ty)^2, int64, between pixel centres, exact (coordinates go up to 65535,
+ *           so d2 can exceed 2^32).
+ *   q(d2)  = isqrt(d2 << 16) = floor(256 * sqrt(d2)): the distance in 1/256 px, rounded down, an exact integer function.
+ *   bin(d2) = min(127, the smallest integer c with c * c >= d2) = min(127, ceil(sqrt(d2))): bin 0 holds d2 = 0, bin c <= 126 the
+ *           distances in (c - 1, c] px, bin 127 SATURATES: it holds everything beyond 126 px.  The cumulative count up to c <= 126
+ *           is therefore the number of points at most c px away.
+ *   pairs [P, 2] i32 = (detection index, annotation index); a mask may be named by several pairs or by none.  Every pair is
+ *           measured in both directions: direction 0 has the detection as the SOURCE S and the annotation as the TARGET T,
+ *           direction 1 the reverse.
+ *   out [P, 2, 136] i32, one record per pair and direction, 8-byte aligned: four little-endian i64
+ *           n = |B(S)|,  max_d2 = max over p in B(S) of d2(p, T),  sum_d2 = their sum,  sum_q = the sum of q(d2(p, T)),
+ *           then hist [128] i32, hist[c] = the number of p in B(S) with bin(d2(p, T)) = c.  The CALLER zeroes out.  Where S or T has
+ *           no border point the record is n and zeros; a pair with an index outside its set leaves its records zero.
+ * Both sets' border stages write what demia_mask_neighbours' does, per set: points behind point_off ([count + 1] i64, the host's
+ * exclusive prefix sum of the pixel counts), nborder [count] i32, sums [count, 3] i64.  bbox: any superset of the tight box that is
+ * zero outside it (crops: inside the room).  H, W <= 65535.
+ * The distance kernel splits the source points of a pair-direction into shares of demia_outline_source_share() points, one
+ * workgroup per share, each thread holding 4 source points and their minima in registers; the target points pass through LDS in
+ * tiles of demia_outline_target_tile().  demia_outline_chunks fills chunk_off [2 P + 1] i64 from the HOST copies of the pixel
+ * counts and the pair list -- pair-direction 2 p + dir gets ceil(pixels of its source / share) workgroups, at least 1 and at most
+ * 256, the shares beyond are strided over -- and returns the grid, n_chunks = chunk_off[2 P]; the entries take its device copy.
+ * Workgroups reduce in LDS first and combine on the record with integer vector atomics (add, unsigned max), so the result does
+ * not depend on scheduling, on the number of workgroups, on alignment, position or the frame form.  No f32 or f64 on the device.
+ * Nothing but the two border stages' outputs and out is written.  P == 0, D == 0 or G == 0: DEMIA_OK without a launch.  Three
+ * launches (two border stages, one distance kernel), no allocation, one stream, capturable. */
+int demia_outline_source_share(void);
+int demia_outline_target_tile(void);
+int64_t demia_outline_chunks(const int64_t* det_area_host /* [D] */, int64_t D, const int64_t* gt_area_host /* [G] */, int64_t G,
+                             const int32_t* pairs_host /* [P, 2] */, int64_t P, int64_t* chunk_off /* [2 P + 1] */);
+int demia_mask_outline_agreement(const uint32_t* det, const int32_t* det_bbox, int64_t D, const uint32_t* gt, const int32_t* gt_bbox,
+                                 int64_t G, int H, int W, const int64_t* det_point_off /* [D + 1] */, uint32_t* det_points,
+                                 int32_t* det_nborder /* [D] */, int64_t* det_sums /* [D, 3] */,
+                                 const int64_t* gt_point_off /* [G + 1] */, uint32_t* gt_points, int32_t* gt_nborder /* [G] */,
+                                 int64_t* gt_sums /* [G, 3] */, const int32_t* pairs /* [P, 2] */, int64_t P,
+                                 const int64_t* chunk_off /* [2 P + 1] */, int64_t n_chunks, int32_t* out /* [P, 2, 136] */,
+                                 void* stream);
+int demia_crop_outline_agreement(const uint32_t* det_payload, const int32_t* det_room, const int64_t* det_offsets,
+                                 const int32_t* det_bbox, int64_t D, const uint32_t* gt_payload, const int32_t* gt_room,
+                                 const int64_t* gt_offsets, const int32_t* gt_bbox, int64_t G, int H, int W,
+                                 const int64_t* det_point_off /* [D + 1] */, uint32_t* det_points, int32_t* det_nborder /* [D] */,
+                                 int64_t* det_sums /* [D, 3] */, const int64_t* gt_point_off /* [G + 1] */, uint32_t* gt_points,
+                                 int32_t* gt_nborder /* [G] */, int64_t* gt_sums /* [G, 3] */, const int32_t* pairs /* [P, 2] */,
+                                 int64_t P, const int64_t* chunk_off /* [2 P + 1] */, int64_t n_chunks,
+                                 int32_t* out /* [P, 2, 136] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
