@@ -13,6 +13,7 @@ from __future__ import annotations
 import csv
 import ctypes as C
 import os
+from functools import partial
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -191,11 +192,10 @@ def rle_crop_set(ops, runs: Sequence[Sequence[int]], H: int, W: int) -> CropMask
     return CropMaskSet(ops, (H, W), room_h, tab[5 * M:], tab[:4 * M].view(M, 4), tab[4 * M:5 * M])
 
 
-def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Optional[np.ndarray], gt: torch.Tensor,
-                 gt_bbox: torch.Tensor, gt_label: Optional[np.ndarray], W: int) -> torch.Tensor:
-    """``[D, G]`` int32 on the device: ``|det_i & gt_j|``, 0 where the labels differ (``demia_mask_cross_matrix``)."""
-    D, H, _ = det.shape
-    G = int(gt.shape[0])
+def _cross(ops, D: int, G: int, det_label: Optional[np.ndarray], gt_label: Optional[np.ndarray], kernel: Callable) -> torch.Tensor:
+    """What both cross matrices share: the zeroed ``[D, G]`` output, the empty cases and the uploaded table (every detection's
+    first annotation and annotation count, the labels).  ``kernel(det labels, gt labels, first, count, out)`` is the one kernel
+    call, on device pointers (the labels 0 when there are none)."""
     out = torch.zeros((D, max(G, 1)), dtype=torch.int32, device=ops.device)
     if D == 0 or G == 0:
         return out[:, :G]
@@ -204,10 +204,20 @@ def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Opti
                           np.asarray(gt_label if gt_label is not None else np.zeros(G), dtype=np.int32)])
     tt = torch.from_numpy(tab).to(ops.device)
     lab = det_label is not None
-    _lib.check(ops.lib.demia_mask_cross_matrix(_lib.ptr(det), _lib.ptr(det_bbox), _lib.ptr(tt[2 * D:]) if lab else 0, _lib.ptr(gt),
-                                               _lib.ptr(gt_bbox), _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]),
-                                               _lib.ptr(out), D, G, H, W, ops._stream()), "demia_mask_cross_matrix")
+    kernel(_lib.ptr(tt[2 * D:]) if lab else 0, _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]), _lib.ptr(out))
     return out
+
+
+def cross_matrix(ops, det: torch.Tensor, det_bbox: torch.Tensor, det_label: Optional[np.ndarray], gt: torch.Tensor,
+                 gt_bbox: torch.Tensor, gt_label: Optional[np.ndarray], W: int) -> torch.Tensor:
+    """``[D, G]`` int32 on the device: ``|det_i & gt_j|``, 0 where the labels differ (``demia_mask_cross_matrix``)."""
+    D, H, _ = det.shape
+    G = int(gt.shape[0])
+
+    def kernel(d_lab, g_lab, first, count, out):
+        _lib.check(ops.lib.demia_mask_cross_matrix(_lib.ptr(det), _lib.ptr(det_bbox), d_lab, _lib.ptr(gt), _lib.ptr(gt_bbox), g_lab, first, count,
+                                                   out, D, G, H, W, ops._stream()), "demia_mask_cross_matrix")
+    return _cross(ops, D, G, det_label, gt_label, kernel)
 
 
 def cross_matrix_crop(ops, det: CropMaskSet, det_label: Optional[np.ndarray], gt: CropMaskSet, gt_label: Optional[np.ndarray],
@@ -215,39 +225,62 @@ def cross_matrix_crop(ops, det: CropMaskSet, det_label: Optional[np.ndarray], gt
     """:func:`cross_matrix` of two crop-framed sets over one frame (``demia_crop_cross_matrix``): the same ``[D, G]`` counts.
     ``det_bbox``: the detections' tight boxes on the device when the caller has its own copy (default: the set's)."""
     D, G = len(det), len(gt)
-    out = torch.zeros((D, max(G, 1)), dtype=torch.int32, device=ops.device)
-    if D == 0 or G == 0:
-        return out[:, :G]
-    assert det.hw == gt.hw
-    tab = np.concatenate([np.zeros(D, np.int32), np.full(D, G, np.int32),
-                          np.asarray(det_label if det_label is not None else np.zeros(D), dtype=np.int32),
-                          np.asarray(gt_label if gt_label is not None else np.zeros(G), dtype=np.int32)])
-    tt = torch.from_numpy(tab).to(ops.device)
-    lab = det_label is not None
-    _lib.check(ops.lib.demia_crop_cross_matrix(_lib.ptr(det.payload), _lib.ptr(det.room), _lib.ptr(det.offsets),
-                                               _lib.ptr(det.bbox if det_bbox is None else det_bbox), _lib.ptr(tt[2 * D:]) if lab else 0,
-                                               _lib.ptr(gt.payload), _lib.ptr(gt.room), _lib.ptr(gt.offsets), _lib.ptr(gt.bbox),
-                                               _lib.ptr(tt[3 * D:]) if lab else 0, _lib.ptr(tt), _lib.ptr(tt[D:]), _lib.ptr(out), D, G,
-                                               ops._stream()), "demia_crop_cross_matrix")
-    return out
+
+    def kernel(d_lab, g_lab, first, count, out):
+        assert det.hw == gt.hw
+        _lib.check(ops.lib.demia_crop_cross_matrix(_lib.ptr(det.payload), _lib.ptr(det.room), _lib.ptr(det.offsets),
+                                                   _lib.ptr(det.bbox if det_bbox is None else det_bbox), d_lab,
+                                                   _lib.ptr(gt.payload), _lib.ptr(gt.room), _lib.ptr(gt.offsets), _lib.ptr(gt.bbox),
+                                                   g_lab, first, count, out, D, G, ops._stream()), "demia_crop_cross_matrix")
+    return _cross(ops, D, G, det_label, gt_label, kernel)
+
+
+def _plane_rle(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int, n, off, counts) -> None:
+    M, H, _ = packed.shape
+    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(n), _lib.ptr(off), _lib.ptr(counts), M, H, W,
+                                               ops._stream()), "demia_mask_rle_colmajor")
+
+
+def _crop_rle(ops, cset: CropMaskSet, bbox: torch.Tensor, n, off, counts) -> None:
+    H, W = cset.hw
+    _lib.check(ops.lib.demia_crop_rle_colmajor(_lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets), _lib.ptr(bbox), _lib.ptr(n),
+                                               _lib.ptr(off), _lib.ptr(counts), len(cset), H, W, ops._stream()), "demia_crop_rle_colmajor")
+
+
+def _rle_two_pass(ops, M: int, kernel: Callable) -> Tuple[np.ndarray, np.ndarray]:
+    """The encoder's two passes with a wait in between: ``kernel(n, None, None)`` counts every mask's runs, the offsets are summed
+    on the host, ``kernel(None, off, counts)`` writes the runs."""
+    if M == 0:
+        return np.zeros((0,), np.uint32), np.zeros((1,), np.int64)
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    kernel(n, None, None)
+    off = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(n.cpu().numpy(), out=off[1:])
+    t_off = torch.from_numpy(off).to(ops.device)
+    counts = torch.empty((int(off[-1]),), dtype=torch.int32, device=ops.device)
+    kernel(None, t_off, counts)
+    return counts.cpu().numpy().view(np.uint32), off
+
+
+def _rle_launched(ops, M: int, room: int, kernel: Callable) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The encoder's two passes enqueued WITHOUT a wait in between: the offsets are summed on the device and cut at ``room``, so a
+    mask whose runs do not fit leaves its slot alone (the write pass checks every slot's size)."""
+    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
+    counts = torch.zeros((max(1, int(room)),), dtype=torch.int32, device=ops.device)
+    if M == 0:
+        return n, counts
+    kernel(n, None, None)
+    off = torch.zeros((M + 1,), dtype=torch.int64, device=ops.device)
+    off[1:] = torch.cumsum(n, 0, dtype=torch.int64)
+    off.clamp_(max=int(counts.shape[0]))
+    kernel(None, off, counts)
+    return n, counts
 
 
 def rle_counts(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int) -> Tuple[np.ndarray, np.ndarray]:
     """Column-major run lengths of every mask, the background run first (pycocotools' ``encode``): ``(counts uint32, offsets
     [M + 1] int64)`` on the host, mask m's runs at ``counts[offsets[m]:offsets[m + 1]]`` (``demia_mask_rle_colmajor``)."""
-    M, H, _ = packed.shape
-    if M == 0:
-        return np.zeros((0,), np.uint32), np.zeros((1,), np.int64)
-    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
-    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(n), 0, 0, M, H, W, ops._stream()),
-               "demia_mask_rle_colmajor")
-    off = np.zeros(M + 1, dtype=np.int64)
-    np.cumsum(n.cpu().numpy(), out=off[1:])
-    t_off = torch.from_numpy(off).to(ops.device)
-    counts = torch.empty((int(off[-1]),), dtype=torch.int32, device=ops.device)
-    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(t_off), _lib.ptr(counts), M, H, W,
-                                               ops._stream()), "demia_mask_rle_colmajor")
-    return counts.cpu().numpy().view(np.uint32), off
+    return _rle_two_pass(ops, int(packed.shape[0]), partial(_plane_rle, ops, packed, bbox, W))
 
 
 def rle_room(bbox: np.ndarray) -> int:
@@ -260,63 +293,22 @@ def rle_room(bbox: np.ndarray) -> int:
 
 
 def rle_counts_launch(ops, packed: torch.Tensor, bbox: torch.Tensor, W: int, room: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Both passes of ``demia_mask_rle_colmajor`` enqueued WITHOUT a wait in between: the offsets are summed on the device and
-    cut at ``room``, so a mask whose runs do not fit leaves its slot alone (the write pass checks every slot's size).  Returns
-    the device tensors ``(n_counts [M] int32, counts [room] int32)`` for the caller to fetch together with its other tables;
+    """Both passes of ``demia_mask_rle_colmajor`` enqueued without a wait in between, into ``room`` counts.  Returns the device
+    tensors ``(n_counts [M] int32, counts [room] int32)`` for the caller to fetch together with its other tables;
     :func:`rle_counts_finish` turns the host copies into ``(counts, offsets)`` or reports that the room was too small."""
-    M, H, _ = packed.shape
-    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
-    counts = torch.zeros((max(1, int(room)),), dtype=torch.int32, device=ops.device)
-    if M == 0:
-        return n, counts
-    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), _lib.ptr(n), 0, 0, M, H, W, ops._stream()),
-               "demia_mask_rle_colmajor")
-    off = torch.zeros((M + 1,), dtype=torch.int64, device=ops.device)
-    off[1:] = torch.cumsum(n, 0, dtype=torch.int64)
-    off.clamp_(max=int(counts.shape[0]))
-    _lib.check(ops.lib.demia_mask_rle_colmajor(_lib.ptr(packed), _lib.ptr(bbox), 0, _lib.ptr(off), _lib.ptr(counts), M, H, W,
-                                               ops._stream()), "demia_mask_rle_colmajor")
-    return n, counts
-
-
-def _crop_rle(ops, cset: CropMaskSet, bbox: torch.Tensor, n, off, counts) -> None:
-    H, W = cset.hw
-    _lib.check(ops.lib.demia_crop_rle_colmajor(_lib.ptr(cset.payload), _lib.ptr(cset.room), _lib.ptr(cset.offsets), _lib.ptr(bbox), _lib.ptr(n),
-                                               _lib.ptr(off), _lib.ptr(counts), len(cset), H, W, ops._stream()), "demia_crop_rle_colmajor")
+    return _rle_launched(ops, int(packed.shape[0]), room, partial(_plane_rle, ops, packed, bbox, W))
 
 
 def rle_counts_crop(ops, cset: CropMaskSet, bbox: Optional[torch.Tensor] = None) -> Tuple[np.ndarray, np.ndarray]:
     """:func:`rle_counts` of a crop-framed set (``demia_crop_rle_colmajor``): the same ``(counts, offsets)``, the masks read in
     their rooms.  ``bbox``: the tight boxes on the device when the caller has its own copy (default: the set's)."""
-    M = len(cset)
-    if M == 0:
-        return np.zeros((0,), np.uint32), np.zeros((1,), np.int64)
-    bbox = cset.bbox if bbox is None else bbox
-    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
-    _crop_rle(ops, cset, bbox, n, None, None)
-    off = np.zeros(M + 1, dtype=np.int64)
-    np.cumsum(n.cpu().numpy(), out=off[1:])
-    t_off = torch.from_numpy(off).to(ops.device)
-    counts = torch.empty((int(off[-1]),), dtype=torch.int32, device=ops.device)
-    _crop_rle(ops, cset, bbox, None, t_off, counts)
-    return counts.cpu().numpy().view(np.uint32), off
+    return _rle_two_pass(ops, len(cset), partial(_crop_rle, ops, cset, cset.bbox if bbox is None else bbox))
 
 
 def rle_counts_launch_crop(ops, cset: CropMaskSet, room: int, bbox: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`rle_counts_launch` of a crop-framed set: both passes enqueued without a wait, the offsets cut at ``room`` counts;
     the same ``(n_counts, counts)`` device tensors for :func:`rle_counts_finish`."""
-    M = len(cset)
-    n = torch.empty((M,), dtype=torch.int32, device=ops.device)
-    counts = torch.zeros((max(1, int(room)),), dtype=torch.int32, device=ops.device)
-    if M == 0:
-        return n, counts
-    bbox = cset.bbox if bbox is None else bbox
-    _crop_rle(ops, cset, bbox, n, None, None)
-    off = torch.zeros((M + 1,), dtype=torch.int64, device=ops.device)
-    off[1:] = torch.cumsum(n, 0, dtype=torch.int64)
-    off.clamp_(max=int(counts.shape[0]))
-    _crop_rle(ops, cset, bbox, None, off, counts)
-    return n, counts
+    return _rle_launched(ops, len(cset), room, partial(_crop_rle, ops, cset, cset.bbox if bbox is None else bbox))
 
 
 def rle_counts_finish(n_host: np.ndarray, counts_host: np.ndarray) -> Optional[Tuple[np.ndarray, np.ndarray]]:

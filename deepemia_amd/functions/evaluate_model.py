@@ -67,13 +67,18 @@ MODES = ("predictor", "pipeline")
 SCORE_FRAMES = ("planes", "crops")
 
 
+def _evaluation_key(dataset_name: Optional[str] = None) -> dict:
+    """The ``evaluation`` key of the configuration (global, or merged with the dataset's file); ``{}`` when it is absent."""
+    try:
+        return (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
+    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
+        return {}
+
+
 def evaluation_settings(dataset_name: Optional[str] = None) -> Tuple[str, List[int]]:
     """``(mode, max_dets)`` from the ``evaluation`` key of the configuration (global, or in the dataset's file; neither entry is
     required); ``DEEPEMIA_EVAL_MODE`` overrides the mode.  ValueError for an unknown mode or a malformed ``max_dets``."""
-    try:
-        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
-    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
-        cfg = {}
+    cfg = _evaluation_key(dataset_name)
     mode = str(os.environ.get("DEEPEMIA_EVAL_MODE") or cfg.get("mode", "predictor")).strip().lower()
     if mode not in MODES:
         raise ValueError(f"evaluation mode must be one of {MODES}, got {mode!r}")
@@ -85,10 +90,7 @@ def score_frame_setting(dataset_name: Optional[str] = None, mask_frame: Optional
     scoring reads, ``planes`` (the default) or ``crops``; the predictor mode never asks.  ValueError for an unknown value and,
     when the dataset's ``mask_frame`` is given, for a pair that does not go together: ``crops`` scores the pipeline's
     :class:`CropMaskSet` and needs ``mask_frame: crop`` or ``crop_direct``; ``planes`` scores planes and needs ``mask_frame: full``."""
-    try:
-        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
-    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
-        cfg = {}
+    cfg = _evaluation_key(dataset_name)
     frame = str(cfg.get("score_frame", "planes")).strip().lower()
     if frame not in SCORE_FRAMES:
         raise ValueError(f"evaluation.score_frame must be 'planes' or 'crops', got {frame!r}")
@@ -109,10 +111,7 @@ def boundary_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float
     ``evaluation.boundary_dilation_ratio`` (default 0.02) and ``evaluation.boundary_width`` (None, or the erosion width in pixels,
     which then replaces the ratio); ``cocoeval.boundary_width`` makes an image's ``d`` of them.  ValueError, with the key named,
     for a wrong type or range; all three keys are checked whether or not the switch is on."""
-    try:
-        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
-    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
-        cfg = {}
+    cfg = _evaluation_key(dataset_name)
     on = cfg.get("boundary_ap", False)
     if not isinstance(on, bool):
         raise ValueError(f"evaluation.boundary_ap must be true or false, got {on!r}")
@@ -132,10 +131,7 @@ def outline_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float,
     an annotation are a pair) and ``evaluation.outline_tolerance`` (default 2, an integer from 0 to 126: the surface Dice's
     tolerance in pixels).  ValueError, with the key named, for a wrong type or range; all three keys are checked whether or not
     the switch is on."""
-    try:
-        cfg = (get_config(dataset_name=dataset_name) if dataset_name else get_config()).get("evaluation", {}) or {}
-    except FileNotFoundError:        # (no configuration at all: the caller's own read reports it)
-        cfg = {}
+    cfg = _evaluation_key(dataset_name)
     on = cfg.get("outline_agreement", False)
     if not isinstance(on, bool):
         raise ValueError(f"evaluation.outline_agreement must be true or false, got {on!r}")
@@ -169,43 +165,6 @@ def _test_records(dataset_name: str, dataset_format: str, dataset_info: dict, sp
     return recs, names, {v: k for k, v in id_map.items()}
 
 
-def _gt_masks(ops: MaskOps, anns: List[dict], H: int, W: int):
-    """Packed ground-truth masks of one image in annotation order, pixel counts and boxes (device)."""
-    poly_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), list)]
-    rle_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), dict)]
-    if any(a.get("segmentation") is None for a in anns):
-        raise ValueError("ground truth without a segmentation cannot be scored for masks")
-    packed, area, bbox = CE.rasterize_polygons(ops, [anns[i]["segmentation"] for i in poly_idx], H, W)
-    if not rle_idx:
-        return packed, area, bbox
-    dense = np.stack([CE.rle_decode(rle_counts_of(anns[i]["segmentation"]), H, W) for i in rle_idx])
-    allm = torch.empty((len(anns), H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
-    if poly_idx:
-        allm[torch.tensor(poly_idx, device=ops.device)] = packed
-    allm[torch.tensor(rle_idx, device=ops.device)] = ops.from_dense(dense)
-    area, bbox = ops.area_bbox(allm)
-    return allm, area, bbox
-
-
-def _gt_crops(ops: MaskOps, anns: List[dict], H: int, W: int) -> Tuple[CropMaskSet, torch.Tensor]:
-    """The ground truth of one image as a :class:`CropMaskSet` in annotation order (its ``area`` / ``bbox``: pixel counts and
-    boxes on the device) and the rasteriser's error word: polygons are rasterised into rooms, run-length annotations are packed
-    on the host.  Nothing is waited for."""
-    if any(a.get("segmentation") is None for a in anns):
-        raise ValueError("ground truth without a segmentation cannot be scored for masks")
-    poly_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), list)]
-    rle_idx = [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), dict)]
-    polys, err = CE.rasterize_polygons_crop(ops, [anns[i]["segmentation"] for i in poly_idx], H, W)
-    if not rle_idx:
-        return polys, err
-    runs = CE.rle_crop_set(ops, [rle_counts_of(anns[i]["segmentation"]) for i in rle_idx], H, W)
-    if not poly_idx:
-        return runs, err
-    place = np.empty(len(anns), dtype=np.int64)
-    place[poly_idx + rle_idx] = np.arange(len(anns))
-    return CropMaskSet.cat([polys, runs]).select(place), err
-
-
 def _gt_box_xywh(a: dict) -> List[float]:
     """``convert_to_coco_dict``'s box: XYWH, each value ``round(float(x), 3)``."""
     b = [float(v) for v in a["bbox"]]
@@ -229,7 +188,7 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     outline = outline_setting(dataset_name)            # (likewise)
     report = CE.OutlineReport(*outline) if outline is not None else None
     config = get_config()
-    max_dets = CE.check_max_dets((get_config(dataset_name=dataset_name).get("evaluation", {}) or {}).get("max_dets"))
+    max_dets = CE.check_max_dets(_evaluation_key(dataset_name).get("max_dets"))
     split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
     category_json = Path(config["paths"]["category_json"]).expanduser().resolve()
     if visualize:
@@ -338,62 +297,187 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
     return results
 
 
-def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
-                 boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
-    """Device work of one image (ground-truth masks, intersections, run lengths) and its rows of the IoU tables.  ``boundary``:
-    :func:`boundary_setting`'s value; not None adds the bands of both sides and their intersections for the ``boundary`` task.
-    ``report``: the run's outline-agreement report; not None measures the image's matched pairs behind the copies (one more)."""
-    H, W = int(rec["height"]), int(rec["width"])
-    if tuple(inst.image_size) != (H, W):
-        raise ValueError(f"{rec['file_name']}: image is {inst.image_size}, the annotation says {(H, W)}")
-    anns = rec["annotations"]
-    n = len(inst)
-    packed = inst.packed_masks if n else torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
-    packed = packed.contiguous()
-    d_area_t, d_bbox_t = ops.area_bbox(packed)
-    g_packed, g_area_t, g_bbox_t = _gt_masks(ops, anns, H, W)
-    classes = inst.pred_classes.cpu().numpy().astype(np.int64) if n else np.zeros((0,), np.int64)
+# ---- the frame being scored -----------------------------------------------------------------------------------------------------
+class _ScoreFrame:
+    """One image's detections in the frame they are scored in and, after :meth:`ground_truth`, its annotations in the same frame:
+    the device work :func:`_score` asks for, and nothing else.  ``hw`` is the image's ``(H, W)``, ``d_bbox_t`` the detections' tight
+    boxes on the device, ``gt_area`` the annotations' pixel counts on the device.  An implementation gives ``_ground_truth``,
+    ``cross``, ``bands``, ``rle_launch``, ``rle_again``, ``outline`` and ``empty`` (the frame of an image without a detection).
+    Labels are host arrays; a method enqueues without a wait unless it says otherwise."""
+
+    def __init__(self, ops: MaskOps, H: int, W: int, d_bbox_t: torch.Tensor):
+        self.ops, self.hw, self.d_bbox_t = ops, (int(H), int(W)), d_bbox_t
+
+    def ground_truth(self, anns: List[dict]) -> List[torch.Tensor]:
+        """Build the ground-truth set in annotation order.  Returns the rasteriser's error word (a 1-element device tensor) for the
+        caller to fetch with its own tables, or nothing where the word was waited for and checked here."""
+        if any(a.get("segmentation") is None for a in anns):
+            raise ValueError("ground truth without a segmentation cannot be scored for masks")
+        return self._ground_truth(anns, [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), list)],
+                                  [i for i, a in enumerate(anns) if isinstance(a.get("segmentation"), dict)])
+
+
+class _PlaneFrame(_ScoreFrame):
+    """``score_frame: planes`` and the predictor mode: the detections are full-frame planes ``[n, H, W/32]`` and every annotation is
+    rasterised into one."""
+
+    def __init__(self, ops: MaskOps, H: int, W: int, packed: torch.Tensor, d_bbox_t: torch.Tensor):
+        super().__init__(ops, H, W, d_bbox_t)
+        self.packed = packed
+
+    @classmethod
+    def empty(cls, ops: MaskOps, H: int, W: int) -> "_PlaneFrame":
+        return cls(ops, H, W, torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device),
+                   torch.zeros((0, 4), dtype=torch.int32, device=ops.device))
+
+    def _ground_truth(self, anns, poly_idx, rle_idx):
+        ops, (H, W), err = self.ops, self.hw, []
+        polys = [anns[i]["segmentation"] for i in poly_idx]
+        if not rle_idx:
+            self.g_packed, self.gt_area, self.g_bbox_t = CE.rasterize_polygons(ops, polys, H, W, err_out=err)
+            return err
+        packed, _, _ = CE.rasterize_polygons(ops, polys, H, W)             # (run-length ground truth: its own waits)
+        dense = np.stack([CE.rle_decode(rle_counts_of(anns[i]["segmentation"]), H, W) for i in rle_idx])
+        self.g_packed = torch.empty((len(anns), H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
+        if poly_idx:
+            self.g_packed[torch.tensor(poly_idx, device=ops.device)] = packed
+        self.g_packed[torch.tensor(rle_idx, device=ops.device)] = ops.from_dense(dense)
+        self.gt_area, self.g_bbox_t = ops.area_bbox(self.g_packed)
+        return err
+
+    def cross(self, det_labels, gt_labels, det=None, gt=None) -> torch.Tensor:
+        """``[n, G]`` intersections of the detections and the annotations (or of the planes ``det`` / ``gt`` in their boxes)."""
+        return CE.cross_matrix(self.ops, self.packed if det is None else det, self.d_bbox_t, det_labels,
+                               self.g_packed if gt is None else gt, self.g_bbox_t, gt_labels, self.hw[1])
+
+    def bands(self, d: int, det_labels, gt_labels) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The boundary task at width ``d``: (band intersections ``[n, G]``, detection band areas ``[n]``, ground-truth band areas ``[G]``)."""
+        d_band, d_ba = self.ops.boundary_band(self.packed, self.d_bbox_t, d, self.hw[1])
+        g_band, g_ba = self.ops.boundary_band(self.g_packed, self.g_bbox_t, d, self.hw[1])
+        return self.cross(det_labels, gt_labels, d_band, g_band), d_ba, g_ba
+
+    def rle_launch(self, room: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return CE.rle_counts_launch(self.ops, self.packed, self.d_bbox_t, self.hw[1], room)
+
+    def rle_again(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The two-pass encoder, for a room that was too small: one more wait."""
+        return CE.rle_counts(self.ops, self.packed, self.d_bbox_t, self.hw[1])
+
+    def outline(self, pairs, d_px, g_px) -> OutlineAgreement:
+        return self.ops.outline_agreement(self.packed, self.d_bbox_t, d_px, self.g_packed, self.g_bbox_t, g_px, pairs, W=self.hw[1])
+
+
+class _CropFrame(_ScoreFrame):
+    """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too (polygons are
+    rasterised into rooms, run-length annotations are packed on the host), the cross matrix and the run lengths read both sets'
+    words in place, and the bands of the boundary task are sets over the same rooms.  No ``[*, H, W/32]`` tensor exists here."""
+
+    def __init__(self, ops: MaskOps, cset: CropMaskSet, d_bbox_t: torch.Tensor):
+        super().__init__(ops, *cset.hw, d_bbox_t)
+        self.cset = cset
+
+    @classmethod
+    def empty(cls, ops: MaskOps, H: int, W: int) -> "_CropFrame":
+        cset = CropMaskSet.empty(ops, (H, W))
+        return cls(ops, cset, cset.bbox)
+
+    def _ground_truth(self, anns, poly_idx, rle_idx):
+        ops, (H, W) = self.ops, self.hw
+        self.gt, err = CE.rasterize_polygons_crop(ops, [anns[i]["segmentation"] for i in poly_idx], H, W)
+        if rle_idx:
+            runs = CE.rle_crop_set(ops, [rle_counts_of(anns[i]["segmentation"]) for i in rle_idx], H, W)
+            if poly_idx:
+                place = np.empty(len(anns), dtype=np.int64)
+                place[poly_idx + rle_idx] = np.arange(len(anns))
+                runs = CropMaskSet.cat([self.gt, runs]).select(place)
+            self.gt = runs
+        self.gt_area = self.gt.area
+        return [err]
+
+    def cross(self, det_labels, gt_labels, det=None, gt=None) -> torch.Tensor:
+        return CE.cross_matrix_crop(self.ops, self.cset if det is None else det, det_labels, self.gt if gt is None else gt, gt_labels,
+                                    det_bbox=self.d_bbox_t)
+
+    def bands(self, d: int, det_labels, gt_labels) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        d_band, g_band = self.cset.boundary_band(d, bbox=self.d_bbox_t), self.gt.boundary_band(d)
+        return self.cross(det_labels, gt_labels, d_band, g_band), d_band.area, g_band.area
+
+    def rle_launch(self, room: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return CE.rle_counts_launch_crop(self.ops, self.cset, room, bbox=self.d_bbox_t)
+
+    def rle_again(self) -> Tuple[np.ndarray, np.ndarray]:
+        return CE.rle_counts_crop(self.ops, self.cset, bbox=self.d_bbox_t)
+
+    def outline(self, pairs, d_px, g_px) -> OutlineAgreement:
+        return self.cset.outline_agreement(self.gt, pairs, area=d_px, gt_area=g_px, bbox=self.d_bbox_t)
+
+
+def _fetch(parts: Sequence[Tuple[str, torch.Tensor]]) -> Dict[str, np.ndarray]:
+    """ONE device-to-host copy of the int32 device tensors ``parts`` = ``(name, tensor)``, in that order: ``{name: host array of the
+    tensor's shape}``.  A part that is absent is simply not in the list."""
+    host = torch.cat([t.reshape(-1) for _, t in parts]).cpu().numpy()
+    ends = np.cumsum([t.numel() for _, t in parts])
+    return {name: host[end - t.numel():end].reshape(tuple(t.shape)) for (name, t), end in zip(parts, ends)}
+
+
+def _score(frame: _ScoreFrame, rec: dict, det, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
+           boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None,
+           boxes_xywh: Optional[np.ndarray] = None) -> dict:
+    """One image through the scorer, in any frame: ground truth, cross matrix, with ``boundary`` the bands, run lengths, ONE
+    device-to-host copy, then the result rows and the image's rows of the IoU tables; with ``report`` the image's matched pairs are
+    measured in the same frame behind that (one more copy when there is a pair).  ``det`` = the detections on the host
+    (contiguous classes int64, scores float64, pixel counts int64, tight boxes ``[n, 4]`` int32).  ``boxes_xywh`` float64: the
+    detections' boxes when they have regressed ones (predictor mode); default ``toBbox`` of the run lengths."""
+    classes, scores64, d_area, d_bbox = det
+    (H, W), anns, n = frame.hw, rec["annotations"], len(classes)
+    err = frame.ground_truth(anns)
     g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
-    inter_t = CE.cross_matrix(ops, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat, W)
-    band_t = _plane_bands(ops, boundary, H, W, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat)
-    counts, off = CE.rle_counts(ops, packed, d_bbox_t, W)
-    strings = CE.rle_strings(counts, off)
-    band = tuple(t.cpu().numpy().astype(np.int64) for t in band_t) if band_t else None
-    inter = inter_t.cpu().numpy().astype(np.int64)
-    d_area = d_area_t.cpu().numpy().astype(np.int64)
-    g_px = g_area_t.cpu().numpy().astype(np.int64)
-    boxes = inst.pred_boxes.cpu().numpy().astype(np.float32).reshape(-1, 4) if n else np.zeros((0, 4), np.float32)
-    scores = inst.scores.cpu().numpy().astype(np.float32) if n else np.zeros((0,), np.float32)
-    xywh = boxes.copy()
-    xywh[:, 2] -= xywh[:, 0]
-    xywh[:, 3] -= xywh[:, 1]
-    xywh_l, scores_l, classes_l = xywh.tolist(), scores.tolist(), classes.tolist()
+    inter_t = frame.cross(classes, g_cat)
+    band_t = frame.bands(CE.boundary_width(H, W, *boundary), classes, g_cat) if boundary is not None else ()
+    n_t, counts_t = frame.rle_launch(CE.rle_room(d_bbox))
+    host = _fetch([("n_counts", n_t), ("inter", inter_t), ("g_px", frame.gt_area)] + [("err", e) for e in err]
+                  + list(zip(("band_inter", "d_band", "g_band"), band_t)) + [("counts", counts_t)])          # the ONE wait, the ONE layout
+    if "err" in host:
+        CE.check_rasterize_error(int(host["err"][0]))
+    band = tuple(host[k].astype(np.int64) for k in ("band_inter", "d_band", "g_band")) if band_t else None
+    runs = CE.rle_counts_finish(host["n_counts"], host["counts"])
+    if runs is None:
+        system_logger.debug(f"{rec['file_name']}: run lengths need more than {len(host['counts'])} counts; encoding again")
+        runs = frame.rle_again()
+    strings = CE.rle_strings(*runs)
+    xywh = CE.rle_to_bbox(runs[0], runs[1], H) if boxes_xywh is None else boxes_xywh
+    classes_l, xywh_l, scores_l = classes.tolist(), xywh.tolist(), scores64.tolist()
     instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    outline = None if report is None else (report, _outline_stage(
-        lambda pairs, da, ga: ops.outline_agreement(packed, d_bbox_t, da, g_packed, g_bbox_t, ga, pairs, W=W)))
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores.astype(np.float64), xywh.astype(np.float64), d_area, g_cat, g_px, inter, band,
-                    outline)
+    outline = None if report is None else (report, lambda pairs, d_px, g_px: OutlineAgreement.from_host(
+        frame.outline(pairs, d_px, g_px).records.cpu().numpy()))                                              # (its ONE copy)
+    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, host["g_px"].astype(np.int64),
+                    host["inter"].astype(np.int64), band, outline)
     return {"instances": instances}
 
 
-def _outline_stage(launch):
-    """The device stage of the outline report for one image, as ``OutlineReport.add_image`` calls it when the image has a pair:
-    ``launch(pairs, detection pixel counts, annotation pixel counts)`` enqueues the kernels on the frame being scored, and the
-    records come over in ONE copy."""
-    return lambda pairs, d_px, g_px: OutlineAgreement.from_host(launch(pairs, d_px, g_px).records.cpu().numpy())
-
-
-def _plane_bands(ops: MaskOps, boundary, H: int, W: int, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat):
-    """The boundary task's device work on planes, enqueued without a wait: the bands of the detections and of the rasterised ground
-    truth at the image's width ``d`` and their cross matrix -- ``(band intersections [n, G], detection band areas [n], ground-truth
-    band areas [G])`` int32 on the device, or None with the switch off."""
-    if boundary is None:
-        return None
-    d = CE.boundary_width(H, W, *boundary)
-    d_band, d_ba = ops.boundary_band(packed, d_bbox_t, d, W)
-    g_band, g_ba = ops.boundary_band(g_packed, g_bbox_t, d, W)
-    return CE.cross_matrix(ops, d_band, d_bbox_t, classes, g_band, g_bbox_t, g_cat, W), d_ba, g_ba
+def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
+                 boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
+    """Predictor mode: one image's ``Instances`` through :func:`_score` on planes.  Classes, scores, predicted boxes and the masks'
+    pixel counts and tight boxes come over in one copy; the result rows and the ``bbox`` task carry the predicted boxes (float32,
+    widened).  ``boundary`` / ``report``: as for :func:`_score`."""
+    H, W = int(rec["height"]), int(rec["width"])
+    if tuple(inst.image_size) != (H, W):
+        raise ValueError(f"{rec['file_name']}: image is {inst.image_size}, the annotation says {(H, W)}")
+    if len(inst) == 0:
+        frame = _PlaneFrame.empty(ops, H, W)
+        det, xywh = (np.zeros((0,), np.int64), np.zeros((0,), np.float64), np.zeros((0,), np.int64), np.zeros((0, 4), np.int32)), np.zeros((0, 4), np.float32)
+    else:
+        packed = inst.packed_masks.contiguous()
+        d_area_t, d_bbox_t = ops.area_bbox(packed)
+        frame = _PlaneFrame(ops, H, W, packed, d_bbox_t)
+        host = _fetch([("classes", inst.pred_classes.to(torch.int32)), ("scores", inst.scores.to(torch.float32).view(torch.int32)),
+                       ("boxes", inst.pred_boxes.to(torch.float32).reshape(-1, 4).view(torch.int32)), ("area", d_area_t), ("bbox", d_bbox_t)])
+        det = (host["classes"].astype(np.int64), host["scores"].view(np.float32).astype(np.float64), host["area"].astype(np.int64), host["bbox"])
+        xywh = host["boxes"].view(np.float32).copy()
+        xywh[:, 2] -= xywh[:, 0]
+        xywh[:, 3] -= xywh[:, 1]
+    return _score(frame, rec, det, tables, to_dataset_id, boundary, report, boxes_xywh=xywh.astype(np.float64))
 
 
 def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None, outline=None) -> None:
@@ -516,13 +600,10 @@ def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tabl
 
 def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None,
                           boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
-    """Device work of one image's final instances (ground-truth masks, intersections, run lengths) and its rows of the IoU
-    tables.  Everything the host needs comes over in ONE device-to-host copy; the detections' pixel counts and boxes are
-    already on the host (``tabs``).  Dispatches on what ``final_instances`` handed over: planes are scored on planes, a
-    :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no instance).  ``boundary``:
-    :func:`boundary_setting`'s value; not None adds the band launches, and their counts ride the same copy.  ``report``: the run's
-    outline-agreement report; not None matches the image's pairs from that copy and, where there is one, measures them in the
-    frame being scored -- exactly one more copy."""
+    """Pipeline mode: one image's final instances through :func:`_score`.  The detections' pixel counts and boxes are already on
+    the host (``tabs``), so everything the host needs comes over in the scorer's ONE copy.  Dispatches on what ``final_instances``
+    handed over: planes are scored on planes, a :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no
+    instance).  ``boundary`` / ``report``: as for :func:`_score`."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(int(v) for v in hw) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
@@ -533,92 +614,8 @@ def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, 
         d_area, d_bbox = np.asarray(tabs[0]).astype(np.int64), np.ascontiguousarray(np.asarray(tabs[1]).reshape(-1, 4), dtype=np.int32)
     det = (np.asarray([int(c) for c in classes][:n], dtype=np.int64), np.asarray([float(v) for v in scores][:n], dtype=np.float64), d_area, d_bbox)
     if isinstance(packed, CropMaskSet) or (n == 0 and score_frame == "crops"):
-        return _score_crops(ops, rec, H, W, packed if n else CropMaskSet.empty(ops, (H, W)), det, tables, to_dataset_id, boundary, report)
-    if n == 0:
-        packed = torch.zeros((0, H, (W + 31) // 32), dtype=torch.int32, device=ops.device)
-    return _score_planes(ops, rec, H, W, packed.contiguous(), det, tables, to_dataset_id, boundary, report)
-
-
-def _score_planes(ops: MaskOps, rec: dict, H: int, W: int, packed: torch.Tensor, det, tables, to_dataset_id, boundary=None, report=None) -> dict:
-    """``score_frame: planes``: the detections are full-frame planes and every annotation is rasterised into one."""
-    anns = rec["annotations"]
-    classes, _, _, d_bbox = det
-    ops.set_frame_width(W)
-    d_bbox_t = torch.from_numpy(d_bbox).to(ops.device)
-    if any(isinstance(a.get("segmentation"), dict) for a in anns):
-        g_packed, g_area_t, g_bbox_t = _gt_masks(ops, anns, H, W)          # (RLE ground truth: its own waits)
-        err = []
+        frame = _CropFrame(ops, packed, ops.upload(d_bbox)) if n else _CropFrame.empty(ops, H, W)
     else:
-        if any(a.get("segmentation") is None for a in anns):
-            raise ValueError("ground truth without a segmentation cannot be scored for masks")
-        err = []
-        g_packed, g_area_t, g_bbox_t = CE.rasterize_polygons(ops, [a["segmentation"] for a in anns], H, W, err_out=err)
-    g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
-    inter_t = CE.cross_matrix(ops, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat, W)
-    band_t = _plane_bands(ops, boundary, H, W, packed, d_bbox_t, classes, g_packed, g_bbox_t, g_cat)
-    n_t, counts_t = CE.rle_counts_launch(ops, packed, d_bbox_t, W, CE.rle_room(d_bbox))
-    host = torch.cat([n_t, inter_t.reshape(-1), g_area_t.reshape(-1)] + [e.reshape(-1) for e in err] + [t.reshape(-1) for t in band_t or ()]
-                     + [counts_t]).cpu().numpy()                                                                                    # the ONE wait
-    outline = None if report is None else (report, _outline_stage(
-        lambda pairs, da, ga: ops.outline_agreement(packed, d_bbox_t, da, g_packed, g_bbox_t, ga, pairs, W=W)))
-    return _finish_pipeline_image(rec, H, det, g_cat, host, bool(err), int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts(ops, packed, d_bbox_t, W), band_t is not None, outline)
-
-
-def _score_crops(ops: MaskOps, rec: dict, H: int, W: int, cset: CropMaskSet, det, tables, to_dataset_id, boundary=None, report=None) -> dict:
-    """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too, the cross
-    matrix and the run lengths read both sets' words in place, and the bands of the boundary task are sets over the same rooms.
-    No ``[*, H, W/32]`` tensor exists here."""
-    anns = rec["annotations"]
-    classes, _, _, d_bbox = det
-    d_bbox_t = ops.upload(d_bbox) if len(cset) else cset.bbox
-    gt, err = _gt_crops(ops, anns, H, W)
-    g_cat = np.asarray([a["category_id"] for a in anns], dtype=np.int64)
-    inter_t = CE.cross_matrix_crop(ops, cset, classes, gt, g_cat, det_bbox=d_bbox_t)
-    band_t = []
-    if boundary is not None:
-        d = CE.boundary_width(H, W, *boundary)
-        d_band, g_band = cset.boundary_band(d, bbox=d_bbox_t), gt.boundary_band(d)
-        band_t = [CE.cross_matrix_crop(ops, d_band, classes, g_band, g_cat, det_bbox=d_bbox_t).reshape(-1), d_band.area, g_band.area]
-    n_t, counts_t = CE.rle_counts_launch_crop(ops, cset, CE.rle_room(d_bbox), bbox=d_bbox_t)
-    host = torch.cat([n_t, inter_t.reshape(-1), gt.area.reshape(-1), err.reshape(-1)] + band_t + [counts_t]).cpu().numpy()           # the ONE wait
-    outline = None if report is None else (report, _outline_stage(
-        lambda pairs, da, ga: cset.outline_agreement(gt, pairs, area=da, gt_area=ga, bbox=d_bbox_t)))
-    return _finish_pipeline_image(rec, H, det, g_cat, host, True, int(counts_t.shape[0]), tables, to_dataset_id,
-                                  lambda: CE.rle_counts_crop(ops, cset, bbox=d_bbox_t), boundary is not None, outline)
-
-
-def _finish_pipeline_image(rec: dict, H: int, det, g_cat, host: np.ndarray, has_err: bool, room: int, tables, to_dataset_id, encode_again,
-                           has_band: bool = False, outline=None) -> dict:
-    """Host side of both scorers, from the one copy ``host`` = run-length sizes [n], intersections [n, G], ground-truth pixel
-    counts [G], the rasteriser's error word (``has_err``), with ``has_band`` the band intersections [n, G] and the band areas of
-    the detections [n] and of the ground truth [G], the run-length room: the result rows and the image's rows of the IoU
-    tables.  ``encode_again`` runs the two-pass encoder (one more wait) when the room was too small.  ``outline``: as for
-    :func:`_add_image_rows`."""
-    classes, scores64, d_area, _ = det
-    n, G, W = len(classes), len(g_cat), int(rec["width"])
-    classes_l = classes.tolist()
-    n_host, pos = host[:n], n
-    inter = host[pos:pos + n * G].reshape(n, G).astype(np.int64)
-    pos += n * G
-    g_px = host[pos:pos + G].astype(np.int64)
-    pos += G
-    if has_err:
-        CE.check_rasterize_error(int(host[pos]))
-        pos += 1
-    band = None
-    if has_band:
-        band = (host[pos:pos + n * G].reshape(n, G).astype(np.int64), host[pos + n * G:pos + n * G + n].astype(np.int64),
-                host[pos + n * G + n:pos + n * G + n + G].astype(np.int64))
-        pos += n * G + n + G
-    runs = CE.rle_counts_finish(n_host, host[pos:pos + room]) if n else (np.zeros((0,), np.uint32), np.zeros((1,), np.int64))
-    if runs is None:
-        system_logger.debug(f"{rec['file_name']}: run lengths need more than {room} counts; encoding again")
-        runs = encode_again()
-    strings = CE.rle_strings(*runs)
-    xywh = CE.rle_to_bbox(runs[0], runs[1], H)
-    xywh_l, scores_l = xywh.tolist(), scores64.tolist()
-    instances = [{"image_id": rec["image_id"], "category_id": classes_l[k], "bbox": xywh_l[k], "score": scores_l[k],
-                  "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
-    _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, g_px, inter, band, outline)
-    return {"instances": instances}
+        ops.set_frame_width(W)
+        frame = _PlaneFrame(ops, H, W, packed.contiguous(), torch.from_numpy(d_bbox).to(ops.device)) if n else _PlaneFrame.empty(ops, H, W)
+    return _score(frame, rec, det, tables, to_dataset_id, boundary, report)

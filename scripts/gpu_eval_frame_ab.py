@@ -8,7 +8,8 @@ lengths, the one device-to-host copy, strings and table rows).
 
 Per scorer: the first repetition and the steady ones apart (host clock around work that ends in a device synchronise), the peak
 device memory of a repetition above what its input holds (`torch.cuda.max_memory_allocated` after `reset_peak_memory_stats`,
-minus the bytes allocated before the call), the bytes of the input form itself, and whether both scorers gave the same rows.
+minus the bytes allocated before the call), the bytes of the input form itself, whether both scorers gave the same rows, and the
+digest of each scorer's rows and tables (`row_digest`: equal digests at two commits mean the scoring computed the same).
 
     python scripts/gpu_eval_frame_ab.py [size=8192] [n=900] [reps=4] [out.json]
 """
@@ -89,7 +90,7 @@ for rep in range(reps):
               f"({input_bytes[form] / 2**20:.1f} MiB)", flush=True)
 
 res = {"image": f"{size}x{size}", "instances": n, "annotations": len(anns), "reps_per_scorer": reps, "order": "alternating planes, crops",
-       "same_rows": len(set(digest.values())) == 1, "device": torch.cuda.get_device_name(0), "scorers": {}}
+       "same_rows": len(set(digest.values())) == 1, "row_digest": digest, "device": torch.cuda.get_device_name(0), "scorers": {}}
 for form, rr in runs_by.items():
     steady = [r["seconds"] for r in rr[1:]]
     res["scorers"][form] = dict(first_image_seconds=rr[0]["seconds"], steady_seconds=steady,

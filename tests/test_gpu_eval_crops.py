@@ -1,6 +1,7 @@
 """GPU tests of the evaluate task's crop scoring (``evaluation.score_frame: crops``): the polygon rasteriser into rooms, the
 cross matrix and the run-length encoder over crop-framed sets -- each bit-identical to its plane entry and to the CPU
-restatements, with canaries around everything they write -- the peak memory of one image's crop scoring, and
+restatements, with canaries around everything they write -- the peak memory of one image's crop scoring, one small image
+through the scorer's three entries (predictor mode, pipeline mode on planes and on crops: the same rows), and
 ``evaluate_model`` end to end under ``crop_direct`` / ``crops`` against ``full`` / ``planes``."""
 import gc
 import json
@@ -416,6 +417,83 @@ def test_crop_scoring_peaks_below_a_quarter_of_the_planes_and_gives_the_same_row
     inter = CE.cross_matrix_crop(ops, cset, None, gt, None).cpu().numpy()
     CE.check_rasterize_error(int(err.item()))
     assert np.array_equal(inter, inter_planes) and np.array_equal(gt.area.cpu().numpy(), g_area)
+
+
+class _FakeInstances:
+    """What the predictor mode's entry reads of an ``Instances``."""
+
+    def __init__(self, image_size, packed_masks, pred_classes, pred_boxes, scores):
+        self.image_size, self.packed_masks, self.pred_classes, self.pred_boxes, self.scores = image_size, packed_masks, pred_classes, pred_boxes, scores
+
+    def __len__(self):
+        return len(self.scores)
+
+
+def test_the_three_entries_of_the_scorer_give_the_same_rows_for_the_same_masks(ops):
+    """Five detections (one empty) against four annotations (one given as run lengths, one a crowd region, one of another class) at
+    70 x 100 (four words per row, the last one partial), boundary AP at width 2 and the outline report on: the predictor mode's
+    entry, the pipeline entry on planes and the pipeline entry on a ``CropMaskSet`` give the same ``segm`` and ``boundary`` IoU
+    tables, the same run-length strings and the same outline rows; ``bbox`` is the same on planes and crops, and for the predictor
+    entry it is ``box_iou`` of the boxes it was given."""
+    from deepemia_amd import cocoeval as CE
+    from deepemia_amd.cropset import CropMaskSet
+    from deepemia_amd.functions.evaluate_model import _gt_box_xywh, _new_tables, _score_image, _score_pipeline_image
+
+    H, W = 70, 100
+    rng = np.random.RandomState(4)
+    dense = np.zeros((5, H, W), dtype=bool)
+    dense[0, 5:30, 20:60] = True                                      # (across the first word boundary)
+    dense[1, 35:65, 60:100] = True                                    # (up to the last column, in the partial word)
+    dense[3, 40:60, 5:40] = rng.rand(20, 35) < .8                     # dense[2] stays empty
+    dense[4, 2:12, 70:95] = True
+    runs = np.zeros((H, W), dtype=bool)
+    runs[36:66, 58:98] = True
+
+    def poly(x0, y0, x1, y1):
+        return [[x0, y0, x1, y0, x1, y1, x0, y1]]
+    anns = [{"segmentation": poly(19.5, 4.5, 61.5, 31.5), "category_id": 0, "iscrowd": 0, "area": 1100.0, "bbox": [19.5, 4.5, 61.5, 31.5], "bbox_mode": "XYXY_ABS"},
+            {"segmentation": {"size": [H, W], "counts": X.encode(runs)}, "category_id": 1, "iscrowd": 0, "area": 1200.0, "bbox": [58.0, 36.0, 40.0, 30.0],
+             "bbox_mode": "XYWH_ABS"},
+            {"segmentation": poly(0.0, 38.0, 50.0, 68.0), "category_id": 0, "iscrowd": 1, "area": 1500.0, "bbox": [0.0, 38.0, 50.0, 30.0], "bbox_mode": "XYWH_ABS"},
+            {"segmentation": poly(69.5, 1.5, 95.5, 12.5), "category_id": 0, "iscrowd": 0, "area": 280.0, "bbox": [69.5, 1.5, 26.0, 11.0], "bbox_mode": "XYWH_ABS"}]
+    rec = {"file_name": "synthetic.png", "image_id": 0, "height": H, "width": W, "annotations": anns}
+    classes, scores = [0, 1, 0, 0, 1], [0.875, 0.75, 0.625, 0.5, 0.375]                       # (exact in float32)
+    boxes = np.asarray([[19.0, 4.0, 61.5, 31.0], [58.5, 34.0, 100.0, 66.0], [1.0, 2.0, 3.0, 4.5], [4.0, 39.0, 41.0, 61.0], [69.0, 1.0, 96.0, 13.0]], np.float32)
+    planes = ops.from_dense(dense)
+    ops.set_frame_width(W)
+    area, bbox = ops.area_bbox(planes)
+    tabs = (area.cpu().numpy(), bbox.cpu().numpy())
+    assert planes.shape == (5, H, 4) and tabs[0][2] == 0
+    ids, boundary = {0: 0, 1: 1}, (CE.BOUNDARY_RATIO, 2)
+    inst = _FakeInstances((H, W), planes, torch.tensor(classes, device=ops.device), torch.from_numpy(boxes).to(ops.device),
+                          torch.tensor(scores, dtype=torch.float32, device=ops.device))
+    got = {}
+    for entry in ("predictor", "planes", "crops"):
+        tables, report = _new_tables(boundary), CE.OutlineReport(0.5, 2)
+        if entry == "predictor":
+            rows = _score_image(ops, rec, inst, tables, ids, boundary, report)
+        else:
+            masks = planes if entry == "planes" else CropMaskSet.from_planes(ops, planes, W, bbox=tabs[1], area=tabs[0])
+            rows = _score_pipeline_image(ops, rec, (H, W), masks, scores, classes, tabs, tables, ids, entry, boundary, report)
+        got[entry] = (rows["instances"], tables, report)
+    want = got["planes"]
+    assert len(want[0]) == 5 and len(want[2].rows) >= 2 and list(want[1]) == ["bbox", "segm", "boundary"]
+    assert np.count_nonzero(want[1]["segm"].cat("iou")) >= 3 and (want[1]["boundary"].cat("iou") < want[1]["segm"].cat("iou")).any()
+    assert CE.rle_from_string(want[0][2]["segmentation"]["counts"]).tolist() == [H * W]      # the empty detection
+    for entry in ("predictor", "crops"):
+        inst_rows, tables, report = got[entry]
+        for task in ("segm", "boundary"):
+            assert np.array_equal(tables[task].cat("iou"), want[1][task].cat("iou")), (entry, task)
+        assert [r["segmentation"] for r in inst_rows] == [r["segmentation"] for r in want[0]], entry
+        assert [(r["category_id"], r["score"]) for r in inst_rows] == [(r["category_id"], r["score"]) for r in want[0]], entry
+        assert report.rows == want[2].rows and report.counts == want[2].counts, entry
+    assert got["crops"][0] == want[0] and np.array_equal(got["crops"][1]["bbox"].cat("iou"), want[1]["bbox"].cat("iou"))
+    xywh = boxes.copy()
+    xywh[:, 2:] -= xywh[:, :2]
+    assert [r["bbox"] for r in got["predictor"][0]] == xywh.tolist()
+    g_box = np.asarray([_gt_box_xywh(a) for a in anns], dtype=np.float64)
+    crowd = np.asarray([a["iscrowd"] for a in anns], dtype=np.uint8)
+    assert np.array_equal(got["predictor"][1]["bbox"].cat("iou"), CE.box_iou(xywh.astype(np.float64), g_box, crowd).reshape(-1))
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------------------
