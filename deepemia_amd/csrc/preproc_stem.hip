@@ -96,6 +96,168 @@ __global__ __launch_bounds__(256) void resize_h_row_kernel(const uint8_t* __rest
 //  table is not re-read per row: same bytes out, 0.3 ms SLOWER for 48 tiles -- the table reads hit L1 and the dynamic tap loop
 //  beats eight predicated taps; one short-lived workgroup per row it stays.)
 
+// ---- both Pillow passes in ONE kernel, four BYTES per pixel out (the fused front end) --------------------------------------
+// A workgroup owns `strip` output rows of one image and walks the source rows they need, in order: a source row is staged in
+// LDS as in resize_h_row_kernel (16-byte loads from the aligned address at or below its first byte; the NEXT row's first 8 KiB
+// are already in flight in registers while this one is computed), its horizontal taps go into a ring of `ksy` u8 rows in LDS
+// (the intermediate IS rounded and clipped to u8, as Pillow does), and an output row is taken from the ring as soon as its
+// last source row is in.  `tmp` never exists in HBM.
+// KS > 0 (ksx == KS, newW <= 1024): a thread owns the same (up to four) output columns for every source row of the strip, so
+// their offsets and coefficients are read ONCE into registers and the taps are KS unrolled multiply-adds; coefficients behind
+// a column's xsize are 0 (the bytes they meet lie inside the LDS allocation).  Re-reading the table per row and tap, as the
+// row kernel does, made this kernel a chain of table-load latencies: 535 us for 48 tiles, 911 us with the table transposed.
+// KS == 0: any size, tables re-read per row.  The tables must be monotone (ymin and ymin + ysize never decrease), which
+// engine.py::pil_bilinear_tables guarantees.
+// Ring layout: pixel xx sits at byte 9 + 3 xx of its row = 3 x its COLUMN xx + 3 in dst, so the four dst columns 4 t .. 4 t + 3
+// are three aligned dwords in LDS and one aligned 16-byte store in HBM; columns outside the image are computed from
+// whatever the ring holds and never stored.
+// Out: [N, PH + 6, PW + 8] pixels of four bytes (c0, c1, c2, 1); border and padding are NOT written (the buffer is zeroed once).
+constexpr int HV_PRE = 2;                        // 16-byte chunks of the next source row per thread in registers (8 KiB per row)
+
+__device__ __forceinline__ uint4 hv_load16(const uint8_t* __restrict__ src, long a, long src_bytes) {
+    if (a >= 0 && a + 16 <= src_bytes) return *reinterpret_cast<const uint4*>(src + a);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};                                     // the first / last chunk of the source: byte by byte
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+        if (a + q >= 0 && a + q < src_bytes) w[q >> 2] |= (uint32_t)src[a + q] << (8 * (q & 3));
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int KS>
+__global__ __launch_bounds__(256, 6) void resize_hv_u8x4_kernel(const uint8_t* __restrict__ src, uint32_t* __restrict__ dst, long src_bytes, int H,
+                                                             int W, int newH, int newW, int PH, int PW, const int* __restrict__ xmin,
+                                                             const int* __restrict__ xsize, const int* __restrict__ xk, int ksx,
+                                                             const int* __restrict__ ymin, const int* __restrict__ ysize,
+                                                             const int* __restrict__ yk, int ksy, int strip, int in_sz, int ring_stride) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t hv_lds[];      // [source row: in_sz | ring: ksy rows of ring_stride]
+    uint8_t* rowbuf = hv_lds;
+    uint8_t* ring = hv_lds + in_sz;
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const int y0 = blockIdx.x * strip, y1 = min(y0 + strip, newH);
+    const int DW = PW + 8, DH = PH + 6;
+    const int s0 = ymin[y0], s1 = ymin[y1 - 1] + ysize[y1 - 1];           // source rows [s0, s1)
+    const bool need_h = W != newW;
+    const int Q = (newW + 6) >> 2;                                        // quads of dst columns that hold an image pixel
+    int yy = y0, ylast = ymin[y0] + ysize[y0] - 1;
+    long b0 = ((long)n * H + s0) * W * 3;                                 // first byte of source row s
+    int mis = (int)((reinterpret_cast<unsigned long long>(src) + (unsigned long long)b0) & 15ull);
+    uint4 pre[HV_PRE];
+#pragma unroll
+    for (int j = 0; j < HV_PRE; ++j) {
+        const int o = (tid + 256 * j) * 16;
+        pre[j] = o < W * 3 + mis ? hv_load16(src, b0 - mis + o, src_bytes) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    constexpr int NPX = 4, KR = KS > 0 ? KS : 1;                          // columns tid + 256 j, j < NPX
+    int poff[NPX], pk[NPX][KR];
+    if (KS > 0) {
+#pragma unroll
+        for (int j = 0; j < NPX; ++j) {
+            const int xx = tid + 256 * j;
+            const bool on = xx < newW;
+            poff[j] = on ? xmin[xx] * 3 : 0;
+            const int cnt = on ? xsize[xx] : 0;
+#pragma unroll
+            for (int x = 0; x < KR; ++x) pk[j][x] = x < cnt ? xk[(long)xx * KS + x] : 0;
+        }
+    }
+    for (int s = s0; s < s1; ++s) {
+        const int nbytes = W * 3 + mis, cur_mis = mis;
+#pragma unroll
+        for (int j = 0; j < HV_PRE; ++j) {
+            const int o = (tid + 256 * j) * 16;
+            if (o < nbytes) *reinterpret_cast<uint4*>(rowbuf + o) = pre[j];
+        }
+        for (int o = (tid + 256 * HV_PRE) * 16; o < nbytes; o += 256 * 16)
+            *reinterpret_cast<uint4*>(rowbuf + o) = hv_load16(src, b0 - mis + o, src_bytes);
+        __syncthreads();                                                  // the row is staged
+        if (s + 1 < s1) {
+            b0 += (long)W * 3;
+            mis = (int)((reinterpret_cast<unsigned long long>(src) + (unsigned long long)b0) & 15ull);
+#pragma unroll
+            for (int j = 0; j < HV_PRE; ++j) {
+                const int o = (tid + 256 * j) * 16;
+                pre[j] = o < W * 3 + mis ? hv_load16(src, b0 - mis + o, src_bytes) : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        uint8_t* rrow = ring + (s % ksy) * ring_stride + 9;
+        if (KS > 0) {
+#pragma unroll
+            for (int j = 0; j < NPX; ++j) {
+                const int xx = tid + 256 * j;
+                if (xx < newW) {
+                    const uint8_t* p = rowbuf + cur_mis + poff[j];
+                    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+#pragma unroll
+                    for (int x = 0; x < KR; ++x) {
+                        a0 += (int)p[x * 3 + 0] * pk[j][x];
+                        a1 += (int)p[x * 3 + 1] * pk[j][x];
+                        a2 += (int)p[x * 3 + 2] * pk[j][x];
+                    }
+                    rrow[xx * 3 + 0] = (uint8_t)clip8(a0);
+                    rrow[xx * 3 + 1] = (uint8_t)clip8(a1);
+                    rrow[xx * 3 + 2] = (uint8_t)clip8(a2);
+                }
+            }
+        } else if (need_h) {
+            for (int xx = tid; xx < newW; xx += 256) {
+                const uint8_t* p = rowbuf + cur_mis + xmin[xx] * 3;
+                const int cnt = xsize[xx];
+                const int* k = xk + (long)xx * ksx;
+                int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+                for (int x = 0; x < cnt; ++x) {
+                    const int kv = k[x];
+                    a0 += (int)p[x * 3 + 0] * kv;
+                    a1 += (int)p[x * 3 + 1] * kv;
+                    a2 += (int)p[x * 3 + 2] * kv;
+                }
+                rrow[xx * 3 + 0] = (uint8_t)clip8(a0);
+                rrow[xx * 3 + 1] = (uint8_t)clip8(a1);
+                rrow[xx * 3 + 2] = (uint8_t)clip8(a2);
+            }
+        } else {
+            for (int t = tid; t < newW * 3; t += 256) rrow[t] = rowbuf[cur_mis + t];
+        }
+        __syncthreads();                                                  // ring row s is complete, the staged row is free
+        while (yy < y1 && ylast <= s) {                                   // the same for every thread of the workgroup
+            const int cnt = ysize[yy];
+            const int* k = yk + (long)yy * ksy;
+            const int r0 = ymin[yy] % ksy;
+            for (int t = tid; t < Q; t += 256) {
+                int acc[12];
+#pragma unroll
+                for (int c = 0; c < 12; ++c) acc[c] = 1 << 21;
+                int ri = r0;
+                for (int y = 0; y < cnt; ++y) {
+                    const int kv = k[y];
+                    const uint32_t* r = reinterpret_cast<const uint32_t*>(ring + ri * ring_stride) + 3 * t;
+                    const uint32_t w0 = r[0], w1 = r[1], w2 = r[2];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        acc[c] += (int)((w0 >> (8 * c)) & 255u) * kv;
+                        acc[4 + c] += (int)((w1 >> (8 * c)) & 255u) * kv;
+                        acc[8 + c] += (int)((w2 >> (8 * c)) & 255u) * kv;
+                    }
+                    ri = ri + 1 == ksy ? 0 : ri + 1;
+                }
+                uint32_t px[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    px[q] = (uint32_t)clip8(acc[3 * q]) | ((uint32_t)clip8(acc[3 * q + 1]) << 8) | ((uint32_t)clip8(acc[3 * q + 2]) << 16) | (1u << 24);
+                uint32_t* o = dst + ((long)n * DH + yy + 3) * DW + 4 * t;
+                if (4 * t >= 3 && 4 * t + 3 < newW + 3) {
+                    *reinterpret_cast<uint4*>(o) = make_uint4(px[0], px[1], px[2], px[3]);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (4 * t + q >= 3 && 4 * t + q < newW + 3) o[q] = px[q];
+                }
+            }
+            ++yy;
+            if (yy < y1) ylast = ymin[yy] + ysize[yy] - 1;
+        }
+    }
+}
+
 // vertical pass + (x - mean) + write into the zero-bordered, 4-channel f32 stem input
 __global__ void resize_v_norm_kernel(const uint8_t* __restrict__ tmp, float* __restrict__ dst, long total, int H, int newW,
                                      int newH, int PH, int PW, const int* __restrict__ ymin,
@@ -450,7 +612,74 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_kernel(const float* __restri
 // tile write and pooling, and only other workgroups hide it (1.15 -> see DESIGN §8 for the measured time).
 constexpr int SP_CPX = 36;                       // words per conv pixel in LDS: 32 channels + 4 pad
 constexpr int SP_CROW = 16 * SP_CPX;             // words per conv row in LDS
-__global__ __launch_bounds__(256, 3) void stem_pool_mfma_kernel(const float* __restrict__ in, const _Float16* __restrict__ wpl,
+// Where the 37 x 40 pixel patch comes from (as Acc<T> in roialign.hip): either source stages the SAME values -- x * s_in split
+// into planes h = half(y), l = half(y - h) -- so everything after the staging barrier is one code.
+// gy0 / gx0: bordered coordinates of the patch's first pixel (gx0 is even; negative at the top / left tiles: zeros).
+struct StemSrcF32 {                              // [N, PH + 6, PW + 8, 4] f32, border / padding / fourth channel zero
+    const float* in;
+    __device__ __forceinline__ void stage(char* sx, int n, int gy0, int gx0, int DH, int DW, float s_in, int tid) const {
+        const float4* in4 = reinterpret_cast<const float4*>(in) + (long)n * DH * DW;
+        for (int i = tid; i < SM_ROWS * SM_PW; i += 256) {
+            const int r = i / SM_PW, c = i - r * SM_PW;
+            const int gy = gy0 + r, gx = gx0 + c;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gy >= 0 && gx >= 0 && gy < DH && gx < DW) v = in4[(long)gy * DW + gx];
+            const float y[4] = {v.x * s_in, v.y * s_in, v.z * s_in, v.w * s_in};
+            f16x4 h, l;
+#pragma unroll
+            for (int c4 = 0; c4 < 4; ++c4) {
+                h[c4] = (_Float16)y[c4];
+                l[c4] = (_Float16)(y[c4] - (float)h[c4]);
+            }
+            *reinterpret_cast<f16x4*>(sx + i * 8) = h;
+            *reinterpret_cast<f16x4*>(sx + SM_ROWS * SM_PW * 8 + i * 8) = l;
+        }
+    }
+};
+struct StemSrcU8 {                               // [N, PH + 6, PW + 8] x (c0, c1, c2, flag) bytes: x = flag ? (float)c - mean : 0
+    const uint8_t* in;
+    float m0, m1, m2;
+    __device__ __forceinline__ void stage(char* sx, int n, int gy0, int gx0, int DH, int DW, float s_in, int tid) const {
+        const uint32_t* in1 = reinterpret_cast<const uint32_t*>(in) + (long)n * DH * DW;
+        // two pixels = one aligned 8-byte load (gx0 and DW are even).  ALL of a thread's loads are issued before the first
+        // conversion: as a loop of load - convert - store the staging was a chain of global-memory latencies per workgroup
+        constexpr int PAIRS = SM_ROWS * (SM_PW / 2), ROUNDS = (PAIRS + 255) / 256;
+        uint2 w[ROUNDS];
+#pragma unroll
+        for (int j = 0; j < ROUNDS; ++j) {
+            const int i = tid + 256 * j;
+            const int r = i / (SM_PW / 2), c = 2 * (i - r * (SM_PW / 2));
+            const int gy = gy0 + r, gx = gx0 + c;
+            w[j] = make_uint2(0u, 0u);
+            if (i < PAIRS && gy >= 0 && gx >= 0 && gy < DH && gx < DW) w[j] = *reinterpret_cast<const uint2*>(in1 + (long)gy * DW + gx);
+        }
+#pragma unroll
+        for (int j = 0; j < ROUNDS; ++j) {
+            const int i = tid + 256 * j;
+            if (i >= PAIRS) continue;
+            const uint32_t ww[2] = {w[j].x, w[j].y};
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const bool inside = (ww[p] >> 24) != 0u;
+                const float v0 = inside ? (float)(ww[p] & 255u) - m0 : 0.f;
+                const float v1 = inside ? (float)((ww[p] >> 8) & 255u) - m1 : 0.f;
+                const float v2 = inside ? (float)((ww[p] >> 16) & 255u) - m2 : 0.f;
+                const float y[4] = {v0 * s_in, v1 * s_in, v2 * s_in, 0.f};
+                f16x4 h, l;
+#pragma unroll
+                for (int c4 = 0; c4 < 4; ++c4) {
+                    h[c4] = (_Float16)y[c4];
+                    l[c4] = (_Float16)(y[c4] - (float)h[c4]);
+                }
+                *reinterpret_cast<f16x4*>(sx + (2 * i + p) * 8) = h;
+                *reinterpret_cast<f16x4*>(sx + SM_ROWS * SM_PW * 8 + (2 * i + p) * 8) = l;
+            }
+        }
+    }
+};
+
+template <typename Src>
+__global__ __launch_bounds__(256, 3) void stem_pool_mfma_kernel(const Src src, const _Float16* __restrict__ wpl,
                                                                 const float* __restrict__ scale, const float* __restrict__ bias,
                                                                 char* __restrict__ out, float* __restrict__ meta, int PH, int PW,
                                                                 float s_in, float s_out, int groups, int single) {
@@ -461,31 +690,23 @@ __global__ __launch_bounds__(256, 3) void stem_pool_mfma_kernel(const float* __r
     const int hb = 2 * pi0 - 1, wb = 2 * pj0 - 1;                // conv position of tile element (0, 0)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wo = lane & 15, q = lane >> 4;
-    const f16x8* wh = reinterpret_cast<const f16x8*>(wpl) + (lane & 15) * 4 + q;
-    constexpr int WPLANE = 7 * 64 * 4;
-    f16x8 bh[2][4], bl[2][4];
-#pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
-        bh[0][nb] = wh[(nb * 16) * 4];
-        bl[0][nb] = wh[WPLANE + (nb * 16) * 4];
-    }
+    // B fragments: the 8 KiB of one kernel row (both planes) come into LDS ONCE per workgroup, 32 bytes per thread, behind the
+    // input planes (rows padded to 80 bytes: conflict-free 16-byte fragment reads), one kernel row ahead in registers; every
+    // wave takes its fragments from there.  (Each wave reading its own fragments from global memory was 224 KB through L1
+    // per workgroup, 9 GB per 48 tiles from L2; 48 tiles from the f32 buffer: 979 -> 836 us.)
+    const f16x8* wg = reinterpret_cast<const f16x8*>(wpl) + tid;        // + kh * 256: unit (co = tid >> 2, q = tid & 3) of kernel row kh
+    constexpr int WPLANE = 7 * 64 * 4;                                    // f16x8 units per plane
+    constexpr int SW_ROW = 80, SW_PLANE = 64 * SW_ROW;
+    char* sw = smem + 2 * SM_ROWS * SM_PW * 8;                           // 10 KiB of the 13 KiB the input planes leave free
+    const int w_st = (tid >> 2) * SW_ROW + (tid & 3) * 16;
+    const int w_ld = (lane & 15) * SW_ROW + q * 16;                      // + nb * 16 * SW_ROW (+ SW_PLANE)
+    f16x8 wr_h = wg[0], wr_l = wg[WPLANE];
     // input patch: bordered rows 2 hb .. + 36, pixels 2 wb .. + 39 (negative at the top / left tiles: zeros)
-    const float4* in4 = reinterpret_cast<const float4*>(in) + (long)n * DH * DW;
-    for (int i = tid; i < SM_ROWS * SM_PW; i += 256) {
-        const int r = i / SM_PW, c = i - r * SM_PW;
-        const int gy = 2 * hb + r, gx = 2 * wb + c;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gy >= 0 && gx >= 0 && gy < DH && gx < DW) v = in4[(long)gy * DW + gx];
-        const float y[4] = {v.x * s_in, v.y * s_in, v.z * s_in, v.w * s_in};
-        f16x4 h, l;
-#pragma unroll
-        for (int c4 = 0; c4 < 4; ++c4) {
-            h[c4] = (_Float16)y[c4];
-            l[c4] = (_Float16)(y[c4] - (float)h[c4]);
-        }
-        *reinterpret_cast<f16x4*>(sx + i * 8) = h;
-        *reinterpret_cast<f16x4*>(sx + SM_ROWS * SM_PW * 8 + i * 8) = l;
-    }
+    src.stage(sx, n, 2 * hb, 2 * wb, DH, DW, s_in, tid);
+    *reinterpret_cast<f16x8*>(sw + w_st) = wr_h;
+    *reinterpret_cast<f16x8*>(sw + SW_PLANE + w_st) = wr_l;
+    wr_h = wg[256];
+    wr_l = wg[WPLANE + 256];
     __syncthreads();
     f32x4 acc[4][4];
 #pragma unroll
@@ -496,12 +717,19 @@ __global__ __launch_bounds__(256, 3) void stem_pool_mfma_kernel(const float* __r
     constexpr int XL = SM_ROWS * SM_PW * 8;
 #pragma unroll
     for (int kh = 0; kh < 7; ++kh) {
-        const int cur = kh & 1, nxt = cur ^ 1;
-        if (kh + 1 < 7) {
+        f16x8 bh[4], bl[4];
 #pragma unroll
-            for (int nb = 0; nb < 4; ++nb) {
-                bh[nxt][nb] = wh[((kh + 1) * 64 + nb * 16) * 4];
-                bl[nxt][nb] = wh[WPLANE + ((kh + 1) * 64 + nb * 16) * 4];
+        for (int nb = 0; nb < 4; ++nb) {
+            bh[nb] = *reinterpret_cast<const f16x8*>(sw + nb * 16 * SW_ROW + w_ld);
+            bl[nb] = *reinterpret_cast<const f16x8*>(sw + SW_PLANE + nb * 16 * SW_ROW + w_ld);
+        }
+        if (kh + 1 < 7) {
+            __syncthreads();                                    // every wave holds its fragments of kernel row kh
+            *reinterpret_cast<f16x8*>(sw + w_st) = wr_h;
+            *reinterpret_cast<f16x8*>(sw + SW_PLANE + w_st) = wr_l;
+            if (kh + 2 < 7) {
+                wr_h = wg[(kh + 2) * 256];
+                wr_l = wg[WPLANE + (kh + 2) * 256];
             }
         }
 #pragma unroll
@@ -512,12 +740,13 @@ __global__ __launch_bounds__(256, 3) void stem_pool_mfma_kernel(const float* __r
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
                 f32x4 c = acc[i][nb];
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[cur][nb], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[cur][nb], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[cur][nb], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[nb], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[nb], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[nb], c, 0, 0, 0);
                 acc[i][nb] = c;
             }
         }
+        if (kh + 1 < 7) __syncthreads();                        // kernel row kh + 1 is in LDS
     }
     float* cv = reinterpret_cast<float*>(smem);
     float sc4[4], bs4[4];
@@ -691,6 +920,49 @@ extern "C" int demia_resize_v_norm(const uint8_t* tmp, void* dst, int N, int H, 
     return DEMIA_OK;
 }
 
+// LDS of resize_hv_u8x4_kernel: the staged source row (as resize_h_row_kernel's) and `ksy` ring rows of 3 (newW + 3) bytes in whole quads
+static inline long hv_in_bytes(int W) { return ((long)W * 3 + 32 + 15) & ~15L; }
+static inline long hv_ring_stride(int newW) { return ((long)((newW + 6) >> 2) * 12 + 15) & ~15L; }
+
+extern "C" int64_t demia_resize_hv_fits(int W, int newW, int ksy) {
+    if (W <= 0 || newW <= 0 || ksy <= 0) return 0;
+    const long smem = hv_in_bytes(W) + (long)ksy * hv_ring_stride(newW);
+    return smem <= 60 * 1024 ? smem : 0;                                  // the default LDS window, as demia_resize_h_u8
+}
+
+extern "C" int demia_resize_hv_u8x4(const uint8_t* src, void* dst, int N, int H, int W, int newH, int newW, int PH, int PW,
+                                    const int32_t* xmin, const int32_t* xsize, const int32_t* xk, int ksx, const int32_t* ymin,
+                                    const int32_t* ysize, const int32_t* yk, int ksy, int strip, void* stream) {
+    DEMIA_REQUIRE(src && dst && ymin && ysize && yk && ksy > 0, "args");
+    DEMIA_REQUIRE(W == newW || (xmin && xsize && xk && ksx > 0), "horizontal tables");
+    DEMIA_REQUIRE(PH >= newH && PW >= newW && PH % 32 == 0 && PW % 32 == 0, "padded size");
+    DEMIA_REQUIRE((reinterpret_cast<unsigned long long>(dst) & 15ull) == 0, "dst is 16-byte aligned");
+    DEMIA_REQUIRE(N <= 65535, "N");
+    if ((long)N * newH * newW == 0) return DEMIA_OK;
+    const long smem = demia_resize_hv_fits(W, newW, ksy);
+    DEMIA_REQUIRE(smem > 0, "a source row and the ring do not fit the LDS window: use demia_resize_h_u8 + demia_resize_v_norm");
+    if (strip <= 0) {
+        // A strip of R rows walks R * H / newH + ksy source rows; the grid runs in rounds of as many workgroups as fit the chip
+        // (256 CUs x the workgroups the LDS admits, at most the 6 its ~106 scalar registers admit).  Take the R in 8 .. 32 with
+        // the fewest source rows per CU: 25 for 48 tiles of 2048^2 -> 800^2 (32 strips x 48 = 1536 workgroups, one round).
+        const long per_cu = 160 * 1024 / smem;
+        const long slots = 256 * (per_cu < 1 ? 1 : (per_cu > 6 ? 6 : per_cu));
+        double best = 0.;
+        for (int r = 8; r <= 32; ++r) {
+            const long wgs = (long)N * cdiv(newH, r);
+            const double cost = (double)((wgs + slots - 1) / slots) * ((double)r * H / newH + ksy);
+            if (strip <= 0 || cost < best) { best = cost; strip = r; }
+        }
+    }
+    const int ks = (W != newW && newW <= 1024 && (ksx == 3 || ksx == 5 || ksx == 7)) ? ksx : 0;   // Pillow's bilinear tables: 2 ceil(scale) + 1 taps
+    auto kern = ks == 3 ? resize_hv_u8x4_kernel<3> : ks == 5 ? resize_hv_u8x4_kernel<5> : ks == 7 ? resize_hv_u8x4_kernel<7> : resize_hv_u8x4_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(cdiv(newH, strip), N), dim3(256), (size_t)smem, (hipStream_t)stream, src, (uint32_t*)dst,
+                       (long)N * H * W * 3, H, W, newH, newW, PH, PW, xmin, xsize, xk, ksx, ymin, ysize, yk, ksy, strip,
+                       (int)hv_in_bytes(W), (int)hv_ring_stride(newW));
+    DEMIA_CHECK_LAUNCH("resize_hv_u8x4_kernel");
+    return DEMIA_OK;
+}
+
 extern "C" int demia_stem_conv(const void* in, const void* w, const float* scale, const float* bias, void* mid, int N,
                                int PH, int PW, int dtype, void* stream) {
     DEMIA_REQUIRE(in && w && scale && bias && mid, "args");
@@ -736,10 +1008,27 @@ extern "C" int demia_stem_pool_mfma(const float* in, const void* w_planes, const
     DEMIA_REQUIRE(N <= 65535, "N");
     const int Hp = PH / 4, Wp = PW / 4;
     if ((long)N * Hp * Wp == 0) return DEMIA_OK;
-    hipLaunchKernelGGL(stem_pool_mfma_kernel, dim3(cdiv(Wp, 7), cdiv(Hp, 7), N), dim3(256), 0, (hipStream_t)stream, in,
+    hipLaunchKernelGGL(stem_pool_mfma_kernel<StemSrcF32>, dim3(cdiv(Wp, 7), cdiv(Hp, 7), N), dim3(256), 0, (hipStream_t)stream, StemSrcF32{in},
                        reinterpret_cast<const _Float16*>(w_planes), scale, bias, (char*)out, out_meta, PH, PW, s_in, s_out, groups,
                        single);
     DEMIA_CHECK_LAUNCH("stem_pool_mfma_kernel");
+    return DEMIA_OK;
+}
+
+extern "C" int demia_stem_pool_mfma_u8(const uint8_t* in, const float* mean3, const void* w_planes, const float* scale, const float* bias,
+                                       void* out, float* out_meta, int N, int PH, int PW, float s_in, float s_out, int groups, int single,
+                                       void* stream) {
+    DEMIA_REQUIRE(in && mean3 && w_planes && scale && bias && out && out_meta && s_in > 0.f && s_out > 0.f, "args");
+    DEMIA_REQUIRE((reinterpret_cast<unsigned long long>(in) & 7ull) == 0, "in is 8-byte aligned");
+    DEMIA_REQUIRE(PH % 32 == 0 && PW % 32 == 0, "padded size");
+    DEMIA_REQUIRE(groups <= 1 || groups == N, "scale groups: one per image");
+    DEMIA_REQUIRE(N <= 65535, "N");
+    const int Hp = PH / 4, Wp = PW / 4;
+    if ((long)N * Hp * Wp == 0) return DEMIA_OK;
+    hipLaunchKernelGGL(stem_pool_mfma_kernel<StemSrcU8>, dim3(cdiv(Wp, 7), cdiv(Hp, 7), N), dim3(256), 0, (hipStream_t)stream,
+                       StemSrcU8{in, mean3[0], mean3[1], mean3[2]}, reinterpret_cast<const _Float16*>(w_planes), scale, bias, (char*)out,
+                       out_meta, PH, PW, s_in, s_out, groups, single);
+    DEMIA_CHECK_LAUNCH("stem_pool_mfma_u8_kernel");
     return DEMIA_OK;
 }
 

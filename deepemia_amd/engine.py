@@ -318,6 +318,9 @@ class MaskRCNNEngine:
         self.roi_order = os.environ.get("DEEPEMIA_ROI_ORDER", "0") == "1"
         # (A/B switch, default ON) the RPN predictor fused into the RPN conv's epilogue (f16x2 only; see ``rpn``)
         self.rpn_fused = os.environ.get("DEEPEMIA_RPN_FUSED", "1") != "0"
+        # (A/B switch, default ON) the front end in two launches: ``forward`` resizes in one kernel into four BYTES per pixel and the
+        # fused stem reads them (``preprocess_u8x4``); ``preprocess`` itself keeps its contract, the f32 buffer
+        self.front_end_fused = True
         self.conv_events = None   # bench hook: list of (start_event, end_event, algorithmic_flops, kernel kind, algorithmic_bytes)
         self.unmatched_keys: List[str] = []
         self._used = set()
@@ -733,10 +736,48 @@ class MaskRCNNEngine:
                    "demia_resize_v_norm")
         return dst, newh, neww, ph, pw
 
+    def front_end_fits(self, h: int, w: int) -> bool:
+        """Whether ``forward`` takes the two-launch front end for [*, h, w, 3] images: the P32 path with the fused stem, the switch
+        on, and a source row plus the ring of resized rows inside the resize kernel's LDS window."""
+        if not (self.p32 and self.stem_mode == "fused" and self.front_end_fused):
+            return False
+        t = self._resize_tables(h, w)
+        return int(self.lib.demia_resize_hv_fits(w, t["neww"], t["ksy"])) > 0
+
+    def preprocess_u8x4(self, images: torch.Tensor):
+        """``preprocess`` in ONE launch, four bytes per pixel: [B, PH + 6, PW + 8, 4] u8 = (c0, c1, c2, flag) in the geometry of the
+        f32 stem input, (newh, neww, PH, PW).  Border and padding keep the zeros (flag 0) of the arena buffer's allocation.
+        Only where ``front_end_fits``; ``backbone`` takes the buffer as it takes the f32 one."""
+        b, h, w, _ = images.shape
+        t = self._resize_tables(h, w)
+        newh, neww = t["newh"], t["neww"]
+        ph, pw = (newh + 31) // 32 * 32, (neww + 31) // 32 * 32
+        self._begin_forward((b, h, w), ph, pw)              # the first stage of every forward
+        dst = self._scratch(b * (ph + 6) * (pw + 8) * 4, torch.uint8, zero=True).view(b, ph + 6, pw + 8, 4)
+        _lib.check(self.lib.demia_resize_hv_u8x4(_lib.ptr(images), _lib.ptr(dst), b, h, w, newh, neww, ph, pw, _lib.ptr(t["xm"]),
+                                                 _lib.ptr(t["xs"]), _lib.ptr(t["xk"]), t["ksx"], _lib.ptr(t["ym"]), _lib.ptr(t["ys"]),
+                                                 _lib.ptr(t["yk"]), t["ksy"], 0, self._stream()), "demia_resize_hv_u8x4")
+        return dst, newh, neww, ph, pw
+
+    @staticmethod
+    def decode_u8x4(buf: torch.Tensor) -> torch.Tensor:
+        """The f32 stem input that a ``preprocess_u8x4`` buffer stands for (the rule of ``include/deepemia_hip.h``); debugging only."""
+        x = torch.zeros(buf.shape, dtype=torch.float32, device=buf.device)
+        mean = torch.tensor(PIXEL_MEAN, dtype=torch.float32, device=buf.device)
+        x[..., :3] = torch.where(buf[..., 3:] != 0, buf[..., :3].to(torch.float32) - mean, torch.zeros((), dtype=torch.float32, device=buf.device))
+        return x
+
     def backbone(self, xin: torch.Tensor, ph: int, pw: int) -> Dict[str, torch.Tensor]:
         b = xin.shape[0]
         st = self._stream()
-        if self.p32:
+        if self.p32 and xin.dtype == torch.uint8:
+            # the fused stem on the bytes of ``preprocess_u8x4``: the same planes as from the f32 buffer, a quarter of the bytes staged
+            x = self.new_p32((b, ph // 4, pw // 4, 64))
+            mean = (C.c_float * 3)(*PIXEL_MEAN)
+            _lib.check(self.lib.demia_stem_pool_mfma_u8(_lib.ptr(xin), mean, _lib.ptr(self.stem_planes), _lib.ptr(self.stem_scale_mfma),
+                                                        _lib.ptr(self.stem_bias), _lib.ptr(x.buf), _lib.ptr(x.meta), b, ph, pw, self.stem_s_in,
+                                                        p32.plane_scale(self.stem_bound), x.groups, int(self.single_plane), st), "demia_stem_pool_mfma_u8")
+        elif self.p32:
             if self.stem_mode == "fused":
                 # stem + max pool in one launch, planes out: the 2 GB f32 stem output of a 48-tile batch is never written
                 x = self.new_p32((b, ph // 4, pw // 4, 64))
@@ -921,7 +962,7 @@ class MaskRCNNEngine:
         images = images.contiguous()
         b, h, w, _ = images.shape
         self._amax_buf = None            # f16x2r: a fresh (zeroed) pool of |activation| bounds per forward
-        xin, newh, neww, ph, pw = self.preprocess(images)
+        xin, newh, neww, ph, pw = self.preprocess_u8x4(images) if self.front_end_fits(h, w) else self.preprocess(images)
         feats = self.backbone(xin, ph, pw)
         props, pscores, pcount = self.rpn(feats, newh, neww)
         pooled = self.roi_align(feats, props, pcount, 7)
@@ -932,7 +973,7 @@ class MaskRCNNEngine:
         out_boxes, valid, packed, bbox = self.paste(mask_prob, det_boxes, det_classes, det_count, newh, neww, h, w)
         res = RawDetections(out_boxes, det_scores, det_classes, valid, det_count, packed, h, w, bbox)
         if keep_intermediates:
-            res.dbg = dict(xin=xin, feats=feats, props=props, pscores=pscores, pcount=pcount, pooled=pooled,
+            res.dbg = dict(xin=self.decode_u8x4(xin) if xin.dtype == torch.uint8 else xin, feats=feats, props=props, pscores=pscores, pcount=pcount, pooled=pooled,
                            logits=logits, det_boxes=det_boxes, mpooled=mpooled, mask_prob=mask_prob,
                            heads=self._dbg_heads, newh=newh, neww=neww)
         return res

@@ -220,6 +220,25 @@ int demia_stem_conv_mfma(const float* in, const void* w_planes, const float* sca
  * s_out / groups as demia_maxpool3x3s2_p32 (s_out = the planes' power-of-two scale from the a-priori bound of the stem output). */
 int demia_stem_pool_mfma(const float* in, const void* w_planes, const float* scale, const float* bias, void* out, float* out_meta,
                          int N, int PH, int PW, float s_in, float s_out, int groups, int single, void* stream);
+/* The fused front end: both Pillow passes in ONE launch, and the stem + pool reading its bytes.
+ *   dst  [N, PH + 6, PW + 8] pixels of four BYTES (c0, c1, c2, flag) in the geometry of the f32 stem input above.
+ *        Decoding rule: x[c] = flag ? (float)c_c - mean[c] : 0 for c < 3, x[3] = 0 -- bit for bit the f32 buffer that
+ *        demia_resize_h_u8 + demia_resize_v_norm write.  The kernel stores (c0, c1, c2, 1) for the newH x newW image pixels
+ *        at (+3, +3) and NOTHING else: border and padding are recognised by flag = 0 in a buffer the caller zeroed once.
+ *        dst is 16-byte aligned.  `tmp` does not exist: the horizontally resized rows (rounded and clipped to u8, as Pillow's)
+ *        live in an LDS ring of ksy rows.  W == newW: no horizontal pass (x tables may be NULL).  The tables are monotone.
+ *   strip  output rows per workgroup; <= 0: chosen from the grid size.
+ * demia_resize_hv_fits: the kernel's LDS bytes, or 0 when a source row of W pixels and ksy ring rows of newW pixels do not
+ * fit its 60 KiB window -- then demia_resize_hv_u8x4 fails and the two launches above are the path. */
+int64_t demia_resize_hv_fits(int W, int newW, int ksy);
+int demia_resize_hv_u8x4(const uint8_t* src, void* dst, int N, int H, int W, int newH, int newW, int PH, int PW,
+                         const int32_t* xmin, const int32_t* xsize, const int32_t* xk, int ksx,
+                         const int32_t* ymin, const int32_t* ysize, const int32_t* yk, int ksy, int strip, void* stream);
+/* demia_stem_pool_mfma on that buffer (8-byte aligned): staging decodes by the rule above with the host array mean3, then
+ * the same multiply by s_in and plane split; planes and meta are bit-identical to demia_stem_pool_mfma on the f32 buffer. */
+int demia_stem_pool_mfma_u8(const uint8_t* in, const float* mean3, const void* w_planes, const float* scale, const float* bias,
+                            void* out, float* out_meta, int N, int PH, int PW, float s_in, float s_out, int groups, int single,
+                            void* stream);
 int demia_maxpool3x3s2(const void* in, void* out, int N, int H, int W, int C, int dtype, void* stream);
 /* the same pool from an f32 input into a P32 buffer scaled with the power of two `s` (the caller derives it from the
  * stem's a-priori bound); out_meta receives {max |out| (atomic max; zero it first), s} -- one pair (groups <= 1) or one
