@@ -19,7 +19,8 @@
 //   from the MEASURED amax of its input.
 //
 // Kernel shape (CDNA4, 64-wide waves): one workgroup of 8 waves (512 threads, <= 256 VGPRs) per CU computes a
-// BM x BN tile, BM = WM * TM * 32, BN = WN * TN * 32 (256 x 256 for the big layers), accumulators in registers.
+// BM x BN tile, BM = WM * TM * 32, BN = WN * TN * 32 (256 x 256 for the big layers), accumulators in registers; the
+// 256 x 256 tile of the large-K layers and of the fused-head layer runs on 16 waves (1024 threads, <= 128 VGPRs).
 // Both operands go global -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no staging
 // registers, no ds_write); the LDS image is linear (DMA writes lane-linear) and bank conflicts of the ds_read_b128
 // fragment reads are removed by an XOR swizzle applied to the SOURCE address of the DMA and to the read address
@@ -264,9 +265,10 @@ __device__ __forceinline__ void p32_epilogue(const ConvQ& p, const GroupScales& 
     constexpr int BN = WN * TN * 32;
     const int tid = threadIdx.x, lane = tid & 63;
     constexpr int EROW = BN * 4 + 16;
-    constexpr int GPR = BN / 8, RSTEP = 512 / GPR, ITEMS = WM * 32 / RSTEP;
+    constexpr int NT = WM * WN * 64;                              // threads of the workgroup
+    constexpr int GPR = BN / 8, RSTEP = NT / GPR, ITEMS = WM * 32 / RSTEP;
     // (the launch sizes the LDS for max(two stages, this image))
-    static_assert(512 % GPR == 0 && (WM * 32) % RSTEP == 0, "epilogue split");
+    static_assert(NT % GPR == 0 && (WM * 32) % RSTEP == 0, "epilogue split");
     constexpr int BM_ = WM * TM * 32;
     static_assert(!HEAD || BN == 256, "the fused head needs a 256-wide tile");
     const bool planes_out = !HEAD && !p.out_f32;
@@ -494,11 +496,20 @@ __device__ __forceinline__ void p32_epilogue_planes(const ConvQ& p, const GroupS
     const int line = lg % TN;                                // which of the wave's TN lines (32 channels) per row
     const int r_first = (lg / TN) * 2 + rs;                  // row of item 0 inside the wave's 32-row block
     const int co = n0 + ((wn * TN + line) * 4 + cj) * 8;
+    // Sixteen waves have 128 registers each.  With TN = 2 (64 accumulators, four items per pass) two things change -- neither
+    // touches a result: scale and bias are loaded when the first tile-row has left its 32 accumulator registers, not in front
+    // of it; and the residual lines are requested RES_AHEAD = 2 items ahead into a ring of two register sets (16 registers),
+    // not a whole pass of four ahead (32 beside the 32 of the pass being worked on).  Per CU that is 16 waves x 4 KiB in
+    // flight, what eight waves x 8 KiB are.  The waits stay counted: the code is as straight as before.
+    constexpr bool TIGHT = WM * WN == 16 && TN == 2;
+    constexpr int RES_AHEAD = 2;
     float sc[8], bs[8];
+    if constexpr (!TIGHT) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        sc[q] = p.scale ? p.scale[co + q] : 1.0f;
-        bs[q] = p.bias ? p.bias[co + q] : 0.0f;
+        for (int q = 0; q < 8; ++q) {
+            sc[q] = p.scale ? p.scale[co + q] : 1.0f;
+            bs[q] = p.bias ? p.bias[co + q] : 0.0f;
+        }
     }
     const bool sigmoid_on = p.act == DEMIA_ACT_SIGMOID;
     const float act_lo = p.act == DEMIA_ACT_RELU ? 0.f : -INFINITY;
@@ -533,18 +544,24 @@ __device__ __forceinline__ void p32_epilogue_planes(const ConvQ& p, const GroupS
         return r;
     };
     u32x4 rh[ITEMS], rl[ITEMS];                              // as loaded: [0] = this lane's piece of row r, [1] = of row r + 1
+    auto load_res_item = [&](int i, int k, int slot) {        // the lines of item k of pass i into register set `slot`
+        const int mp = row_of(i, k) - rs;                    // row r of the pair
+        if (P32_ABLATE & 32) { rh[slot] = u32x4{0, 0, 0, 0}; rl[slot] = rh[slot]; return; }
+        rh[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, res_off(mp), 0, P32_RES_AUX);
+        rl[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, res_off(mp + 1), 0, P32_RES_AUX);
+    };
     auto load_res = [&](int i) {
 #pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-            const int mp = row_of(i, k) - rs;                // row r of the pair
-            if (P32_ABLATE & 32) { rh[k] = u32x4{0, 0, 0, 0}; rl[k] = rh[k]; continue; }
-            rh[k] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, res_off(mp), 0, P32_RES_AUX);
-            rl[k] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, res_off(mp + 1), 0, P32_RES_AUX);
-        }
+        for (int k = 0; k < ITEMS; ++k) load_res_item(i, k, k);
     };
     float vmax0 = 0.f, vmax1 = 0.f, vmax2 = 0.f;
     if (P32_ABLATE & 512) return;                            // timing-only: everything but the passes
-    load_res(0);
+    if constexpr (TIGHT) {
+#pragma unroll
+        for (int j = 0; j < RES_AHEAD; ++j) load_res_item(j / ITEMS, j % ITEMS, j);
+    } else {
+        load_res(0);
+    }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         // (compiler barriers only: the reads of pass i - 1 are issued before these writes, the writes before the reads below)
@@ -553,16 +570,33 @@ __device__ __forceinline__ void p32_epilogue_planes(const ConvQ& p, const GroupS
         write_tile_row(i, reinterpret_cast<float*>(wsm));
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        f16x8 ch[ITEMS], cl[ITEMS];
+        if constexpr (TIGHT) {
+            if (i == 0) {
 #pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-            // a lane of row r loaded h_j(r) and h_j(r + 1), its partner l_j(r) and l_j(r + 1)
-            ch[k] = __builtin_bit_cast(f16x8, from_below(rh[k], rl[k]));     // row r: own first load; row r + 1: the partner's second
-            cl[k] = __builtin_bit_cast(f16x8, from_above(rl[k], rh[k]));     // row r: the partner's first; row r + 1: own second
+                for (int q = 0; q < 8; ++q) {
+                    sc[q] = p.scale ? p.scale[co + q] : 1.0f;
+                    bs[q] = p.bias ? p.bias[co + q] : 0.0f;
+                }
+            }
         }
-        if (i + 1 < TM) load_res(i + 1);
+        f16x8 ch[ITEMS], cl[ITEMS];
+        // a lane of row r loaded h_j(r) and h_j(r + 1), its partner l_j(r) and l_j(r + 1)
+        auto exchange = [&](int k, int slot) {
+            ch[k] = __builtin_bit_cast(f16x8, from_below(rh[slot], rl[slot]));     // row r: own first load; row r + 1: the partner's second
+            cl[k] = __builtin_bit_cast(f16x8, from_above(rl[slot], rh[slot]));     // row r: the partner's first; row r + 1: own second
+        };
+        if constexpr (!TIGHT) {
+#pragma unroll
+            for (int k = 0; k < ITEMS; ++k) exchange(k, k);
+            if (i + 1 < TM) load_res(i + 1);
+        }
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
+            if constexpr (TIGHT) {
+                const int j = i * ITEMS + k, slot = j % RES_AHEAD;
+                exchange(k, slot);
+                if (j + RES_AHEAD < TM * ITEMS) load_res_item((j + RES_AHEAD) / ITEMS, (j + RES_AHEAD) % ITEMS, slot);
+            }
             const int lr = r_first + k * RPI;
             const int m = row_of(i, k);
             const float4 x0 = *reinterpret_cast<const float4*>(wsm + lr * (LDW * 4) + (line * 4 + cj) * 32);
@@ -816,12 +850,16 @@ constexpr int EPI_GENERIC = 0, EPI_PLANES = 1, EPI_HEAD = 2, EPI_HEAD_PLANES = 3
 // same MFMAs and fragment reads per product, HALF the DMA bytes and half the barriers.  The fragment addresses are the ones
 // the two-plane kernel uses for its planes (chunk = half * 4 + (lane >> 4)), so a stage is consumed as two K sub-steps.
 template <int WM, int WN, int TM, int TN, bool M16 = true, int EPI = EPI_PLANES, int NST = 2, bool HK = false>
-__global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 2 : 1) void conv_p32_kernel(const ConvQ p) {
+__global__ __launch_bounds__(WM * WN * 64, WM * WN / 4) void conv_p32_kernel(const ConvQ p) {
     static_assert(NST == 2 || NST == 3, "two or three LDS stages");
     static_assert(!HK || (P32_SINGLE && M16 && NST == 2), "HK is a variant of the single-plane 16x16x32 kernel");
     // eight waves (two per SIMD, <= 256 registers each), or FOUR waves of a larger wave tile (one per SIMD, the whole
     // register file): a third less fragment traffic out of the LDS per output and half the barrier participants
-    static_assert(WM * WN == 8 || (WM * WN == 4 && EPI == EPI_PLANES), "eight waves, or four (planes epilogue only)");
+    // or SIXTEEN waves of a smaller wave tile (four per SIMD, <= 128 registers each: a wave's fragment-read latency has three
+    // partners to hide behind, at a third more fragment traffic and twice the barrier participants) -- not with the fused 1x1
+    // layer, whose LDS image is laid out for eight
+    static_assert(WM * WN == 8 || (WM * WN == 4 && EPI == EPI_PLANES) || (WM * WN == 16 && EPI != EPI_HEAD_PLANES),
+                  "eight waves, four (planes epilogue only) or sixteen (not the fused 1x1 layer)");
     constexpr int NW = WM * WN;
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int STAGE = (BM + BN) * 128;
@@ -851,7 +889,7 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 2 : 1) void conv_p32_k
     const i32x4 rsrc_a = make_rsrc(p.in, p.in_bytes), rsrc_b = make_rsrc(p.w, p.w_bytes);
     const unsigned lds0 = (unsigned)(__SIZE_TYPE__)((lds_void*)smem);
 
-    // ---- DMA bookkeeping: wave w moves pieces w, w + 8, ... (8 rows = 1 KiB each) of the A tile and of the B tile ----
+    // ---- DMA bookkeeping: wave w moves pieces w, w + NW, ... (8 rows = 1 KiB each) of the A tile and of the B tile ----
     constexpr int QA = (NIA + NW - 1) / NW, QB = NIB / NW;
     constexpr bool A_EVEN = NIA % NW == 0;      // else the last round of A pieces is issued by the first NIA % NW waves only
     static_assert(NIB % NW == 0, "tile width is a multiple of 64");
@@ -1224,7 +1262,11 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN == 8 ? 2 : 1) void conv_p32_k
     } else if constexpr (M16 && HEAD && P32_HEAD_DIRECT) {
         // (block-uniform) the layer's own activation is ReLU / none and the head has at most 2 rows (K = 2 classes): straight from
         // the accumulators; anything else through the general epilogue
-        if (p.act != DEMIA_ACT_SIGMOID && p.head_n <= 2)
+        // (sixteen waves: the straight path only -- the host refuses the rest; the general epilogue's 32 head-weight registers
+        //  do not fit beside the accumulators in 128)
+        if constexpr (NW == 16)
+            p32_epilogue_head_direct<WM, WN, TM, TN, 2>(p, gs, smem, acc16, wm, wn, m0, n0);
+        else if (p.act != DEMIA_ACT_SIGMOID && p.head_n <= 2)
             p32_epilogue_head_direct<WM, WN, TM, TN, 2>(p, gs, smem, acc16, wm, wn, m0, n0);
         else
             p32_epilogue<WM, WN, TM, TN, HEAD>(p, gs, smem, [&](int i, float* e) { write_acc16<TN, BN + 4>(acc16[2 * i], acc16[2 * i + 1], e, lane); }, wm, wn, m0, n0);
@@ -1402,9 +1444,18 @@ extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
 #endif
     if (d->head_n > 0) {
         // the fused head has its own instantiations: 256 x 256, 128 x 256 and 192 x 256
+        // 256 x 256 on SIXTEEN waves where the head goes straight from the accumulators (the general epilogue's head weights do
+        // not fit into 128 registers).  4 x 4 waves keep WN and TN of the eight-wave tile, i.e. the order in which a row's 256
+        // products are added up; 2 x 8 waves of 32 columns add them in another order (measured: not bit-identical), so that grid
+        // has no fused-head instantiation.
+        const bool head16 = !P32_SINGLE && P32_HEAD_DIRECT && d->act != DEMIA_ACT_SIGMOID && d->head_n <= 2;
         switch (tile) {
-            case 1: return launch_q<2, 4, 4, 2, true, EPI_HEAD>(p, st);
+            case 1: return head16 ? launch_q<4, 4, 2, 2, true, EPI_HEAD>(p, st) : launch_q<2, 4, 4, 2, true, EPI_HEAD>(p, st);
             case 2: return launch_q<2, 4, 2, 2, true, EPI_HEAD>(p, st);
+#if P32_DEV_TILES
+            case 61: DEMIA_REQUIRE(head16, "sixteen-wave fused head: ReLU / no activation, at most 2 head rows"); return launch_q<4, 4, 2, 2, true, EPI_HEAD>(p, st);
+            case 65: return launch_q<2, 4, 4, 2, true, EPI_HEAD>(p, st);     // the eight-wave twin of id 1 (A/B)
+#endif
             default: return launch_q<1, 8, 6, 1, true, EPI_HEAD>(p, st);
         }
     }
@@ -1437,8 +1488,12 @@ extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
             default: break;       // the ping-pong kernels keep the guarded epilogue
         }
     }
+    // 256 x 256 at K >= 2304 (the 3x3 layers of 256 / 512 channels, FC1): sixteen waves of 128 x 32, four per SIMD -- a wave that
+    // waits for its fragment reads has three partners to issue MFMAs instead of one (1-4 % on those layers, DESIGN.md section 4;
+    // the short-K layers gain nothing and keep eight waves).  Same K order and MFMA order per output element: same bits.
+    const bool waves16 = !P32_SINGLE && p.ksteps >= 72;
     switch (tile) {
-        case 1: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 4, 4, 2>(p, st);   // 256 x 256
+        case 1: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return waves16 ? launch_q<2, 8, 4, 1>(p, st) : launch_q<2, 4, 4, 2>(p, st);   // 256 x 256
         case 2: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 4, 2, 2>(p, st);   // 128 x 256
         case 4: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<1, 8, 6, 1>(p, st);   // 192 x 256
         case 6: DEMIA_REQUIRE(n128, "tile needs CoutPad % 128 == 0"); return launch_q<4, 2, 2, 2>(p, st);   // 256 x 128
@@ -1464,6 +1519,12 @@ extern "C" int demia_conv2d_p32(const demia_conv_p32_desc* d, void* stream) {
         case 49: return launch_q<8, 1, 1, 2, true, EPI_PLANES, 3>(p, st);                                                           // 256 x 64
         case 31: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 4, 4, 2, false>(p, st);  // 256 x 256, 32x32x16 MFMAs (A/B)
         case 34: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<1, 8, 6, 1, false>(p, st);  // 192 x 256, 32x32x16 MFMAs (A/B)
+        // sixteen waves (four per SIMD, <= 128 registers): same K order and MFMA order per output element as the eight-wave tiles
+        case 65: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 4, 4, 2>(p, st);   // 256 x 256 on eight waves at any K (the twin of id 1)
+        case 61: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<4, 4, 2, 2>(p, st);   // 256 x 256, 4 x 4 waves of 64 x 64
+        case 62: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 8, 4, 1>(p, st);   // 256 x 256, 2 x 8 waves of 128 x 32
+        case 63: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<4, 4, 1, 2>(p, st);   // 128 x 256, 4 x 4 waves of 32 x 64
+        case 64: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_q<2, 8, 2, 1>(p, st);   // 128 x 256, 2 x 8 waves of 64 x 32
         case 21: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_pp<4, 2>(p, st);        // 256 x 256, ping-pong
         case 22: DEMIA_REQUIRE(n256, "tile needs CoutPad % 256 == 0"); return launch_pp<2, 2>(p, st);        // 128 x 256, ping-pong
         case 26: DEMIA_REQUIRE(n128, "tile needs CoutPad % 128 == 0"); return launch_pp<4, 1>(p, st);        // 256 x 128, ping-pong

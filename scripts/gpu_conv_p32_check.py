@@ -40,11 +40,14 @@ class Layer:
         self.bbound = float(self.bias.abs().max())
 
 
-def conv_p32(x: p32.P32, L: Layer, stride=1, pad=0, act=ACT_NONE, res=None, res_mode=RES_NONE, out_f32=False, out_ld=0, hint=0, single=0):
+def conv_p32(x: p32.P32, L: Layer, stride=1, pad=0, act=ACT_NONE, res=None, res_mode=RES_NONE, out_f32=False, out_ld=0, hint=0, single=0, head=None):
+    """head = (weights [2, 256] f32, bias [2] f32, out [M * Cout / 256, 2] f32): the fused 1x1 head + sigmoid; the planes are not written"""
     n, h, w, cin = x.shape
     ho = (h + 2 * pad - L.kh) // stride + 1
     wo = (w + 2 * pad - L.kw) // stride + 1
-    if out_f32:
+    if head is not None:
+        out, optr, ometa = head[2], 0, 0
+    elif out_f32:
         ld = out_ld or L.cout
         out = torch.zeros((n, ho, wo, ld), dtype=torch.float32, device=dev)
         optr, ometa = _lib.ptr(out), 0
@@ -56,6 +59,8 @@ def conv_p32(x: p32.P32, L: Layer, stride=1, pad=0, act=ACT_NONE, res=None, res_
                          L.wbound, L.bbound, n, h, w, cin, ho, wo, L.cout, L.cout_pad, L.kh, L.kw, stride, pad, act, res_mode,
                          1 if out_f32 else 0, out_ld, hint)
     d.single = single
+    if head is not None:
+        d.head_w, d.head_b, d.head_out, d.head_n, d.head_ld, d.head_act = _lib.ptr(head[0]), _lib.ptr(head[1]), _lib.ptr(head[2]), 2, 2, ACT_SIGMOID
     _lib.check(lib.demia_conv2d_p32(C.byref(d), st()), 'demia_conv2d_p32')
     return out
 
@@ -144,7 +149,8 @@ def check():
 
 
 HINTS = {60: 'pingpong', 14: '192x256', 42: '128x256s3', 52: '160x256ns3', 49: '256x64s3', 12: '160x256n', 13: '224x256n', 31: '256x256m32', 34: '192x256m32', 21: '256x256pp', 22: '128x256pp', 26: '256x128pp', 1: '256x256', 2: '128x256', 3: '256x256n', 4: '192x256n', 5: '128x256n', 6: '256x128', 7: '128x128', 8: '128x128n',
-         9: '256x64', 10: '256x64b', 11: '128x64'}
+         9: '256x64', 10: '256x64b', 11: '128x64',
+         61: '256x256w16_4x4', 62: '256x256w16_2x8', 63: '128x256w16_4x4', 64: '128x256w16_2x8', 65: '256x256w8'}
 
 R101_B16 = [
     # (count, M-shape n h w, cin, cout, k, stride, residual)
@@ -256,6 +262,67 @@ def key_layers(hint=1, which='mfma'):
     print(os.environ.get('AB_LIB', 'default'), f'hint {hint} |', ' | '.join(out), flush=True)
 
 
+# the classes of launches the 256 x 256 tile serves at B tiles per forward: (class, name, count per forward, (n, h, w), cin, cout, k, residual)
+WAVES16_LAYERS = [
+    ('large-K 3x3', 'fpn_output2 / rpn 200x200', 2, (16, 200, 200), 256, 256, 3, 0),
+    ('large-K 3x3', 'mask_fcn 14x14', 4, (1600, 14, 14), 256, 256, 3, 0),
+    ('large-K 3x3', 'res4 conv2', 25, (16, 50, 50), 256, 256, 3, 0),
+    ('large-K 3x3', 'fpn_output3 100x100', 2, (16, 100, 100), 256, 256, 3, 0),
+    ('large-K 3x3', 'res5 conv2', 3, (16, 25, 25), 512, 512, 3, 0),
+    ('FC1', 'box head fc1', 1, (1, 1, 16000), 12544, 1024, 1, 0),
+    ('short-K residual', 'res4 conv3', 23, (16, 50, 50), 256, 1024, 1, 1),
+    ('short-K residual', 'res2 conv3', 4, (16, 200, 200), 64, 256, 1, 1),
+    ('short-K residual', 'res3 conv3', 4, (16, 100, 100), 128, 512, 1, 1),
+    ('short-K residual', 'res5 conv3', 3, (16, 25, 25), 512, 2048, 1, 1),
+    ('short-K residual', 'fpn lateral 200x200', 1, (16, 200, 200), 256, 256, 1, 1),
+    ('short-K plain', 'res4 conv1', 23, (16, 50, 50), 1024, 256, 1, 0),
+    ('short-K plain', 'res5 conv1', 2, (16, 25, 25), 2048, 512, 1, 0),
+    ('fused-head deconv', 'mask deconv + predictor', 1, (1, 1, 313600), 256, 1024, 1, 2),
+]
+
+
+def waves16(B=48, repeats=3, json_path=None, hints=(65, 61, 62), window_ms=300.0):
+    """Dev build: the sixteen-wave grids (hints 61 / 62; 63 / 64 at 128 x 256) beside the eight-wave tile of the same block (65; 2),
+    per layer, at B tiles.  The hints ALTERNATE inside every repeat (same process, same buffers); one round is thrown away first
+    (clocks), then per hint the median and the min-max spread of `repeats` timings of `window_ms` of launches each.  A sixteen-wave
+    grid wins a layer when its median is below the eight-wave one's by more than the larger of the two spreads."""
+    import json
+    import statistics
+    rows = []
+    for cls, name, cnt, (n, h, w), cin, cout, k, rs in WAVES16_LAYERS:
+        if n == 16:
+            n = B
+        elif n == 1600:
+            n = 100 * B
+        elif n == 1:
+            w = w // 16 * B
+        L = Layer(cout, cin, k, k, seed=1)
+        xp = p32.from_f32(torch.randn(n, h, w, cin, device=dev))
+        res = p32.from_f32(torch.randn(n, h, w, cout, device=dev)) if rs == 1 else None
+        head = None
+        if rs == 2:
+            head = ((torch.randn(2, 256, device=dev) * 0.1).contiguous(), torch.randn(2, device=dev), torch.empty(n * h * w * (cout // 256), 2, device=dev))
+        use = [hh for hh in hints if not (head is not None and hh in (62, 63, 64))]      # the fused head: 4 x 4 waves only (summation order)
+        tt = {hh: [] for hh in use}
+        run = lambda hh: conv_p32(xp, L, 1, k // 2, ACT_RELU, res, RES_SAME if res is not None else RES_NONE, hint=hh, head=head)
+        reps = {hh: max(5, int(window_ms / timeit(lambda: run(hh), reps=3))) for hh in use}       # (also the discarded round)
+        for _ in range(repeats):
+            for hh in use:
+                tt[hh].append(timeit(lambda: run(hh), reps=reps[hh]) * 1e3)
+        fl = 2.0 * n * h * w * cout * cin * k * k
+        row = {'class': cls, 'layer': name, 'launches_per_forward': cnt, 'M': n * h * w, 'K': cin * k * k, 'N': cout,
+               'us': {HINTS[hh]: {'median': round(statistics.median(v), 1), 'min': round(min(v), 1), 'max': round(max(v), 1)} for hh, v in tt.items()}}
+        rows.append(row)
+        print(f'{cls:18s} {name:26s} M={n*h*w:8d} K={cin*k*k:6d} N={cout:5d} x{cnt:2d} | ' +
+              ' '.join(f'{HINTS[hh]}={statistics.median(v):.1f}[{min(v):.1f}-{max(v):.1f}]' for hh, v in tt.items()) +
+              f' | {fl / statistics.median(tt[use[0]]) / 1e6:.0f} TF/s at {HINTS[use[0]]}', flush=True)
+        del xp, res, head, L
+        torch.cuda.empty_cache()
+    if json_path:
+        with open(json_path, 'w') as f:
+            json.dump({'tiles_per_forward': B, 'repeats': repeats, 'ms_of_launches_per_timing': window_ms, 'unit': 'us per launch', 'layers': rows}, f, indent=1)
+
+
 def single_sweep(B=48):
     """The single-plane layers (mask head) at B tiles over every tile this build instantiates: which tile suits ONE MFMA per product."""
     for name, (n, h, w), cin, cout, k in (('mask_fcn 3x3', (100 * B, 14, 14), 256, 256, 3), ('deconv 1x1', (1, 1, 19600 * B), 256, 1024, 1)):
@@ -348,6 +415,10 @@ if __name__ == '__main__':
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'single':
         single_sweep(int(sys.argv[2]) if len(sys.argv) > 2 else 48)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'waves16':       # waves16 [B] [json path]
+        waves16(int(sys.argv[2]) if len(sys.argv) > 2 else 48, json_path=sys.argv[3] if len(sys.argv) > 3 else None,
+                hints=tuple(int(v) for v in sys.argv[4].split(',')) if len(sys.argv) > 4 else (65, 61, 62))
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'key':
         key_layers(int(sys.argv[2]) if len(sys.argv) > 2 else 1, sys.argv[3] if len(sys.argv) > 3 else 'mfma')
