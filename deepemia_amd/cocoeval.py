@@ -553,6 +553,110 @@ class OutlineReport:
         return summary
 
 
+# ---- error maps: one picture per image of where the detections and the ground truth differ -------------------------------------------
+ERROR_MAP_IOU = 0.5          # a detection and an annotation are a pair from this mask IoU on (outline_match)
+ERROR_MAP_ALPHA = 96         # weight of a fill colour, of 256
+# BGR; the order is the kernel's (include/deepemia_hip.h): three fills, then the five line classes by priority
+ERROR_MAP_PALETTE = ((0, 255, 0), (0, 0, 255), (255, 0, 0), (255, 0, 255), (255, 255, 0), (0, 255, 255), (255, 255, 255), (128, 128, 128))
+ERROR_MAP_LABELS = ("agree (fill)", "excess: detected, not annotated (fill)", "missing: annotated, not detected (fill)",
+                    "unmatched detection (line)", "missed annotation (line)", "matched detection (line)", "matched annotation (line)",
+                    "crowd region (line)")
+ERROR_MAP_HEADER = ["image_id", "file_name", "detections", "annotations", "matched", "missed", "spurious", "crowd", "agree_px", "excess_px",
+                    "missing_px", "ignored_px", "pixel_precision", "pixel_recall", "pixel_dice"]
+
+
+def error_map_line(H: int, W: int) -> int:
+    """The default line width of an ``H x W`` image: ``min(4, max(1, round(max(H, W) / 1024)))``, round = Python's (half to even)."""
+    return min(4, max(1, round(max(int(H), int(W)) / 1024)))
+
+
+def error_map_states(pairs: np.ndarray, n_det: int, crowd: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """``(d_state [n_det], g_state [G])`` int32 for the error-map kernel from the pairs of :func:`outline_match`: a paired mask is 1,
+    an unpaired one 2 (a spurious detection, a missed annotation), a crowd annotation 3."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    crowd = np.asarray(crowd).astype(bool).reshape(-1)
+    d_state = np.full(int(n_det), 2, dtype=np.int32)
+    g_state = np.where(crowd, 3, 2).astype(np.int32)
+    d_state[pairs[:, 0]] = 1
+    g_state[pairs[:, 1]] = 1
+    return d_state, g_state
+
+
+def error_map_ratios(agree: int, excess: int, missing: int) -> Tuple[Optional[float], Optional[float], Optional[float]]:
+    """(pixel precision, pixel recall, pixel Dice) from the three integers; None where a denominator is 0."""
+    def ratio(num: int, den: int) -> Optional[float]:
+        return None if den == 0 else float(num) / float(den)
+    return ratio(agree, agree + excess), ratio(agree, agree + missing), ratio(2 * agree, 2 * agree + excess + missing)
+
+
+class ErrorMaps:
+    """The error maps of one evaluate run (``--visualize``), the sibling of :class:`OutlineReport`: per test image one picture
+    ``evaluation_images/<image_id>_<stem>_evaluation.png`` under ``output_dir`` and one row of ``evaluation_images.csv``.  ``paint``
+    of :meth:`add_image` is the device stage: ``paint(d_state, g_state)`` returns the painted image on the host (``[H, W, 3]`` uint8
+    BGR) and the four pixel counts (agree, excess, missing, ignored), from one device-to-host copy.  ``line``: the line width, or None
+    for :func:`error_map_line` of each image."""
+
+    def __init__(self, output_dir: str, iou: float = ERROR_MAP_IOU, alpha: int = ERROR_MAP_ALPHA, line: Optional[int] = None):
+        self.output_dir, self.iou, self.alpha, self.line = str(output_dir), float(iou), int(alpha), (None if line is None else int(line))
+        self.rows: List[list] = []
+
+    @property
+    def image_dir(self) -> str:
+        return os.path.join(self.output_dir, "evaluation_images")
+
+    def line_for(self, H: int, W: int) -> int:
+        return error_map_line(H, W) if self.line is None else self.line
+
+    def image_path(self, image_id, file_name: str) -> str:
+        stem = os.path.splitext(os.path.basename(str(file_name)))[0]
+        return os.path.join(self.image_dir, f"{image_id}_{stem}_evaluation.png")
+
+    def add_image(self, image_id, file_name: str, d_cat, scores, g_cat, crowd, iou: np.ndarray,
+                  paint: Callable[[np.ndarray, np.ndarray], Tuple[np.ndarray, Sequence[int]]]) -> str:
+        """One image: ``d_cat`` / ``g_cat`` dataset category ids, ``scores`` f64, ``iou`` the ``segm`` IoU table.  Returns the
+        picture's path."""
+        from PIL import Image
+
+        crowd = np.asarray(crowd).astype(bool).reshape(-1)
+        pairs = outline_match(iou, scores, d_cat, g_cat, crowd, self.iou)
+        d_state, g_state = error_map_states(pairs, len(scores), crowd)
+        bgr, counts = paint(d_state, g_state)
+        path = self.image_path(image_id, file_name)
+        os.makedirs(self.image_dir, exist_ok=True)
+        Image.fromarray(np.ascontiguousarray(np.asarray(bgr)[:, :, ::-1])).save(path)
+        n_det, n_ann, n_pair = len(d_state), int((~crowd).sum()), len(pairs)
+        agree, excess, missing, ignored = (int(v) for v in counts)
+        self.rows.append([image_id, os.path.basename(str(file_name)), n_det, n_ann, n_pair, n_ann - n_pair, n_det - n_pair, int(crowd.sum()),
+                          agree, excess, missing, ignored] + list(error_map_ratios(agree, excess, missing)))
+        return path
+
+    def write(self) -> str:
+        """``evaluation_images.csv`` in ``output_dir`` and ``evaluation_images/legend.png``; returns the table's path."""
+        os.makedirs(self.image_dir, exist_ok=True)
+        path = os.path.join(self.output_dir, "evaluation_images.csv")
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(ERROR_MAP_HEADER)
+            for r in self.rows:
+                w.writerow(["" if x is None else (repr(x) if isinstance(x, float) else x) for x in r])
+        self._legend().save(os.path.join(self.image_dir, "legend.png"))
+        return path
+
+    @staticmethod
+    def _legend():
+        """The palette with its eight labels (Pillow's default font; no parity is claimed for it)."""
+        from PIL import Image, ImageDraw
+
+        row, pad, sw = 22, 6, 28
+        im = Image.new("RGB", (360, 2 * pad + row * len(ERROR_MAP_PALETTE)), (32, 32, 32))
+        d = ImageDraw.Draw(im)
+        for k, ((b, g, r), label) in enumerate(zip(ERROR_MAP_PALETTE, ERROR_MAP_LABELS)):
+            y = pad + k * row
+            d.rectangle([pad, y + 3, pad + sw, y + row - 4], fill=(r, g, b), outline=(0, 0, 0))
+            d.text((2 * pad + sw, y + 5), label, fill=(255, 255, 255))
+        return im
+
+
 def box_iou(dt: np.ndarray, gt: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     """``maskUtils.iou``'s box branch (``bbIou``) on XYWH float64 boxes."""
     dt = np.asarray(dt, dtype=np.float64).reshape(-1, 4)

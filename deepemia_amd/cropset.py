@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .maskset import (_WORKLISTS, Agglomerates, ContourSet, MaskOps, Neighbours, OutlineAgreement, PlanePool, _launch_agglomerates,
-                      _launch_neighbours, _launch_outline, reads_words)
+                      _launch_error_map, _launch_neighbours, _launch_outline, reads_words)
 from .parallel import HDR
 from .utils.mask_algebra import DeviceMaskAlgebra
 
@@ -429,6 +429,18 @@ class CropMaskSet:
             gt_area = gt.area.cpu().numpy() if G else np.zeros(0)
         return _launch_outline(ops, "demia_crop_outline_agreement", (self.payload, self.room, self.offsets, self.bbox if bbox is None else bbox),
                                D, area, (gt.payload, gt.room, gt.offsets, gt.bbox), G, gt_area, self.hw[0], self.hw[1], pairs)
+
+    def error_map(self, gt: "CropMaskSet", d_state, g_state, image: torch.Tensor, alpha: int, line: int, palette=None,
+                  bbox: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``MaskOps.error_map`` of this set (the detections) against ``gt`` (the annotations) over the same frame, on the words in
+        place (``demia_crop_error_map``): the same picture and counts, no plane, no wait -- the image and its painted copy are the
+        only full-frame buffers.  ``bbox``: this set's tight boxes on the device when the caller has its own copy (default: the
+        set's)."""
+        if self.hw != gt.hw:
+            raise ValueError(f"error_map: a set over {self.hw} against a set over {gt.hw}")
+        return _launch_error_map(self.ops, "demia_crop_error_map", (self.payload, self.room, self.offsets, self.bbox if bbox is None else bbox),
+                                 len(self), d_state, (gt.payload, gt.room, gt.offsets, gt.bbox), len(gt), g_state, self.hw[0], self.hw[1],
+                                 image, alpha, line, palette)
 
     def trace(self, max_contours: int = 64, max_points: Optional[int] = None, total_area=None, scratch: Optional[torch.Tensor] = None,
               keep_words: bool = False) -> ContourSet:

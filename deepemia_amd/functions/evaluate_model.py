@@ -33,11 +33,24 @@ the signed equivalent-diameter error and the relative area error of them.  An im
 copy; an image without one, and a run with the switch off, launch, allocate, copy and write nothing for it.  The AP tables, the
 result files and the returned dict are the same with the switch on or off.
 
+``--visualize`` (both modes, both score frames) draws one ERROR MAP per test image -- not Detectron2's ``Visualizer`` picture, whose
+look is not reproduced: the detections over the ground truth in the frame being scored, painted on the GPU from the packed words the
+scorer holds (``demia_mask_error_map`` / ``demia_crop_error_map``; the definitions are stated in ``include/deepemia_hip.h``).  Per
+image the masks are paired as for the outline report (``cocoeval.outline_match`` at ``evaluation.visualize_iou``, default 0.5);
+pixels both sides hold are filled in one colour, pixels only a detection holds in a second, pixels only an annotation holds in a
+third (weight ``evaluation.visualize_alpha`` of 256, default 96), and the outlines of matched, spurious and missed masks and of
+crowd regions are drawn on top, ``evaluation.visualize_line`` pixels wide (1 to 4; default ``cocoeval.error_map_line`` of the
+image's size).  The pictures go to ``evaluation_images/<image_id>_<stem>_evaluation.png`` with a ``legend.png``, and
+``evaluation_images.csv`` has one row per image: the counts of the pairing and the agree / excess / missing / ignored pixels with
+the pixel precision, recall and Dice of them.  An image costs one more device-to-host copy (the picture and the counts) and its PNG
+encode; with the flag off nothing is launched, allocated, copied or written for it, and the tables, the result files and the
+returned dict are the same with the flag on or off.
+
 Outputs in ``output_dir``: ``metrics.csv`` (``metric,value``, one row per task: ``bbox``, ``segm`` and, when asked for, ``boundary``), ``coco_instances_results.json``
 (``instances_to_coco_json`` layout, dataset category ids) and ``instances_predictions.pth``; with the outline report,
 ``outline_agreement.csv`` (one row per matched pair, in image order, then detection order) and ``outline_summary.csv`` (one row per
-class and the row ``all``, pooled over the pairs; a class without a pair has empty value fields).  Not provided: prediction
-images (``--visualize`` only logs a warning) and, in predictor mode, the ``combo`` model pair.
+class and the row ``all``, pooled over the pairs; a class without a pair has empty value fields); with ``--visualize``,
+``evaluation_images/`` and ``evaluation_images.csv``.  Not provided: in predictor mode, the ``combo`` model pair.
 """
 from __future__ import annotations
 
@@ -144,6 +157,26 @@ def outline_setting(dataset_name: Optional[str] = None) -> Optional[Tuple[float,
     return (float(iou), int(tol)) if on else None
 
 
+def visualize_setting(dataset_name: Optional[str] = None) -> Tuple[float, int, Optional[int]]:
+    """The error maps' settings of the ``evaluation`` key (global, or in the dataset's file), for ``--visualize``: ``(iou, alpha,
+    line)`` -- ``evaluation.visualize_iou`` (default 0.5, a number in (0, 1]: the mask IoU from which a detection and an annotation are
+    a pair), ``evaluation.visualize_alpha`` (default 96, an integer from 0 to 256: the fill colours' weight of 256) and
+    ``evaluation.visualize_line`` (default unset: ``cocoeval.error_map_line`` of each image; or an integer from 1 to 4, the outlines'
+    width in pixels).  ValueError, with the key named, for a wrong type or range; all three keys are checked whether or not the flag
+    is given."""
+    cfg = _evaluation_key(dataset_name)
+    iou = cfg.get("visualize_iou", CE.ERROR_MAP_IOU)
+    if isinstance(iou, bool) or not isinstance(iou, (int, float)) or not (0.0 < float(iou) <= 1.0):
+        raise ValueError(f"evaluation.visualize_iou must be a number in (0, 1], got {iou!r}")
+    alpha = cfg.get("visualize_alpha", CE.ERROR_MAP_ALPHA)
+    if isinstance(alpha, bool) or not isinstance(alpha, int) or not (0 <= alpha <= 256):
+        raise ValueError(f"evaluation.visualize_alpha must be an integer from 0 to 256, got {alpha!r}")
+    line = cfg.get("visualize_line")
+    if line is not None and (isinstance(line, bool) or not isinstance(line, int) or not (1 <= line <= 4)):
+        raise ValueError(f"evaluation.visualize_line must be an integer from 1 to 4, got {line!r}")
+    return float(iou), int(alpha), line
+
+
 def read_image_bgr(path: str) -> np.ndarray:
     """Detectron2's ``read_image(path, "BGR")``: PIL decode, EXIF orientation applied, converted to RGB, channels reversed."""
     from PIL import Image, ImageOps
@@ -187,21 +220,22 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
     boundary = boundary_setting(dataset_name)          # (checked before any model is loaded)
     outline = outline_setting(dataset_name)            # (likewise)
     report = CE.OutlineReport(*outline) if outline is not None else None
+    visual = visualize_setting(dataset_name)           # (likewise, whether or not the flag is given)
+    maps = CE.ErrorMaps(output_dir, *visual) if visualize else None
     config = get_config()
     max_dets = CE.check_max_dets(_evaluation_key(dataset_name).get("max_dets"))
     split_dir = Path(config["paths"]["split_dir"]).expanduser().resolve()
     category_json = Path(config["paths"]["category_json"]).expanduser().resolve()
-    if visualize:
-        system_logger.warning("--visualize: evaluation images are not drawn in this build (Detectron2's Visualizer is not "
-                              "provided); the metrics are computed as usual")
     dataset_info = read_dataset_info(category_json)
     register_datasets(dataset_info, dataset_name, dataset_format=dataset_format)
     recs, class_names, to_dataset_id = _test_records(dataset_name, dataset_format, dataset_info, split_dir)
     metadata = MetadataCatalog.get(f"{dataset_name}_train")
     if mode == "pipeline":
         tables = _new_tables(boundary)
-        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id, boundary, report)
-        return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline", report)
+        per_image, times = _run_pipeline(dataset_name, recs, metadata, str(split_dir), rcnn, threshold, tables, to_dataset_id, boundary, report,
+                                         maps)
+        return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, "pipeline", report,
+                              maps)
     predictor, _ = choose_and_use_model(get_trained_model_paths(str(split_dir), rcnn), dataset_name, SCORE_THRESH, metadata, rcnn)
     if predictor is None:
         raise FileNotFoundError(f"no trained rcnn_r{rcnn} model for dataset {dataset_name} under {split_dir}")
@@ -232,15 +266,16 @@ def evaluate_model(dataset_name: str, output_dir: str, visualize: bool = False, 
         outs = predictor.predict_batch(batch)
         torch.cuda.synchronize(device)
         t2 = time.perf_counter()
-        for ri, out in zip(group, outs):
-            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id, boundary, report)
+        for k, (ri, out) in enumerate(zip(group, outs)):
+            per_image[ri] = _score_image(ops, recs[ri], out["instances"], tables, to_dataset_id, boundary, report,
+                                         maps=maps, image=batch[k] if maps is not None else None)
         t3 = time.perf_counter()
         t_read += t1 - t0
         t_fwd += t2 - t1
         t_score += t3 - t2
 
     return _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, (t_read, t_fwd, t_score),
-                          "forwards", report)
+                          "forwards", report, maps)
 
 
 def _new_tables(boundary=None) -> Dict[str, CE.EvalTables]:
@@ -252,10 +287,11 @@ def _new_tables(boundary=None) -> Dict[str, CE.EvalTables]:
 
 
 def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_dir, max_dets, t_start, times, work: str,
-                   report: Optional[CE.OutlineReport] = None):
+                   report: Optional[CE.OutlineReport] = None, maps: Optional[CE.ErrorMaps] = None):
     """COCOeval over the tables of all images, the three result files and the timing line (``work`` names what ``times[1]``
     measured: the predictor's forwards, or the whole inference pipeline of an image).  ``report``: the run's outline-agreement
-    report, when asked for -- its two files are written beside the three and its ``all`` row is logged."""
+    report, when asked for -- its two files are written beside the three and its ``all`` row is logged.  ``maps``: the run's error
+    maps, when asked for -- their table and legend are written."""
     t_read, t_fwd, t_score = times
     t0 = time.perf_counter()
     predictions = [{"image_id": recs[i]["image_id"], "instances": per_image[i]["instances"]} for i in range(len(recs))]
@@ -290,6 +326,10 @@ def _write_results(recs, per_image, tables, to_dataset_id, class_names, output_d
         system_logger.info(f"Outline agreement over {len(report.rows)} matched pairs (IoU >= {report.iou}, NSD at {report.tolerance} px): "
                            + ", ".join(f"{k}={v}" for k, v in zip(CE.OUTLINE_SUMMARY_HEADER, summary[-1])))
         t_score += time.perf_counter() - t0
+    if maps is not None:
+        t0 = time.perf_counter()
+        system_logger.info(f"Error maps of {len(maps.rows)} images (IoU >= {maps.iou}, alpha {maps.alpha}) in {maps.image_dir}; table: {maps.write()}")
+        t_score += time.perf_counter() - t0
     n = max(1, len(recs))
     system_logger.info(f"Evaluation wall time {time.perf_counter() - t_start:.2f}s: {work} {t_fwd:.3f}s ({1e3 * t_fwd / n:.1f} ms/image), "
                        f"scoring {t_score:.3f}s ({1e3 * t_score / n:.1f} ms/image), image reads {t_read:.3f}s; "
@@ -302,7 +342,7 @@ class _ScoreFrame:
     """One image's detections in the frame they are scored in and, after :meth:`ground_truth`, its annotations in the same frame:
     the device work :func:`_score` asks for, and nothing else.  ``hw`` is the image's ``(H, W)``, ``d_bbox_t`` the detections' tight
     boxes on the device, ``gt_area`` the annotations' pixel counts on the device.  An implementation gives ``_ground_truth``,
-    ``cross``, ``bands``, ``rle_launch``, ``rle_again``, ``outline`` and ``empty`` (the frame of an image without a detection).
+    ``cross``, ``bands``, ``rle_launch``, ``rle_again``, ``outline``, ``error_map`` and ``empty`` (the frame of an image without a detection).
     Labels are host arrays; a method enqueues without a wait unless it says otherwise."""
 
     def __init__(self, ops: MaskOps, H: int, W: int, d_bbox_t: torch.Tensor):
@@ -366,6 +406,10 @@ class _PlaneFrame(_ScoreFrame):
     def outline(self, pairs, d_px, g_px) -> OutlineAgreement:
         return self.ops.outline_agreement(self.packed, self.d_bbox_t, d_px, self.g_packed, self.g_bbox_t, g_px, pairs, W=self.hw[1])
 
+    def error_map(self, image, d_state, g_state, alpha: int, line: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The error map of the frame on ``image`` (uint8, on the device): ``(picture [H, W, 3], counts [4] int64)`` on the device."""
+        return self.ops.error_map(self.packed, self.d_bbox_t, d_state, self.g_packed, self.g_bbox_t, g_state, image, alpha, line, W=self.hw[1])
+
 
 class _CropFrame(_ScoreFrame):
     """``score_frame: crops``: the same launches over rooms -- the ground truth becomes a :class:`CropMaskSet` too (polygons are
@@ -411,6 +455,9 @@ class _CropFrame(_ScoreFrame):
     def outline(self, pairs, d_px, g_px) -> OutlineAgreement:
         return self.cset.outline_agreement(self.gt, pairs, area=d_px, gt_area=g_px, bbox=self.d_bbox_t)
 
+    def error_map(self, image, d_state, g_state, alpha: int, line: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return self.cset.error_map(self.gt, d_state, g_state, image, alpha, line, bbox=self.d_bbox_t)
+
 
 def _fetch(parts: Sequence[Tuple[str, torch.Tensor]]) -> Dict[str, np.ndarray]:
     """ONE device-to-host copy of the int32 device tensors ``parts`` = ``(name, tensor)``, in that order: ``{name: host array of the
@@ -422,12 +469,14 @@ def _fetch(parts: Sequence[Tuple[str, torch.Tensor]]) -> Dict[str, np.ndarray]:
 
 def _score(frame: _ScoreFrame, rec: dict, det, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
            boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None,
-           boxes_xywh: Optional[np.ndarray] = None) -> dict:
+           boxes_xywh: Optional[np.ndarray] = None, maps: Optional[CE.ErrorMaps] = None, image: Optional[torch.Tensor] = None) -> dict:
     """One image through the scorer, in any frame: ground truth, cross matrix, with ``boundary`` the bands, run lengths, ONE
     device-to-host copy, then the result rows and the image's rows of the IoU tables; with ``report`` the image's matched pairs are
     measured in the same frame behind that (one more copy when there is a pair).  ``det`` = the detections on the host
     (contiguous classes int64, scores float64, pixel counts int64, tight boxes ``[n, 4]`` int32).  ``boxes_xywh`` float64: the
-    detections' boxes when they have regressed ones (predictor mode); default ``toBbox`` of the run lengths."""
+    detections' boxes when they have regressed ones (predictor mode); default ``toBbox`` of the run lengths.  With ``maps`` (the run's
+    error maps) the image's map is painted on ``image`` (uint8, on the device) in the same frame behind the table rows: one more
+    copy, the picture and its counts together."""
     classes, scores64, d_area, d_bbox = det
     (H, W), anns, n = frame.hw, rec["annotations"], len(classes)
     err = frame.ground_truth(anns)
@@ -451,16 +500,26 @@ def _score(frame: _ScoreFrame, rec: dict, det, tables: Dict[str, CE.EvalTables],
                   "segmentation": {"size": [H, W], "counts": strings[k]}} for k in range(n)]
     outline = None if report is None else (report, lambda pairs, d_px, g_px: OutlineAgreement.from_host(
         frame.outline(pairs, d_px, g_px).records.cpu().numpy()))                                              # (its ONE copy)
+    paint = None
+    if maps is not None:
+        if image is None:
+            raise ValueError(f"{rec['file_name']}: the error maps need the image on the device")
+
+        def paint(d_state, g_state):
+            dst, counts = frame.error_map(image, d_state, g_state, maps.alpha, maps.line_for(H, W))
+            both = torch.cat([dst.reshape(-1), counts.view(torch.uint8)]).cpu().numpy()                      # (its ONE copy)
+            return both[:H * W * 3].reshape(H, W, 3), both[H * W * 3:].copy().view(np.int64)
     _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, xywh, d_area, g_cat, host["g_px"].astype(np.int64),
-                    host["inter"].astype(np.int64), band, outline)
+                    host["inter"].astype(np.int64), band, outline, maps=None if maps is None else (maps, paint))
     return {"instances": instances}
 
 
 def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables], to_dataset_id: Dict[int, int],
-                 boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
+                 boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None,
+                 maps: Optional[CE.ErrorMaps] = None, image: Optional[torch.Tensor] = None) -> dict:
     """Predictor mode: one image's ``Instances`` through :func:`_score` on planes.  Classes, scores, predicted boxes and the masks'
     pixel counts and tight boxes come over in one copy; the result rows and the ``bbox`` task carry the predicted boxes (float32,
-    widened).  ``boundary`` / ``report``: as for :func:`_score`."""
+    widened).  ``boundary`` / ``report`` / ``maps`` / ``image``: as for :func:`_score`."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(inst.image_size) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {inst.image_size}, the annotation says {(H, W)}")
@@ -477,15 +536,17 @@ def _score_image(ops: MaskOps, rec: dict, inst, tables: Dict[str, CE.EvalTables]
         xywh = host["boxes"].view(np.float32).copy()
         xywh[:, 2] -= xywh[:, 0]
         xywh[:, 3] -= xywh[:, 1]
-    return _score(frame, rec, det, tables, to_dataset_id, boundary, report, boxes_xywh=xywh.astype(np.float64))
+    return _score(frame, rec, det, tables, to_dataset_id, boundary, report, boxes_xywh=xywh.astype(np.float64), maps=maps, image=image)
 
 
-def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None, outline=None) -> None:
+def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_area, g_cat, g_px, inter, band=None, outline=None,
+                    maps=None) -> None:
     """One image's rows of the tasks' tables: detections (contiguous classes, float64 scores and XYWH boxes, mask pixel
     counts) against the record's annotations (``g_px`` their rasterised pixel counts, ``inter`` the intersection counts).
     ``band`` = (band intersections, detection band areas, ground-truth band areas) fills the ``boundary`` task: its IoU is
     ``min(mask IoU, boundary IoU)``, its areas are those of ``segm``.  ``outline`` = (the run's ``OutlineReport``, the image's
-    device stage): the image's pairs are matched from the ``segm`` IoU table and measured."""
+    device stage): the image's pairs are matched from the ``segm`` IoU table and measured.  ``maps`` = (the run's ``ErrorMaps``, the
+    image's ``paint``): the image's error map is painted from the same table and written."""
     anns = rec["annotations"]
     crowd = np.asarray([int(a.get("iscrowd", 0)) for a in anns], dtype=np.uint8)
     g_area = np.asarray([float(a["area"]) for a in anns], dtype=np.float64)
@@ -502,6 +563,8 @@ def _add_image_rows(tables, rec, to_dataset_id, classes_l, scores64, d_box64, d_
                              CE.box_iou(d_box64, g_box, crowd))
     if outline is not None:
         outline[0].add_image(img, os.path.basename(str(rec["file_name"])), d_cat, scores64, d_area, g_cat_ds, g_px, crowd, m_iou, outline[1])
+    if maps is not None:
+        maps[0].add_image(img, str(rec["file_name"]), d_cat, scores64, g_cat_ds, crowd, m_iou, maps[1])
 
 
 # ---- pipeline mode -----------------------------------------------------------------------------------------------------------
@@ -538,6 +601,7 @@ class PipelineRunner:
         self.num_classes = len(metadata.thing_classes)
         self.dev = self.pipe.dev
         self.t_read = self.t_pipe = 0.0
+        self.image_dev: Optional[torch.Tensor] = None      # the image of the instances last yielded, uint8 BGR on the device
 
     def _load(self, path: str) -> torch.Tensor:
         t0 = time.perf_counter()
@@ -551,7 +615,9 @@ class PipelineRunner:
         """Generator over ``paths`` in order: ``(path, (H, W), packed, scores, classes, tabs)`` -- the image's final masks on the
         device (None or empty when nothing is left), its scores and classes, ``tabs = (pixel counts, boxes)`` on the host.
         ``packed`` is what ``final_instances`` keeps in the dataset's ``mask_frame``: full-frame planes ``[n, H, W/32]`` int32 under
-        ``full`` (``score_frame: planes``), a :class:`CropMaskSet` under ``crop`` and ``crop_direct`` (``score_frame: crops``)."""
+        ``full`` (``score_frame: planes``), a :class:`CropMaskSet` under ``crop`` and ``crop_direct`` (``score_frame: crops``).
+        While the consumer holds a tuple, ``image_dev`` is that image on the device (uint8 ``[H, W, 3]`` BGR): what the error maps
+        are painted on."""
         INF, st, pipe = self.INF, self.st, self.pipe
         t0, r0 = time.perf_counter(), self.t_read
         on_dev = {p: self._load(p) for p in paths[:5]}
@@ -579,11 +645,13 @@ class PipelineRunner:
                 finally:
                     pipe.drop_cached(path)
                 self.t_pipe += time.perf_counter() - t0
+                self.image_dev = image_dev
                 yield path, (int(image_dev.shape[0]), int(image_dev.shape[1])), packed, scores, classes, tabs
+        self.image_dev = None
         pipe.clear_cache()
 
 
-def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id, boundary=None, report=None):
+def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tables, to_dataset_id, boundary=None, report=None, maps=None):
     """Every test image through the inference pipeline and the scorer; ``(per_image, (reads, pipeline, scoring) seconds)``."""
     system_logger.info(f"Evaluating the inference pipeline on {len(recs)} test images of {dataset_name} (rcnn {rcnn}, threshold {threshold})")
     runner = PipelineRunner(dataset_name, metadata, split_dir, rcnn, threshold)
@@ -593,17 +661,18 @@ def _run_pipeline(dataset_name, recs, metadata, split_dir, rcnn, threshold, tabl
     for ri, (_, hw, packed, scores, classes, tabs) in enumerate(runner.instances([rec["file_name"] for rec in recs])):
         t0 = time.perf_counter()
         per_image[ri] = _score_pipeline_image(ops, recs[ri], hw, packed, scores, classes, tabs, tables, to_dataset_id, runner.score_frame, boundary,
-                                              report)
+                                              report, maps=maps, image=runner.image_dev if maps is not None else None)
         t_score += time.perf_counter() - t0
     return per_image, (runner.t_read, runner.t_pipe, t_score)
 
 
 def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, tabs, tables, to_dataset_id, score_frame: Optional[str] = None,
-                          boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None) -> dict:
+                          boundary: Optional[Tuple[float, Optional[int]]] = None, report: Optional[CE.OutlineReport] = None,
+                          maps: Optional[CE.ErrorMaps] = None, image: Optional[torch.Tensor] = None) -> dict:
     """Pipeline mode: one image's final instances through :func:`_score`.  The detections' pixel counts and boxes are already on
     the host (``tabs``), so everything the host needs comes over in the scorer's ONE copy.  Dispatches on what ``final_instances``
     handed over: planes are scored on planes, a :class:`CropMaskSet` on rooms (``score_frame`` decides for an image that kept no
-    instance).  ``boundary`` / ``report``: as for :func:`_score`."""
+    instance).  ``boundary`` / ``report`` / ``maps`` / ``image``: as for :func:`_score`."""
     H, W = int(rec["height"]), int(rec["width"])
     if tuple(int(v) for v in hw) != (H, W):
         raise ValueError(f"{rec['file_name']}: image is {tuple(hw)}, the annotation says {(H, W)}")
@@ -618,4 +687,4 @@ def _score_pipeline_image(ops: MaskOps, rec: dict, hw, packed, scores, classes, 
     else:
         ops.set_frame_width(W)
         frame = _PlaneFrame(ops, H, W, packed.contiguous(), torch.from_numpy(d_bbox).to(ops.device)) if n else _PlaneFrame.empty(ops, H, W)
-    return _score(frame, rec, det, tables, to_dataset_id, boundary, report)
+    return _score(frame, rec, det, tables, to_dataset_id, boundary, report, maps=maps, image=image)

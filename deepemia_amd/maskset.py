@@ -309,6 +309,54 @@ def _launch_outline(ops: "MaskOps", entry: str, det_source: Sequence[Optional[to
     return OutlineAgreement(records, pairs, det, gt)
 
 
+def _launch_error_map(ops: "MaskOps", entry: str, det_source: Sequence[Optional[torch.Tensor]], D: int, d_state,
+                      gt_source: Sequence[Optional[torch.Tensor]], G: int, g_state, H: int, W: int, image: torch.Tensor,
+                      alpha, line, palette) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One error-map stage, enqueued without a wait: ``(dst [H, W, 3] u8, counts [4] i64)`` on the device.  ``entry`` with the
+    leading word-source arguments of both sides, as for :func:`_launch_outline`: ``demia_mask_error_map`` with planes ``(packed,
+    bbox)`` or ``demia_crop_error_map`` with crops ``(payload, room, offsets, bbox)``.  ``d_state`` / ``g_state`` are host arrays and
+    go up in ONE upload.  Every argument is checked before anything is allocated or launched: ValueError."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, np.integer)) or not (0 <= int(alpha) <= 256):
+        raise ValueError(f"error_map: alpha must be an integer from 0 to 256, got {alpha!r}")
+    if isinstance(line, bool) or not isinstance(line, (int, np.integer)) or not (1 <= int(line) <= 4):
+        raise ValueError(f"error_map: line must be an integer from 1 to 4, got {line!r}")
+    if palette is None:
+        from .cocoeval import ERROR_MAP_PALETTE          # (the one table of the defaults)
+        palette = ERROR_MAP_PALETTE
+    try:
+        pal = np.asarray(palette)
+        ok = pal.shape == (8, 3) and pal.dtype.kind in "iu" and int(pal.min()) >= 0 and int(pal.max()) <= 255
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("error_map: the palette must be 8 BGR triples of bytes")
+    pal = np.ascontiguousarray(pal, dtype=np.uint8)
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.device != ops.device or \
+            tuple(image.shape) not in ((H, W), (H, W, 1), (H, W, 3)):
+        got = tuple(image.shape) if isinstance(image, torch.Tensor) else type(image).__name__
+        raise ValueError(f"error_map: the image must be a uint8 device tensor of the frame, [{H}, {W}] or [{H}, {W}, 1 | 3], got {got}")
+    if not (0 < H <= 65535 and 0 < W <= 65535):
+        raise ValueError(f"error_map: a frame of {(H, W)}")
+    states = []
+    for name, st, n, top in (("d_state", d_state, D, 2), ("g_state", g_state, G, 3)):
+        st = np.asarray(st).reshape(-1)
+        if len(st) != n or (n and (st.dtype.kind not in "iu" or int(st.min()) < 0 or int(st.max()) > top)):
+            raise ValueError(f"error_map: {name} must be {n} integers from 0 to {top}")
+        states.append(st.astype(np.int32))
+    image = image.contiguous()
+    C = 3 if image.dim() == 3 and int(image.shape[2]) == 3 else 1
+    dev = ops.device
+    st_d = ops.upload(np.concatenate(states)) if D + G else torch.zeros((0,), dtype=torch.int32, device=dev)
+    dst = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    counts = torch.empty((4,), dtype=torch.int64, device=dev)
+    partial = torch.empty((int(ops.lib.demia_error_map_tiles(H, W)), 4), dtype=torch.int64, device=dev)
+    _lib.check(getattr(ops.lib, entry)(*(_lib.ptr(t) for t in det_source), _lib.ptr(st_d[:D]) if D else 0, D,
+                                       *(_lib.ptr(t) for t in gt_source), _lib.ptr(st_d[D:]) if G else 0, G, H, W, _lib.ptr(image), C,
+                                       _lib.ptr(dst), int(alpha), int(line), pal.ctypes.data, _lib.ptr(partial), _lib.ptr(counts),
+                                       ops._stream()), entry)
+    return dst, counts
+
+
 class PlanePool:
     """Mask planes that stay ZERO outside per-slot boxes (``demia_mask_gather_regions_pooled``): a gather into the pool
     writes the union of a slot's previous box and its new one instead of whole 512-KiB planes.  The planes handed out are
@@ -727,6 +775,25 @@ class MaskOps:
             raise ValueError(f"outline_agreement: planes of {wpr} words per row are not {W} pixels wide")
         return _launch_outline(self, "demia_mask_outline_agreement", (det_packed, det_bbox), D, det_area, (gt_packed, gt_bbox), G, gt_area,
                                H, self._w(det_packed) if W is None else int(W), pairs)
+
+    def error_map(self, det_packed: torch.Tensor, det_bbox: torch.Tensor, d_state, gt_packed: torch.Tensor, gt_bbox: torch.Tensor,
+                  g_state, image: torch.Tensor, alpha: int, line: int, palette=None, W: Optional[int] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The error map of two plane sets over one frame on ``image`` (``demia_mask_error_map``; the definitions are in
+        ``include/deepemia_hip.h``): ``(dst [H, W, 3] uint8 BGR, counts [4] int64 = agree, excess, missing, ignored pixels)`` on the
+        device, enqueued without a wait; ``image`` (uint8 ``[H, W]``, ``[H, W, 1]`` or ``[H, W, 3]`` BGR, on the device) and the planes
+        are left as they are.  ``det_bbox`` / ``gt_bbox``: any superset of the tight boxes, on the device; ``d_state`` (0 not drawn,
+        1 matched, 2 unmatched) / ``g_state`` (0 skip, 1 matched, 2 missed, 3 crowd): host arrays; ``alpha`` 0 .. 256; ``line`` 1 .. 4;
+        ``palette``: 8 BGR triples (default ``cocoeval.ERROR_MAP_PALETTE``); ``W``: the frame's pixel width (default:
+        ``set_frame_width``'s rule).  ValueError for a bad argument, before any launch."""
+        D, H, wpr = (int(v) for v in det_packed.shape)
+        G = int(gt_packed.shape[0])
+        if tuple(gt_packed.shape[1:]) != (H, wpr):
+            raise ValueError(f"error_map: planes of {tuple(gt_packed.shape[1:])} against planes of {(H, wpr)}")
+        if W is not None and (int(W) + 31) // 32 != wpr:
+            raise ValueError(f"error_map: planes of {wpr} words per row are not {W} pixels wide")
+        return _launch_error_map(self, "demia_mask_error_map", (det_packed, det_bbox), D, d_state, (gt_packed, gt_bbox), G, g_state,
+                                 H, self._w(det_packed) if W is None else int(W), image, alpha, line, palette)
 
 
 class ContourSet:

@@ -872,6 +872,51 @@ int demia_crop_outline_agreement(const uint32_t* det_payload, const int32_t* det
                                  int64_t P, const int64_t* chunk_off /* [2 P + 1] */, int64_t n_chunks,
                                  int32_t* out /* [P, 2, 136] */, void* stream);
 
+/* demia_mask_error_map / demia_crop_error_map = the error map of one image of the evaluate task (`--task evaluate --visualize`; not
+ * the reference's Detectron2 Visualizer picture, whose look is not reproduced): the detections over the ground truth, painted from
+ * the packed words of both sets.  The definitions, stated here once:
+ *   inputs   a frame of H x W pixels; src u8 [H, W, C], C = 1 (gray) or 3 (BGR); dst u8 [H, W, 3] BGR, a buffer distinct from src;
+ *           D detections and G annotations over the frame, from the same word source, with boxes (any superset of the tight boxes
+ *           that is zero outside it, -1 = empty) and states
+ *             d_state [D] i32   0 = not drawn and not counted, 1 = matched, 2 = unmatched (spurious)
+ *             g_state [G] i32   0 = skip, 1 = matched, 2 = missed, 3 = crowd region        (any other value: as 0)
+ *           alpha in 0 .. 256; the line width t in 1 .. 4; a palette of 8 BGR triples.
+ *   sets     Dall = the union of the detections of state 1 or 2, Gall = the union of the annotations of state 1 or 2, Gc = the union
+ *           of the annotations of state 3.  Bits of mask words beyond column W - 1 are nobody's pixels.
+ *   fill class of a pixel, the first that applies:  agree  in Dall & Gall;  ignored  in (Dall & Gc) \ Gall, counted and NOT filled;
+ *           excess  in Dall \ Gall \ Gc;  missing  in Gall \ Dall;  else none.
+ *   base     b = src for C = 3, the gray byte in all three channels for C = 1.
+ *   fill     a pixel of class agree, excess or missing is (b_c * (256 - alpha) + colour_c * alpha + 128) >> 8 per channel; every
+ *           other pixel is b.
+ *   outline  outline_t(m) = m \ erode_t(m), erode_t the erosion by the (2t + 1) x (2t + 1) square, pixels outside the frame counting
+ *           as not set: a mask thinner than 2t + 1 is all outline, and a mask on the frame's edge has outline there.
+ *   lines    an outline pixel is painted SOLID over the fill, in the colour of the highest class it belongs to:  1 unmatched
+ *           detection,  2 missed annotation,  3 matched detection,  4 matched annotation,  5 crowd region.
+ *   palette  [8, 3] u8 BGR: agree, excess, missing, unmatched-detection line, missed-annotation line, matched-detection line,
+ *           matched-annotation line, crowd line.  (The defaults are cocoeval.ERROR_MAP_PALETTE, and nowhere else.)
+ *   counts   [4] i64 = the pixels of class agree, excess, missing, ignored -- of the FILL classes, whatever the lines cover.
+ * Nothing depends on the order of the masks within a state, so dst and counts are unique: integers, exact.
+ * The entries: palette is a HOST pointer to the 24 bytes (they and the scalars travel by value with the launch); partial is the
+ * caller's [demia_error_map_tiles(H, W), 4] i64, one row of counts per tile, every row written; counts is written, not added to.
+ * One workgroup of 256 threads per tile of 32 rows x 8 word columns: the masks of both sets whose boxes meet the tile are found 256
+ * at a time by ballot and taken one after the other (no list, no limit on how many meet a tile), each through LDS -- its words over
+ * the tile and a halo of t rows and one word column, the erosion along the rows, then down the columns -- into eight 32-pixel
+ * accumulators per thread (three unions, five line classes); a second kernel of one workgroup sums the partial rows.  A word outside
+ * a mask's box, its view (crops: its room) or the frame is a zero operand and is never fetched; the tile is never clipped to a view.
+ * The mask words and src are only read; nothing but dst, partial and counts is written.  Boolean word operations, popcounts and the
+ * integer blend; no global atomics, plain vector stores.  D == 0 and G == 0 are valid: dst is b and the counts are 0 when both are.
+ * H, W <= 65535.  Two launches, no allocation, one stream, capturable. */
+int64_t demia_error_map_tiles(int H, int W);
+int demia_mask_error_map(const uint32_t* det, const int32_t* det_bbox, const int32_t* d_state /* [D] */, int64_t D, const uint32_t* gt,
+                         const int32_t* gt_bbox, const int32_t* g_state /* [G] */, int64_t G, int H, int W, const uint8_t* src, int C,
+                         uint8_t* dst, int alpha, int line, const uint8_t* palette /* host, [8, 3] */, int64_t* partial /* [tiles, 4] */,
+                         int64_t* counts /* [4] */, void* stream);
+int demia_crop_error_map(const uint32_t* det_payload, const int32_t* det_room, const int64_t* det_offsets, const int32_t* det_bbox,
+                         const int32_t* d_state /* [D] */, int64_t D, const uint32_t* gt_payload, const int32_t* gt_room,
+                         const int64_t* gt_offsets, const int32_t* gt_bbox, const int32_t* g_state /* [G] */, int64_t G, int H, int W,
+                         const uint8_t* src, int C, uint8_t* dst, int alpha, int line, const uint8_t* palette /* host, [8, 3] */,
+                         int64_t* partial /* [tiles, 4] */, int64_t* counts /* [4] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
